@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- IQ->bits throughput of the MI355X-native path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one full pass of the hot path over one synthetic capture that is already resident in HBM:
 IQ (complex64) -> demodulated signal (Signal.qad, materialised, stays in HBM) -> pulse table -> bits / pauses /
@@ -11,7 +11,7 @@ since round 6: the tail's kernels store the pulse-table rows into a staging blob
 blob while the bits are expanded, the last kernel stores the small head (header, pauses, offsets, packed bits) into the host blob itself
 (kernel stores into pinned memory beside the next hot kernel cost it 10 us per pass) --, and `value` counts K steps
 INCLUDING the delivery of all K (the timed region ends when the last step's results are on the host);
-the device-only figure of the same steps is config.device_only_ms_per_step.  Workload at N=1: BASELINE.json configs[1]
+the device-only figure of the same steps is config.device_only_ms_per_step (--full).  Workload at N=1: BASELINE.json configs[1]
 ("1 GiB synthetic complex64 2-FSK @ 100 samples/symbol, single MI355X") on the bytes SURVEY.md §8(d) config 2
 specifies (128 segments of 2^20 samples: numpy-seeded bits through modulate_c + numpy-seeded AWGN, see
 urh_amd/synth.py:spec_fsk_capture); for N>1 every rank holds a 1 GiB sample-contiguous shard of one N-GiB capture
@@ -20,7 +20,10 @@ urh_amd/synth.py:spec_fsk_capture); for N>1 every rank holds a 1 GiB sample-cont
 `python bench.py --gpus N` with N > 1 starts its own ranks (it re-executes itself under torch.distributed.run,
 one process per GPU over RCCL) unless it already runs inside such a launch (WORLD_SIZE set).
 
-Prints ONE JSON line on rank 0 (see the driver contract) with extra objects:
+A plain run sets up, warms up, times the K steps and prints the line: metric / value / unit / ms_per_step, the workload in `config`
+and the headline's own fraction of HBM peak in `roofline`.  --dump-outputs DIR writes the last timed step's outputs (pulse table,
+bits, pauses, offsets, bit_sample_pos, a seeded sample of qad) as DIR/<name>.npy; the capture is seeded, so two builds can be compared
+output for output.  Everything else is measured and checked with --full only, which adds to the line:
   roofline      the dominant kernel (k_demod_runs_bp: demodulation + run segmentation) against HBM peak;
                 achieved = algorithmic bytes (12 B/sample) / mean kernel time measured with HIP events
                 attached to the kernel's dispatch on its launch stream, in K pipelined device-only steps right behind the timed
@@ -854,6 +857,57 @@ def sharded_self_check(torch, dist, pipe, iq, p, rank, world, local_rank, fir_ta
 
 
 
+DUMP_LIMIT_BYTES = 56 << 20      # --dump-outputs: all files together (under 64 MB with room for headers and block starts)
+DUMP_BLOCK = 1 << 15             # a sampled array keeps whole blocks of this many rows (neighbours stay comparable)
+DUMP_QAD_BLOCKS = 64             # qad (4 B per sample, 512 MiB per GiB of capture): 64 blocks = 2^21 samples, 8 MiB
+DUMP_SEED = 20260
+FLAT_NAMES = ("bits", "msg_off", "pauses", "bit_sample_pos", "pos_off")      # BitsResult.flat() / HostBits.flat()
+
+
+def dump_block_starts(n, blocks, seed=DUMP_SEED):
+    """Fixed, seeded choice of `blocks` whole blocks of DUMP_BLOCK rows out of n (sorted start rows); None: keep all n rows."""
+    import numpy as np
+    if n <= blocks * DUMP_BLOCK:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(n // DUMP_BLOCK, blocks, replace=False)).astype(np.int64) * DUMP_BLOCK
+
+
+def write_dump(dirname, arrays, prefix=""):
+    """--dump-outputs: every array as <dirname>/<prefix><name>.npy, float32 where that holds its values exactly (float32, 8/16-bit
+    integers), else float64.  Arrays too large for DUMP_LIMIT_BYTES in all are replaced by a seeded sample of whole blocks of rows
+    (<name>_starts.npy: the first row of each block)."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = a.astype(np.float32 if a.dtype == np.float32 or (a.dtype.kind in "iub" and a.dtype.itemsize <= 2) else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        for name in sorted(out, key=lambda k: -out[k].nbytes):
+            a = out[name]
+            if total <= DUMP_LIMIT_BYTES:
+                break
+            room = DUMP_LIMIT_BYTES - (total - a.nbytes)
+            starts = dump_block_starts(len(a), max(1, room // max(1, a[:1].nbytes * DUMP_BLOCK)))
+            if starts is None:
+                continue
+            out[name] = np.concatenate([a[s:s + DUMP_BLOCK] for s in starts])
+            out[name + "_starts"] = starts.astype(np.float64)
+            total += out[name].nbytes + out[name + "_starts"].nbytes - a.nbytes
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, prefix + name + ".npy"), a)
+
+
+def qad_sample(n, read):
+    """The demodulated signal of a step, sampled: read(start, count) -> float32 numpy.  Returns (sample, block starts)."""
+    import numpy as np
+    starts = dump_block_starts(n, DUMP_QAD_BLOCKS)
+    if starts is None:
+        return read(0, n), np.zeros(1)
+    return np.concatenate([read(int(s), DUMP_BLOCK) for s in starts]), starts.astype(np.float64)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` (N > 1) from a bare interpreter: become `python -m torch.distributed.run ... bench.py ...`."""
     with socket.socket() as s:
@@ -895,7 +949,13 @@ def main():
                          "capture (+ the reference on rank 0's shard), then a short line -- under a minute, for a first lease that may be short")
     ap.add_argument("--no-pmc", action="store_true", help="do not launch the two rocprofv3 --pmc children for roofline.traffic (quote the committed profile)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: latencies, the upload, variants, the device-only and un-pipelined loops, roofline "
+                         "(live PMC), the CPU baseline with the parity record, the other configurations, the sharded self-check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64; qad as a seeded sample of blocks)")
     args = ap.parse_args()
+    full = args.full
     if args.pmc_child:
         return pmc_child(args)
 
@@ -1018,10 +1078,10 @@ def main():
         res = step()
     pipe.ctx.join()
     torch.cuda.synchronize()
-    # latency of ONE step with nothing overlapped (device only), and the same plus the D2H copy of the WIDE outputs (int64 pulse table,
-    # one byte per bit, int64 bit_sample_pos -- the round-2 format, kept for comparison; qad stays in HBM)
+    # --full: latency of ONE step with nothing overlapped (device only), and the same plus the D2H copy of the WIDE outputs (int64 pulse
+    # table, one byte per bit, int64 bit_sample_pos -- the round-2 format, kept for comparison; qad stays in HBM)
     lat, lat_d2h = [], []
-    for _ in range(5):
+    for _ in range(5 if full else 0):
         torch.cuda.synchronize()
         t_l = time.perf_counter()
         res = step()
@@ -1035,7 +1095,7 @@ def main():
     import gc
     gc.collect()
     gc.disable()
-    if not sharded and not args.no_d2h:
+    if full and not sharded and not args.no_d2h:
         pinned = {}
         for _ in range(6):
             torch.cuda.synchronize()
@@ -1046,7 +1106,7 @@ def main():
         lat_d2h = lat_d2h[1:]                               # the first call allocates the pinned buffers
         d2h_bytes_wide = int(sum(x.nbytes for x in host_out))
         del pinned, host_out
-    latency_ms = min(lat) * 1e3
+    latency_ms = min(lat) * 1e3 if lat else None
 
     # Anything slow between the clock ramp and a timed region lets the part's clocks fall again (round 3, profiles/HISTORY.md: 1 ms of idling
     # before K = 20 passes costs 3 %, 5 ms 13 %): the profile records' events (a hipEventCreate each) and the process group's first
@@ -1087,6 +1147,7 @@ def main():
     # ---- the headline (N = 1): K steps through the capture stream, D2H of every step's compact outputs included ---------------------
     stream_rec = {}
     last_host = None
+    dump = None                                              # --dump-outputs: name -> the last timed step's array
     headline_dt = None
     kernel_ms = []
     ramp_passes = 0
@@ -1107,13 +1168,14 @@ def main():
                     out.append(r)
             return out + st.flush()
         one, one_tp = [], []
-        for mode, acc in ((1, one), (0, one_tp)):            # ONE capture start to finish, nothing to overlap with: the stream in its latency setting
-            pipe.ctx.set_tuning("stream_latency", mode)      # (an idle pipeline: the tail in segments beside the hot kernel) and in the
-            for _ in range(6):                               # throughput setting the K-step loop below runs in (staged passes)
+        for mode, acc in ((1, one), (0, one_tp)) if full else ():    # ONE capture start to finish, nothing to overlap with: the stream in its
+            pipe.ctx.set_tuning("stream_latency", mode)      # latency setting (an idle pipeline: the tail in segments beside the hot kernel) and
+            for _ in range(6):                               # in the throughput setting the K-step loop below runs in (staged passes)
                 torch.cuda.synchronize()
                 t_l = time.perf_counter()
                 stream_steps(1)
                 acc.append(time.perf_counter() - t_l)
+        pipe.ctx.set_tuning("stream_latency", 0)
         ramp_passes = ramp(lambda: stream_steps(10))
         torch.cuda.synchronize()
         # (no timing events in this loop: the dispatch-attached pair costs 5-7 us per pass while a profile record is open; the hot kernel's
@@ -1124,44 +1186,55 @@ def main():
         torch.cuda.synchronize()
         headline_dt = time.perf_counter() - t0
         kernel_ms = pipe.ctx.profile_end()
-        # where the host's time goes in such a loop (a second, untimed run of the same K steps): inside push() -- which blocks until the
-        # tail of the pass before last has finished -- and between two pushes (Python: wrapping the result)
-        t_in, t_out, t_prev = [], [], None
-        for _ in range(args.steps):
-            ta = time.perf_counter()
-            if t_prev is not None:
-                t_out.append(ta - t_prev)
-            st.push(iq)
-            t_prev = time.perf_counter()
-            t_in.append(t_prev - ta)
-        st.flush()
-        torch.cuda.synchronize()
-        t_in.sort(); t_out.sort()
-        host_rec = {"push_us_median": round(t_in[len(t_in) // 2] * 1e6, 1), "push_us_min": round(t_in[0] * 1e6, 1),
-                    "between_pushes_us_median": round(t_out[len(t_out) // 2] * 1e6, 1)}
         assert len(results) == args.steps and [r.seq for r in results[-3:]] == sorted(r.seq for r in results[-3:])
         last_host = results[-1].check()
-        stream_stats = st.stats()
-        stream_rec = {"single_capture_incl_compact_d2h_ms": round(min(one) * 1e3, 4),
-                      "single_capture_setting": "CaptureStream(latency=True) / tuning stream_latency=1: a pass that finds the pipeline idle runs its tail in 7 rows "
-                                                "segments + 1 bits segment beside the hot kernel; the K-step loop runs in the throughput setting (staged passes), in "
-                                                "which one capture alone takes single_capture_throughput_setting_ms",
-                      "single_capture_throughput_setting_ms": round(min(one_tp) * 1e3, 4), "d2h_bytes_per_step": last_host.blob_bytes + 40,
-                      "host_loop": host_rec, "stream_stats": stream_stats,
-                      "d2h_format": "compact blob: uint16 length (rows of 65535 samples and more through an escape list) + int8 state per pulse-table row, packed bits, int64 pauses / message offsets "
-                                    "(include/urhgpu.h); bit_sample_pos derived on the host from the shipped pulse table when asked for"}
-        # the last timed step's outputs for the parity record: host copies of the blob's sections + its qad read back from HBM
         import numpy as np
         from urh_amd import _lib as _ulib
         import ctypes as C
-        host_copy = {"ppseq": last_host.ppseq(), "flat": last_host.flat(), "counts": (last_host.n_rows, last_host.n_msg, last_host.n_bits, last_host.n_pos)}
+        if args.dump_outputs:                                # the last timed step's outputs, before a later pass can reuse their buffers
+            dump = {"ppseq": last_host.ppseq(), **dict(zip(FLAT_NAMES, last_host.flat()))}
+            if want_qad and last_host.d_qad_ptr:
+                def read_qad(s, k):
+                    a = np.empty(k, np.float32)
+                    _ulib.check(_ulib.load().urhgpu_memcpy_to_host(pipe.ctx.handle, C.c_void_p(last_host.d_qad_ptr + 4 * s),
+                                                                   a.ctypes.data_as(C.c_void_p), k * 4))
+                    return a
+                dump["qad_sample"], dump["qad_sample_starts"] = qad_sample(n, read_qad)
+        stream_rec = {"d2h_bytes_per_step": last_host.blob_bytes + 40, "stream_stats": st.stats(),
+                      "d2h_format": "compact blob: uint16 length (rows of 65535 samples and more through an escape list) + int8 state per pulse-table row, packed bits, int64 pauses / message offsets "
+                                    "(include/urhgpu.h); bit_sample_pos derived on the host from the shipped pulse table when asked for"}
+        host_copy = {"counts": (last_host.n_rows, last_host.n_msg, last_host.n_bits, last_host.n_pos)}
         qad_host = None
-        if want_qad and last_host.d_qad_ptr:
-            qad_host = np.empty(n, np.float32)
-            _ulib.check(_ulib.load().urhgpu_memcpy_to_host(pipe.ctx.handle, C.c_void_p(last_host.d_qad_ptr), qad_host.ctypes.data_as(C.c_void_p), n * 4))
+        if full:
+            # where the host's time goes in such a loop (a second, untimed run of the same K steps): inside push() -- which blocks until the
+            # tail of the pass before last has finished -- and between two pushes (Python: wrapping the result)
+            t_in, t_out, t_prev = [], [], None
+            for _ in range(args.steps):
+                ta = time.perf_counter()
+                if t_prev is not None:
+                    t_out.append(ta - t_prev)
+                st.push(iq)
+                t_prev = time.perf_counter()
+                t_in.append(t_prev - ta)
+            st.flush()
+            torch.cuda.synchronize()
+            t_in.sort(); t_out.sort()
+            host_rec = {"push_us_median": round(t_in[len(t_in) // 2] * 1e6, 1), "push_us_min": round(t_in[0] * 1e6, 1),
+                        "between_pushes_us_median": round(t_out[len(t_out) // 2] * 1e6, 1)}
+            stream_rec.update({"single_capture_incl_compact_d2h_ms": round(min(one) * 1e3, 4),
+                               "single_capture_setting": "CaptureStream(latency=True) / tuning stream_latency=1: a pass that finds the pipeline idle runs its tail in 7 rows "
+                                                         "segments + 1 bits segment beside the hot kernel; the K-step loop runs in the throughput setting (staged passes), in "
+                                                         "which one capture alone takes single_capture_throughput_setting_ms",
+                               "single_capture_throughput_setting_ms": round(min(one_tp) * 1e3, 4),
+                               "host_loop": host_rec, "stream_stats": st.stats()})
+            # the last timed step's outputs for the parity record: host copies of the blob's sections + its qad read back from HBM
+            host_copy.update({"ppseq": last_host.ppseq(), "flat": last_host.flat()})
+            if want_qad and last_host.d_qad_ptr:
+                qad_host = np.empty(n, np.float32)
+                _ulib.check(_ulib.load().urhgpu_memcpy_to_host(pipe.ctx.handle, C.c_void_p(last_host.d_qad_ptr), qad_host.ctypes.data_as(C.c_void_p), n * 4))
         # ---- one capture that starts ON THE HOST (pinned memory): bare H2D copy of the capture against upload + demodulation + results on
         # the host, the pieces demodulated as they land (urhgpu_stream_push_upload) -- SURVEY 8(d): "report H2D-inclusive time separately"
-        if not args.no_upload:
+        if full and not args.no_upload:
             try:
                 pinned = torch.empty(iq.shape, dtype=iq.dtype, pin_memory=True)
                 pinned.copy_(iq)
@@ -1195,7 +1268,7 @@ def main():
                 stream_rec["h2d_inclusive_error"] = repr(exc)[:200]
         st.close()
         # the same with bit_sample_pos computed on the device and shipped (uint32 per bit: 8.9 MB per GiB instead of 3.5)
-        if not args.no_device_loop:
+        if full and not args.no_device_loop:
             st = pipe.stream(n, p, want_qad=want_qad, want_pos=True)
             ramp(lambda: stream_steps(10))
             torch.cuda.synchronize()
@@ -1212,7 +1285,7 @@ def main():
             del r_np
             stream_rec["value_with_positions"] = round(n / stream_rec["ms_per_step_with_device_positions"] / 1e3, 1)
         del st, results
-        if not args.no_device_loop and not args.no_variants:
+        if full and not args.no_device_loop and not args.no_variants:
             try:
                 stream_rec["variants"] = variant_steps(torch, pipe, iq, p, n, args, ramp, host_copy)
             except Exception as exc:                          # noqa: BLE001 (the headline stands; the line says what went wrong)
@@ -1255,61 +1328,78 @@ def main():
                       "d2h_format": "compact blob of this rank's piece: int32 length + int8 state per pulse-table row, packed bits, int64 pauses / "
                                     "message offsets (include/urhgpu.h); bit_sample_pos derived on the host from the shipped pulse table when asked for"}
         host_copy = {"rows": host_piece.ppseq().copy(), "bits": host_piece.bits().copy(), "pauses": host_piece.pauses.copy()}
+        if args.dump_outputs:                                # this rank's piece of the last timed step, as it arrived on the host
+            dump = {"ppseq": host_copy["rows"], "bits": host_copy["bits"], "msg_off": host_piece.msg_off.copy(), "pauses": host_copy["pauses"]}
         pipe.engine.host_results = False
         pipe.ctx.join()
         torch.cuda.synchronize()
 
-    # ---- device only (outputs left in HBM): what round 2 reported as the headline ----------------------------------------------------
-    if use_stream and args.no_device_loop:
-        args_steps_dev = 1
-    else:
-        args_steps_dev = args.steps
-        rp_dev = ramp(lambda: device_steps(10))
-        if not use_stream and not sharded_host:
-            ramp_passes = rp_dev
-    if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    kernel_from_device_loop = not kernel_ms and not os.environ.get("URH_BENCH_NO_PROFILE") and args_steps_dev == args.steps
-    pipe.ctx.profile_begin(args.steps if kernel_from_device_loop else 0)
-    t0 = time.perf_counter()
-    res = device_steps(args_steps_dev)
-    torch.cuda.synchronize()
-    if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    if kernel_from_device_loop:
-        kernel_ms = pipe.ctx.profile_end()
-    else:
-        pipe.ctx.profile_end()
-    if dist:
-        t = torch.tensor([dt], dtype=torch.float64, device=_FLAG_DEV)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
-    device_only_ms = dt / args_steps_dev * 1e3
-    if headline_dt is None:
-        headline_dt = dt
+    # ---- device only (outputs left in HBM): what round 2 reported as the headline -- with --full, or when it is the timed path
+    # (--no-d2h, --no-pipeline) ------------------------------------------------------------------------------------------------------
+    device_only_ms = host_equals_device = None
+    if full or headline_dt is None:
+        if use_stream and args.no_device_loop:
+            args_steps_dev = 1
+        else:
+            args_steps_dev = args.steps
+            rp_dev = ramp(lambda: device_steps(10))
+            if not use_stream and not sharded_host:
+                ramp_passes = rp_dev
+        if dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        kernel_from_device_loop = not kernel_ms and not os.environ.get("URH_BENCH_NO_PROFILE") and args_steps_dev == args.steps
+        pipe.ctx.profile_begin(args.steps if kernel_from_device_loop else 0)
+        t0 = time.perf_counter()
+        res = device_steps(args_steps_dev)
+        torch.cuda.synchronize()
+        if dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        if kernel_from_device_loop:
+            kernel_ms = pipe.ctx.profile_end()
+        else:
+            pipe.ctx.profile_end()
+        if dist:
+            t = torch.tensor([dt], dtype=torch.float64, device=_FLAG_DEV)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t.item())
+        device_only_ms = dt / args_steps_dev * 1e3
+        if headline_dt is None:
+            headline_dt = dt
 
-    counts = res.host_counts()
-    res.check_capacity()
-    host_equals_device = None
-    if sharded_host:                                         # what arrived on the host is what the device-resident pass holds
-        import numpy as np
-        pc = res.piece()
-        host_equals_device = bool(np.array_equal(host_copy["rows"], pc["rows"]) and np.array_equal(host_copy["bits"], pc["bits"]) and
-                                  np.array_equal(host_copy["pauses"], pc["pauses"]))
-        assert host_equals_device, "host blob differs from the device-resident outputs"
-    if use_stream:
-        assert tuple(host_copy["counts"][:3]) == tuple(counts[:3]), (host_copy["counts"], counts)     # (the stream's blob ships no positions)
+        counts = res.host_counts()
+        res.check_capacity()
+        if sharded_host:                                         # what arrived on the host is what the device-resident pass holds
+            import numpy as np
+            pc = res.piece()
+            host_equals_device = bool(np.array_equal(host_copy["rows"], pc["rows"]) and np.array_equal(host_copy["bits"], pc["bits"]) and
+                                      np.array_equal(host_copy["pauses"], pc["pauses"]))
+            assert host_equals_device, "host blob differs from the device-resident outputs"
+        if use_stream:
+            assert tuple(host_copy["counts"][:3]) == tuple(counts[:3]), (host_copy["counts"], counts)     # (the stream's blob ships no positions)
+    elif use_stream:
+        counts = host_copy["counts"]
+    else:
+        counts = (host_piece.n_rows, host_piece.n_msg, host_piece.n_bits, host_piece.n_pos)
+    if args.dump_outputs and dump is None:                   # the device-resident loop was the timed one: its last step's outputs
+        if sharded:
+            pc = res.piece()
+            dump = {"ppseq": pc["rows"], "bits": pc["bits"], "msg_end": pc["msg_end"], "pauses": pc["pauses"], "bit_sample_pos": pc["pos"],
+                    "pos_end": pc["pos_end"]}
+        else:
+            dump = {"ppseq": res.ppseq(), **dict(zip(FLAT_NAMES, res.flat()))}
+            if res.qad is not None:
+                dump["qad_sample"], dump["qad_sample_starts"] = qad_sample(n, lambda s, k: res.qad[s:s + k].cpu().numpy())
 
     # For reference the N = 1 line also carries the same K steps run one after the other, nothing overlapped: step time
     # and the hot kernel's duration when it has the machine to itself.
     alone_ms, alone_kernel_ms = None, None
     ceiling = None
-    if not sharded and n % 8192 == 0:                    # (while the context is still pipelined: its CU-masked hot stream exists)
+    if full and not sharded and n % 8192 == 0:           # (while the context is still pipelined: its CU-masked hot stream exists)
         ceiling = copy_ceiling(torch, pipe, iq, n)
-    if not sharded and args.pipeline and not args.no_reference_loop:
+    if full and not sharded and args.pipeline and not args.no_reference_loop:
         pipe.ctx.join()
         torch.cuda.synchronize()
         pipe.ctx.set_pipelined(False)                    # the same context and buffers, passes one after the other from here on
@@ -1340,18 +1430,7 @@ def main():
         total_samples = n * world
         ms_per_step = headline_dt / args.steps * 1e3
         value = total_samples * args.steps / headline_dt / 1e6
-        k_ms = sum(kernel_ms) / max(len(kernel_ms), 1)
         bytes_per_sample = ALGO_BYTES_PER_SAMPLE if want_qad else 8
-        achieved = (n * bytes_per_sample) / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-        traffic = traffic_src = None
-        if want_qad and n == 128 * SEG:
-            if world == 1 and not force_sharded and not args.no_pmc and not args.no_extra:
-                traffic, traffic_src = pmc_traffic_live(args.segments, "k_demod_runs_bp<0, 4, 1, true")
-            if traffic is None:
-                why = traffic_src
-                traffic, traffic_src = pmc_traffic("k_demod_runs_bp<0, 4, 1, true")
-                if traffic is not None and why:
-                    traffic_src += f" [no live PMC pass: {why}]"
 
         def frac_of(ms):
             return round(n * bytes_per_sample / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if ms else None
@@ -1373,45 +1452,61 @@ def main():
                                         "region ends when every rank holds its last blob (SURVEY 8(d) window per rank)") if sharded_host else
                                        "K device-resident steps (outputs left in HBM)",
                        "samples_per_gpu": n, "samples_per_symbol": sps, "tolerance": tol, "noise_sigma": 0.05,
-                       "host_libm": __import__("urh_amd._lib", fromlist=["_lib"]).host_libm_verdict(warn=False),
                        "outputs": (("qad (HBM) + " if want_qad else "") + "pulse table + bits + pauses + message offsets on the host; bit_sample_pos NOT shipped in the "
                                    "headline steps (derived on the host from the shipped pulse table when asked for: HostBits.bit_sample_pos, compared with the "
                                    "reference's in `parity`); shipped as uint32 in ms_per_step_with_device_positions") if (use_stream or sharded_host) else
                                   (("qad+" if want_qad else "") + "ppseq+bits+pauses+bit_sample_pos, left in HBM"),
                        "rows": counts[0], "messages": counts[1], "bits": counts[2],
                        "steps_pipelined": args.pipeline, "clock_ramp_passes_before_timing": ramp_passes,
-                       "device_only_ms_per_step": round(device_only_ms, 4),
-                       "single_step_latency_ms": round(latency_ms, 4),
-                       "single_step_plus_wide_d2h_ms": round(min(lat_d2h) * 1e3, 4) if lat_d2h else None, "wide_d2h_bytes": d2h_bytes_wide,
                        **stream_rec,
-                       "unpipelined_ms_per_step": round(alone_ms, 4) if alone_ms is not None else None,
                        "rccl_world_size": world if dist else None,
                        "all_gathers_per_pass": (None if not sharded else (2 if halo_given else 3) + (1 if fir_taps is not None else 0)),
                        "collectives": (None if not sharded else type(pipe.comm).__name__),
                        "collectives_fallback_reason": (comm_fallback_reason if sharded else None),
-                       "host_blob_equals_device_outputs": host_equals_device,
-                       "sharded_parity": shard_parity, "parity_bit_exact": (shard_parity or {}).get("bit_exact") if sharded else None,
-                       "fir_halo": fir_halo_rec,
-                       "ranks": ranks_info},
-            "roofline": {"bound": "hbm", "kernel": "k_demod_runs_bp", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_unit": "bytes/launch",
-                         "traffic_source": traffic_src, "algorithmic_bytes": n * bytes_per_sample,
-                         "kernel_ms": round(k_ms, 4), "algorithmic_bytes_per_sample": bytes_per_sample,
-                         "kernel_timing": ("HIP events attached to the kernel's dispatch (hipExtLaunchKernelGGL: the kernel's own begin / end timestamps), K pipelined "
-                                           "device-only steps right after the timed region -- beside the previous step's tail, as in the timed region, whose loop carries "
-                                           "no events (they cost 5-7 us per pass)") if (use_stream or sharded_host) and not os.environ.get("URH_BENCH_HEADLINE_EVENTS") else
-                                          "HIP events attached to the kernel's dispatch, inside the timed region",
-                         "kernel_ms_unshared": round(alone_kernel_ms, 4) if alone_kernel_ms else None,
-                         "frac_unshared": frac_of(alone_kernel_ms),
-                         "copy_ceiling": ceiling,
-                         "copy_ceiling_gbs": max(v for k, v in ceiling.items() if k.startswith("hot_kernel_shape") and k.endswith("_gbs")) if ceiling else None,
-                         "frac_of_copy_ceiling": round(achieved / max(v for k, v in ceiling.items() if k.startswith("hot_kernel_shape") and k.endswith("_gbs")), 4)
-                         if ceiling else None,
-                         "end_to_end_frac": frac_of(ms_per_step),
-                         "end_to_end_device_only_frac": frac_of(device_only_ms),
-                         "end_to_end_single_capture_frac": frac_of(stream_rec.get("single_capture_incl_compact_d2h_ms"))},
+                       "ranks": ranks_info,
+                       "full": full},
+            # the headline's own fraction of HBM peak; the kernel's figures (device-only loop, live PMC passes) come with --full
+            "roofline": {"bound": "hbm", "kernel": "k_demod_runs_bp", "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "algorithmic_bytes": n * bytes_per_sample, "algorithmic_bytes_per_sample": bytes_per_sample,
+                         "end_to_end_frac": frac_of(ms_per_step)},
         }
-        if not args.no_cpu_baseline and world == 1 and not force_sharded:
+        if full:
+            k_ms = sum(kernel_ms) / max(len(kernel_ms), 1)
+            achieved = (n * bytes_per_sample) / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+            traffic = traffic_src = None
+            if want_qad and n == 128 * SEG:
+                if world == 1 and not force_sharded and not args.no_pmc and not args.no_extra:
+                    traffic, traffic_src = pmc_traffic_live(args.segments, "k_demod_runs_bp<0, 4, 1, true")
+                if traffic is None:
+                    why = traffic_src
+                    traffic, traffic_src = pmc_traffic("k_demod_runs_bp<0, 4, 1, true")
+                    if traffic is not None and why:
+                        traffic_src += f" [no live PMC pass: {why}]"
+            out["config"].update({
+                "host_libm": __import__("urh_amd._lib", fromlist=["_lib"]).host_libm_verdict(warn=False),
+                "device_only_ms_per_step": round(device_only_ms, 4),
+                "single_step_latency_ms": round(latency_ms, 4) if latency_ms is not None else None,
+                "single_step_plus_wide_d2h_ms": round(min(lat_d2h) * 1e3, 4) if lat_d2h else None, "wide_d2h_bytes": d2h_bytes_wide,
+                "unpipelined_ms_per_step": round(alone_ms, 4) if alone_ms is not None else None,
+                "host_blob_equals_device_outputs": host_equals_device,
+                "sharded_parity": shard_parity, "parity_bit_exact": (shard_parity or {}).get("bit_exact") if sharded else None,
+                "fir_halo": fir_halo_rec})
+            out["roofline"].update({
+                "achieved": round(achieved, 1), "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_unit": "bytes/launch",
+                "traffic_source": traffic_src, "kernel_ms": round(k_ms, 4),
+                "kernel_timing": ("HIP events attached to the kernel's dispatch (hipExtLaunchKernelGGL: the kernel's own begin / end timestamps), K pipelined "
+                                  "device-only steps right after the timed region -- beside the previous step's tail, as in the timed region, whose loop carries "
+                                  "no events (they cost 5-7 us per pass)") if (use_stream or sharded_host) and not os.environ.get("URH_BENCH_HEADLINE_EVENTS") else
+                                 "HIP events attached to the kernel's dispatch, inside the timed region",
+                "kernel_ms_unshared": round(alone_kernel_ms, 4) if alone_kernel_ms else None,
+                "frac_unshared": frac_of(alone_kernel_ms),
+                "copy_ceiling": ceiling,
+                "copy_ceiling_gbs": max(v for k, v in ceiling.items() if k.startswith("hot_kernel_shape") and k.endswith("_gbs")) if ceiling else None,
+                "frac_of_copy_ceiling": round(achieved / max(v for k, v in ceiling.items() if k.startswith("hot_kernel_shape") and k.endswith("_gbs")), 4)
+                if ceiling else None,
+                "end_to_end_device_only_frac": frac_of(device_only_ms),
+                "end_to_end_single_capture_frac": frac_of(stream_rec.get("single_capture_incl_compact_d2h_ms"))})
+        if full and not args.no_cpu_baseline and world == 1 and not force_sharded:
             host = iq.cpu().numpy()
             rec, ref_out = cpu_reference(host, p)
             out["cpu_baseline"] = rec
@@ -1429,7 +1524,7 @@ def main():
                 bo["bit_exact"] = bool(bo.get("equals_headline_outputs") and out["parity"]["rows_equal"] and out["parity"]["bits_equal"]
                                        and out["parity"]["msg_off_equal"] and out["parity"]["pauses_equal"])
             del host, ref_out
-        if not args.no_extra and world == 1 and not force_sharded:
+        if full and not args.no_extra and world == 1 and not force_sharded:
             del iq
             pipe.ctx.join()
             torch.cuda.synchronize()
@@ -1438,12 +1533,14 @@ def main():
             for key, ex in zip(("configs2_ook_fir", "configs4_psk_costas"), out["extra"]):
                 out["config"][key] = {"ms": ex.get("ms"), "ms_incl_d2h": ex.get("ms_incl_d2h"), "Msamples_per_s": ex.get("value"),
                                       "bit_exact": (ex.get("parity") or {}).get("bit_exact"), "error": ex.get("error")}
-    # ---- N > 1: the line proves itself -- stitched pieces against a single-GPU pass over the whole capture on rank 0 and against the
+    if dump is not None:
+        write_dump(args.dump_outputs, dump, prefix=f"rank{rank}_" if world > 1 else "")
+    # ---- N > 1 (--full): the line proves itself -- stitched pieces against a single-GPU pass over the whole capture on rank 0 and against the
     # reference on rank 0's shard; then the FIR-halo variant BASELINE.json configs[3] names (timed, checked the same way).  It comes LAST
     # and under a watchdog: the checks add collectives (gathers of the pieces and of the shards) that the timed region never needed, and a
     # rank that hangs or dies in them must not cost the run its line -- after URH_BENCH_CHECK_TIMEOUT seconds (default 240) rank 0 prints
     # the line it has, marked as unchecked, and every rank exits.
-    if sharded and not args.no_sharded_check:
+    if full and sharded and not args.no_sharded_check:
         import threading
         line = {"out": out if rank == 0 else None}
 

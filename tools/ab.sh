@@ -14,6 +14,6 @@ else
 fi
 line() { python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); c=d['config']; print(d['ms_per_step'], d['roofline']['kernel_ms'], c.get('single_capture_incl_compact_d2h_ms'), c.get('ms_per_step_with_device_positions'))"; }
 for i in 1 2 3; do
-  echo "default : $(python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-upload --no-pmc --no-variants 2>/dev/null | line)"
-  echo "variant : $(env $ENVV $LIB python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-upload --no-pmc --no-variants 2>/dev/null | line)   [$ENVV $LIB]"
+  echo "default : $(python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-upload --no-pmc --no-variants 2>/dev/null | line)"
+  echo "variant : $(env $ENVV $LIB python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-upload --no-pmc --no-variants 2>/dev/null | line)   [$ENVV $LIB]"
 done

@@ -7,12 +7,12 @@ TAG=${1:-r05f}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 G=gpurun_out/$TAG; mkdir -p $G
-python bench.py --steps 20 --warmup 5 > $G/bench.json 2> $G/bench.err
+python bench.py --full --steps 20 --warmup 5 > $G/bench.json 2> $G/bench.err
 tail -c 300 $G/bench.err
 for mode in pipelined unpipelined; do
   OUT=$R/$G/stats_$mode; mkdir -p $OUT
   if [ $mode = pipelined ]; then A="--no-d2h --no-reference-loop"; else A="--no-d2h --no-pipeline"; fi
-  (cd /tmp && TMPDIR=/tmp timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o b -- python $R/bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-extra --no-upload --no-pmc $A > $OUT/log.txt 2>&1)
+  (cd /tmp && TMPDIR=/tmp timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o b -- python $R/bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-extra --no-upload --no-pmc $A > $OUT/log.txt 2>&1)
   python tools/timeline.py $OUT --passes 12 > $G/timeline_$mode.txt 2>&1
   f=$(find $OUT -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && (head -1 $f; grep "urh::" $f) > $G/fsk_1gib_${mode}_kernel_stats.csv
@@ -56,7 +56,7 @@ for part in ook psk; do echo "== $part"; grep -v "^[WE]2026\|rocprofv3" gpurun_o
 python tools/dtype_probe.py 2>&1 | grep -v amdgpu.ids > $G/dtypes.txt
 python tools/deviation_probe.py 2>&1 | grep -v amdgpu.ids > $G/deviation.txt
 # the sharded path on a 1-rank RCCL group, with its self-check and the FIR-halo record
-URH_BENCH_FORCE_SHARDED=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 5 > $G/bench_sharded_1rank.json 2> $G/bench_sharded_1rank.err
+URH_BENCH_FORCE_SHARDED=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --steps 20 --warmup 5 > $G/bench_sharded_1rank.json 2> $G/bench_sharded_1rank.err
 python - <<PY
 import json
 d = json.loads(open("$G/bench.json").read().strip().splitlines()[-1]); c = d["config"]; r = d["roofline"]

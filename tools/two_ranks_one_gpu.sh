@@ -33,4 +33,4 @@ except Exception as exc:
 PY
 }
 for N in 2 4 8; do run $N ranks${N}_one_gpu_selftest --selftest-only; done
-for N in 2 8; do run $N ranks${N}_one_gpu_bench --steps 3 --warmup 1 --no-variants; done
+for N in 2 8; do run $N ranks${N}_one_gpu_bench --full --steps 3 --warmup 1 --no-variants; done
