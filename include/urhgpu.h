@@ -401,7 +401,10 @@ int urhgpu_stream_wide_passes(urhgpu_stream *st, int64_t *n_passes);
  *     bits / pos may continue past the last one (the message closes on a later rank);
  *   - counts = {local rows, messages closed here, local bits, local positions}.
  * out->blob (FSK / other, not ASK: URHGPU_ERR_UNSUPPORTED): the finish phase also packs this rank's piece into the compact blob.
- * PSK (Costas loop) does not shard: URHGPU_ERR_UNSUPPORTED. */
+ * PSK (Costas loop, orders 2 and 4): two more phases come first, urhgpu_shard_costas_spec_dev and urhgpu_shard_costas_resolve_dev
+ * below; the halo is then the previous shard's last demodulated value (one float, exchanged after the resolve phase) and the runs
+ * phase segments the shard's Costas output.  urhgpu_shard_prelaunch_dev / urhgpu_shard_launch_dev: URHGPU_ERR_UNSUPPORTED for PSK,
+ * as every PSK phase on a pipelined context. */
 #define URHGPU_ROW_ABSORBED (-(INT64_C(1) << 62))
 #define URHGPU_SHARD_SUMMARY_BYTES 72 /* one shard summary (d_summary; d_summaries = world of them, back to back) */
 int urhgpu_shard_runs_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int64_t pos_base, int64_t n_total,
@@ -421,6 +424,30 @@ int urhgpu_shard_launch_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, 
 int urhgpu_shard_rows_dev(urhgpu_ctx *ctx, const void *d_summaries, int64_t *d_merge);
 int urhgpu_shard_bits_prepare_dev(urhgpu_ctx *ctx, const int64_t *d_merge_all, int64_t *d_flags);
 int urhgpu_shard_bits_finish_dev(urhgpu_ctx *ctx, const int64_t *d_flags_all);
+
+/* PSK across shards: the Costas loop carries its state {freq, phase} over the whole capture.  Each rank speculates its shard
+ * (candidate trajectories per 4096-sample chunk, as on one GPU) and reduces it to a fixed-size summary; the caller all-gathers the
+ * summaries and composes them -- a pure function of the gathered bytes that every rank evaluates alike (urh_amd/sharding.py
+ * costas_compose): rank 0 starts in {0.0f, 1.5f}; a shard without an un-gated sample passes the state on; otherwise the state is
+ * looked up BITWISE among the shard's first-chunk candidates and the composed chunk maps give its end state.  Where that chain
+ * breaks (no candidate starts in the state, or the map is broken) the rank whose start state is known resolves and contributes its
+ * true end state in one more all-gather (d_end_state); every rank takes the same number of rounds (<= world).  Exact by construction:
+ * states are compared on their bits and never assumed to have converged.
+ *   urhgpu_costas_halo_samples: raw samples before its shard that a rank > 0 must be handed (fewer where the capture starts
+ *       closer: min(this, pos_base - 1)); host arithmetic.
+ *   urhgpu_shard_costas_spec_dev: d_halo = the n_halo raw samples (capture dtype) immediately before the shard, NULL / 0 on rank 0;
+ *       out->qad (required) receives the shard's demodulated signal in the next phase (index 0 of rank 0: -4.0, as on one GPU);
+ *       d_summary: URHGPU_COSTAS_SUMMARY_BYTES out (layout: costas.hip, k_costas_shard_summary).
+ *   urhgpu_shard_costas_resolve_dev: start_state = HOST pointer to the shard's true start state {freq, phase} as float32 bits;
+ *       stitches from it (host-driven re-speculation rounds where the chain breaks inside the shard; synchronises the stream),
+ *       writes out->qad, and the true state after the shard's last sample to d_end_state (device, 2 x uint32; may be NULL).
+ *       urhgpu_ctx_costas_stats then reports the rank's chunks (by map / checkpoint / serial) and re-speculation rounds.
+ * Then urhgpu_shard_runs_dev (d_left_halo: the previous rank's last qad value, NULL on rank 0) and the later phases as above. */
+#define URHGPU_COSTAS_SUMMARY_BYTES 160
+int64_t urhgpu_costas_halo_samples(const urhgpu_params *p);
+int urhgpu_shard_costas_spec_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int64_t pos_base, int64_t n_total, int rank, int world,
+                                 const void *d_halo, int64_t n_halo, const urhgpu_params *p, const urhgpu_outputs *out, void *d_summary);
+int urhgpu_shard_costas_resolve_dev(urhgpu_ctx *ctx, const uint32_t *start_state, uint32_t *d_end_state);
 
 /* Magnitude chunk statistics for AutoInterpretation.detect_noise_level
  * (src/urh/ainterpretation/AutoInterpretation.py:60-91): chunks of `chunk` samples taken from the END

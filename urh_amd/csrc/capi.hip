@@ -359,6 +359,9 @@ struct ShardSession {
     const int64_t *d_row_base = nullptr;
     bool use_tile = false;         // everything but ASK: the tile tail over the table (pulse_table.hip), as on a single GPU
     TileTailMem tile;
+    // PSK: the rank's Costas pass (urhgpu_shard_costas_*), whose output the runs phase reads instead of the IQ
+    CostasShard costas;
+    int costas_phase = 0;          // 1: speculated (summary out), 2: resolved (the shard's qad written), 0: none / taken by the runs phase
 };
 
 // descriptor memory of the single-pass scans for pulse tables of up to cap_rows rows
@@ -1199,11 +1202,15 @@ static int shard_launch(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int6
     if (rank == 0 && pos_base != 0) return URHGPU_ERR_ARG;
     if (dtype_bytes(p->dtype) == 0) return URHGPU_ERR_DTYPE;
     URH_TRY(check_params(p, true));
-    if (p->mod == URHGPU_MOD_PSK) return URHGPU_ERR_UNSUPPORTED;      // the Costas loop does not shard
     if (((uintptr_t)d_iq & 15) || (out->qad && ((uintptr_t)out->qad & 7))) return URHGPU_ERR_ARG;
     URH_HIP(hipSetDevice(ctx->device));
     ShardSession *ss = session(ctx);
     if (!ss) return URHGPU_ERR_ARG;
+    // PSK: the runs are segmented from the shard's Costas output (resolved by urhgpu_shard_costas_resolve_dev), the route of a
+    // single-GPU PSK pass (digitize from qad); the halo is the previous shard's last demodulated value
+    const bool psk = (p->mod == URHGPU_MOD_PSK);
+    if (psk && (ctx->pipelined || part != 0)) return URHGPU_ERR_UNSUPPORTED;
+    if (psk && (ss->costas_phase != 2 || out->qad != ss->costas.out || n_local != ss->costas.n || d_iq != ss->costas.iq)) return URHGPU_ERR_ARG;
     ss->piped = ctx->pipelined;
     if (ss->piped) URH_TRY(begin_pipelined_pass(ctx)); else URH_TRY(join_tail(ctx));
     // ASK passes (generic tail: a dozen under-occupied launches and one more exchange) keep the caller's stream for the hot kernel and
@@ -1242,14 +1249,14 @@ static int shard_launch(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int6
     RunArgs &a = ss->run;
     memset(&a, 0, sizeof(a));
     URH_TRY(fill_thresholds(a, p));
-    a.in = d_iq; a.qad = out->qad; a.left_halo = d_left_halo; a.n = n_local; a.pos_base = pos_base;
+    a.in = psk ? (const void *)out->qad : d_iq; a.qad = psk ? nullptr : out->qad; a.left_halo = d_left_halo; a.n = n_local; a.pos_base = pos_base;
     a.chunk_len = pl.chunk_len; a.slab_stride = pl.slab_stride;
     a.noise_sqrd = p->noise_threshold * p->noise_threshold;
     a.noise_val = noise_for(p);
     a.tol = p->tolerance;
     a.lds_pad = !ctx->pipelined ? 0 : (ss->use_tile ? ctx->hot_lds_pad : ctx->hot_lds_pad_sharded);
     a.wide_int = ctx->tune_wide_int ? 1 : 0;
-    URH_TRY(max_magnitude_for(p->dtype, &a.max_magnitude));
+    if (!psk) URH_TRY(max_magnitude_for(p->dtype, &a.max_magnitude));
     a.chunks = ss->table + rank;               // this rank's chunks sit at table[rank .. rank + n_chunks)
     a.slab = ss->slab;
     a.launch_part = part;
@@ -1261,9 +1268,10 @@ static int shard_launch(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int6
         hot_done = g_hot_events.stop;
     }
     {
-        const int st = launch_demod_runs_iq(a, p->dtype, p->mod, out->qad != nullptr, s);
+        const int st = psk ? launch_runs_qad(a, s) : launch_demod_runs_iq(a, p->dtype, p->mod, out->qad != nullptr, s);
         if (st != URHGPU_OK) { g_hot_events = HotEvents(); return st; }
     }
+    ss->costas_phase = 0;
     if (hot_done && !g_hot_events.used) hot_done = nullptr;
     if (prof) URH_TRY(prof_end_record(ctx, s));
     else g_hot_events = HotEvents();
@@ -1281,6 +1289,7 @@ static int shard_launch(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int6
 
 int urhgpu_shard_prelaunch_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int64_t pos_base, int64_t n_total,
                                int rank, int world, const urhgpu_params *p, const urhgpu_outputs *out) {
+    if (p && p->mod == URHGPU_MOD_PSK) return URHGPU_ERR_UNSUPPORTED;    // PSK: urhgpu_shard_costas_* first, then urhgpu_shard_runs_dev
     URH_TRY(shard_launch(ctx, d_iq, n_local, pos_base, n_total, rank, world, nullptr, p, out, rank > 0 ? 1 : 0));
     ((ShardSession *)ctx->shard)->phase = -1;
     return URHGPU_OK;
@@ -1289,6 +1298,7 @@ int urhgpu_shard_prelaunch_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_loca
 int urhgpu_shard_launch_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int64_t pos_base, int64_t n_total,
                             int rank, int world, const void *d_left_halo, const urhgpu_params *p, const urhgpu_outputs *out) {
     if ((rank == 0) != (d_left_halo == nullptr)) return URHGPU_ERR_ARG;
+    if (p && p->mod == URHGPU_MOD_PSK) return URHGPU_ERR_UNSUPPORTED;    // PSK: urhgpu_shard_costas_* first, then urhgpu_shard_runs_dev
     URH_TRY(shard_launch(ctx, d_iq, n_local, pos_base, n_total, rank, world, d_left_halo, p, out, 0));
     ((ShardSession *)ctx->shard)->phase = -2;
     return URHGPU_OK;
@@ -1447,6 +1457,57 @@ int urhgpu_shard_bits_finish_dev(urhgpu_ctx *ctx, const int64_t *d_flags_all) {
     URH_HIP(hipGetLastError());
     ss->phase = 0;
     if (ss->piped) URH_TRY(end_pipelined_pass(ctx));
+    return URHGPU_OK;
+}
+
+// ---- PSK across shards: the rank's Costas pass in two phases around the summary exchange (include/urhgpu.h) ----------------------
+int64_t urhgpu_costas_halo_samples(const urhgpu_params *p) {
+    if (!p) return 0;
+    return costas_halo_samples(p);
+}
+
+int urhgpu_shard_costas_spec_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int64_t pos_base, int64_t n_total, int rank, int world,
+                                 const void *d_halo, int64_t n_halo, const urhgpu_params *p, const urhgpu_outputs *out, void *d_summary) {
+    if (!ctx || !p || !out || !d_iq || !out->qad || !d_summary) return URHGPU_ERR_ARG;
+    if (world < 1 || world > kMaxWorld || rank < 0 || rank >= world || n_local < 2 || pos_base < 0 || pos_base + n_local > n_total ||
+        n_total <= 2)
+        return URHGPU_ERR_ARG;
+    if (rank == 0 ? pos_base != 0 : pos_base < 2) return URHGPU_ERR_ARG;
+    if (p->mod != URHGPU_MOD_PSK) return URHGPU_ERR_ARG;
+    if (dtype_bytes(p->dtype) == 0) return URHGPU_ERR_DTYPE;
+    URH_TRY(check_params(p, true));
+    if (((uintptr_t)d_iq & 15) || ((uintptr_t)out->qad & 7)) return URHGPU_ERR_ARG;
+    if (ctx->pipelined) return URHGPU_ERR_UNSUPPORTED;
+    // the halo: every sample a walk back of chunk 0 may read -- all of them down to global sample 1 where the capture starts closer
+    const int64_t need = (rank == 0) ? 0 : std::min<int64_t>(costas_halo_samples(p), pos_base - 1);
+    if (rank == 0 ? (d_halo != nullptr || n_halo != 0) : (d_halo == nullptr || n_halo < need || n_halo > pos_base)) return URHGPU_ERR_ARG;
+    URH_HIP(hipSetDevice(ctx->device));
+    URH_TRY(join_tail(ctx));
+    ShardSession *ss = session(ctx);
+    if (!ss) return URHGPU_ERR_ARG;
+    ss->costas_phase = 0;
+    CostasShard &cs = ss->costas;
+    cs.iq = d_iq; cs.n = n_local; cs.out = out->qad; cs.p = *p;
+    cs.origin = (rank == 0) ? 1 : 0;
+    cs.halo_end = (rank == 0) ? nullptr : (const char *)d_halo + (size_t)n_halo * dtype_bytes(p->dtype);
+    cs.lo = (rank == 0) ? 1 : std::max<int64_t>(1 - pos_base, -n_halo);
+    cs.start1 = 1 - pos_base;
+    URH_TRY(ctx->aux.reserve(costas_scratch_bytes(n_local) + 1024));
+    ctx->aux.reset();
+    cs.scratch = ctx->aux.take(costas_scratch_bytes(n_local));
+    if (!cs.scratch) return URHGPU_ERR_ARG;
+    URH_TRY(launch_costas_shard_spec(ctx, cs, d_summary));
+    ss->costas_phase = 1;
+    return URHGPU_OK;
+}
+
+int urhgpu_shard_costas_resolve_dev(urhgpu_ctx *ctx, const uint32_t *start_state, uint32_t *d_end_state) {
+    if (!ctx || !start_state) return URHGPU_ERR_ARG;
+    ShardSession *ss = (ShardSession *)ctx->shard;
+    if (!ss || ss->costas_phase != 1) return URHGPU_ERR_ARG;
+    URH_HIP(hipSetDevice(ctx->device));
+    URH_TRY(launch_costas_shard_resolve(ctx, ss->costas, start_state[0], start_state[1], d_end_state));
+    ss->costas_phase = 2;
     return URHGPU_OK;
 }
 

@@ -34,6 +34,7 @@
 #include <algorithm>
 #include <math.h>
 #include <string.h>
+#include <type_traits>
 
 #include "cmul.hpp"
 #include "common.hpp"
@@ -49,6 +50,16 @@ struct CostasArgs {
     int warm;                // un-gated samples a candidate runs before its chunk (from the loop bandwidth, see launch_costas)
 };
 struct CostasState { float freq, phase; };
+// One rank's shard of a sharded capture (the SH instantiations below; include/urhgpu.h, "PSK across shards"): local sample i is
+// global sample pos_base + i, and the raw samples handed over with the shard (its left halo) are local samples -n_halo .. -1.
+// Chunks are laid out from the shard's start.
+struct CostasArgsSh : CostasArgs {
+    const void *halo_end;    // one past the halo: local sample i < 0 is read at halo_end[i] (nullptr on rank 0)
+    int64_t origin;          // first sample of chunk 0: 1 on rank 0 (global sample 0 is not part of the loop), 0 on the others
+    int64_t lo;              // lowest local sample a walk back reads: max(1 - pos_base, -n_halo)
+    int64_t start1;          // local index of global sample 1, where the loop starts in {0, 1.5}: 1 - pos_base
+};
+template <bool SH> using CostasArgsT = typename std::conditional<SH, CostasArgsSh, CostasArgs>::type;
 
 __device__ __forceinline__ float costas_clamp(float x) {      // :246-250 (NaN passes through: both comparisons are false)
     float r = (x > 1.0f) ? 1.0f : x;
@@ -216,41 +227,65 @@ __device__ __forceinline__ bool same_state(CostasState a, CostasState b) {
 }
 __device__ __forceinline__ int64_t chunk_begin(int64_t c) { return 1 + c * (int64_t)kChunk; }   // sample 0 is not part of the loop
 
+// What the SH (shard) instantiations read from CostasArgsSh; the single-GPU instantiations keep the constants of a whole capture.
+template <bool SH, class A> __device__ __forceinline__ int64_t chunk_begin_of(const A &a, int64_t c) {
+    if constexpr (SH) return a.origin + c * (int64_t)kChunk;
+    else return chunk_begin(c);
+}
+template <int DT, bool SH, class A> __device__ __forceinline__ float2 costas_at(const A &a, int64_t i) {
+    if constexpr (SH) return CostasLoad<DT>::at(i < 0 ? a.halo_end : a.iq, i);      // the halo: local samples < 0
+    else return CostasLoad<DT>::at(a.iq, i);
+}
+template <bool SH, class A> __device__ __forceinline__ int64_t walk_floor(const A &a) {
+    if constexpr (SH) return a.lo;
+    else return 1;
+}
+template <bool SH, class A> __device__ __forceinline__ int64_t loop_start(const A &a) {
+    if constexpr (SH) return a.start1;
+    else return 1;
+}
+template <bool SH, class A> __device__ __forceinline__ bool chunk0_exact(const A &a) {     // chunk 0 starts where the loop does
+    if constexpr (SH) return a.origin == 1;
+    else return true;
+}
+
 // Candidates of the chunks c >= c_from.  use_seed: all candidates start with freq = seed_freq (the true loop's own
 // frequency where the chain last broke) instead of the estimate from the data.
-template <int DT, int ORDER>
-__global__ __launch_bounds__(256) void k_costas_spec(const CostasArgs a, SpecBuffers b, int64_t n_chunks, int K, int64_t c_from,
+// SH (a shard): the walk back reads into the halo and stops at global sample 1, exactly where the single-GPU walk does.
+template <int DT, int ORDER, bool SH = false>
+__global__ __launch_bounds__(256) void k_costas_spec(const CostasArgsT<SH> a, SpecBuffers b, int64_t n_chunks, int K, int64_t c_from,
                                                       int use_seed, float seed_freq) {
     const int64_t gid = blockIdx.x * 256ll + threadIdx.x;
     const int64_t c = c_from + gid / K;
     const int k = (int)(gid % K);
     if (c >= n_chunks) return;
-    const int64_t s0 = chunk_begin(c);
+    const int64_t s0 = chunk_begin_of<SH>(a, c);
     // candidate k: phase 1.5 + (k - K/2) * spacing, spaced pi/2 (order 4, K = 8) or pi (order 2, K = 4): every lock point and its
     // twin 2*pi away; candidate K/2 has the reference's own initial phase 1.5
     const float spacing = (a.loop_order == 4) ? 1.57079632679489661923f : 3.14159265358979323846f;
     CostasState st{0.0f, 1.5f + (float)(k - K / 2) * spacing};
     float err = 0.0f;
     int64_t p = s0;
-    if (c == 0) {
+    if (c == 0 && chunk0_exact<SH>(a)) {
         st = CostasState{0.0f, 1.5f};                       // every candidate of chunk 0 is the true trajectory
     } else {
         int ungated = 0;
         const int64_t back = (int64_t)kWarmBackFactor * a.warm;
+        const int64_t floor = walk_floor<SH>(a);
         // walk back until `warm` un-gated samples lie between p and the chunk -- eight samples per round trip to memory
-        while (p > 1 && ungated < a.warm && s0 - p < back) {
+        while (p > floor && ungated < a.warm && s0 - p < back) {
             float2 g[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) g[j] = CostasLoad<DT>::at(a.iq, (p - 1 - j >= 1) ? p - 1 - j : 1);
+            for (int j = 0; j < 8; ++j) g[j] = costas_at<DT, SH>(a, (p - 1 - j >= floor) ? p - 1 - j : floor);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                if (p > 1 && ungated < a.warm && s0 - p < back) {
+                if (p > floor && ungated < a.warm && s0 - p < back) {
                     --p;
                     if (!costas_gated(g[j], a)) ++ungated;
                 }
             }
         }
-        if (p == 1) {
+        if (p == loop_start<SH>(a)) {
             st = CostasState{0.0f, 1.5f};                   // reached the start of the capture: exact, not a guess
         } else if (use_seed) {
             st.freq = seed_freq;
@@ -260,13 +295,13 @@ __global__ __launch_bounds__(256) void k_costas_spec(const CostasArgs a, SpecBuf
             // at freq 0 against an offset beyond the loop bandwidth needs thousands of samples to pull in; seeded, it
             // locks within the warm-up.  Heuristic only: a wrong seed costs time (serial fallback), never exactness.
             float ax = 0.0f, ay = 0.0f;
-            float2 prev = CostasLoad<DT>::at(a.iq, p);
+            float2 prev = costas_at<DT, SH>(a, p);
             bool prev_ok = !costas_gated(prev, a);
             const int64_t wend = (p + 512 < s0) ? p + 512 : s0;
             for (int64_t i0 = p + 1; i0 < wend; i0 += 8) {
                 float2 g[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) g[j] = CostasLoad<DT>::at(a.iq, (i0 + j < wend) ? i0 + j : wend - 1);
+                for (int j = 0; j < 8; ++j) g[j] = costas_at<DT, SH>(a, (i0 + j < wend) ? i0 + j : wend - 1);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     if (i0 + j < wend) {
@@ -290,11 +325,11 @@ __global__ __launch_bounds__(256) void k_costas_spec(const CostasArgs a, SpecBuf
             constexpr int PF = 4;                               // as in k_costas_run: the next four samples are on their way
             float2 cur[PF];
 #pragma unroll
-            for (int j = 0; j < PF; ++j) cur[j] = CostasLoad<DT>::at(a.iq, (p + j < s0) ? p + j : s0 - 1);
+            for (int j = 0; j < PF; ++j) cur[j] = costas_at<DT, SH>(a, (p + j < s0) ? p + j : s0 - 1);
             for (int64_t i = p; i < s0; i += PF) {
                 float2 nxt[PF];
 #pragma unroll
-                for (int j = 0; j < PF; ++j) { const int64_t q = i + PF + j; nxt[j] = CostasLoad<DT>::at(a.iq, (q < s0) ? q : s0 - 1); }
+                for (int j = 0; j < PF; ++j) { const int64_t q = i + PF + j; nxt[j] = costas_at<DT, SH>(a, (q < s0) ? q : s0 - 1); }
 #pragma unroll
                 for (int j = 0; j < PF; ++j) if (i + j < s0) costas_step_bf<DT == URHGPU_DT_F32, ORDER>(cur[j], st, err, a);
 #pragma unroll
@@ -322,14 +357,14 @@ __global__ __launch_bounds__(256) void k_costas_spec(const CostasArgs a, SpecBuf
 }
 
 // The chunk itself, one lane per distinct candidate: checkpoints, end state, un-gated sample count.
-template <int DT, int ORDER>
-__global__ __launch_bounds__(256) void k_costas_run(const CostasArgs a, SpecBuffers b, int K) {
+template <int DT, int ORDER, bool SH = false>
+__global__ __launch_bounds__(256) void k_costas_run(const CostasArgsT<SH> a, SpecBuffers b, int K) {
     const int64_t gid = blockIdx.x * 256ll + threadIdx.x;
     if (gid >= *b.run_count) return;
     const int64_t ck = b.run_list[gid];
     const int64_t c = ck / K;
     const int k = (int)(ck % K);
-    const int64_t s0 = chunk_begin(c);
+    const int64_t s0 = chunk_begin_of<SH>(a, c);
     const int64_t e0 = (s0 + kChunk < a.n) ? s0 + kChunk : a.n;
     CostasState st = b.S[ck];
     float err = 0.0f;
@@ -400,9 +435,11 @@ __device__ __forceinline__ uint32_t map_compose(uint32_t later, uint32_t earlier
 // Exit: either all chunks are resolved, or -- when allow_break -- the chain broke for good (a chunk with plenty of
 // un-gated samples was evaluated serially to its end and met no candidate): stats[3] = the next chunk, *b.resume = its true
 // start state, and the host re-speculates the remaining chunks around that state's frequency.
+// SH (a shard): chunk 0 is never taken as exact -- the walk starts at c_from from the true state *b.resume, for c_from == 0 the
+// state the ranks before this one hand over -- and the true state after the shard's last sample is left in b.resume[1].
 constexpr int kStitchBlock = 1024;              // 16 wavefronts: the fast-forward composes 4096 chunk maps per round
-template <int DT, int ORDER>
-__global__ __launch_bounds__(kStitchBlock) void k_costas_stitch(const CostasArgs a, SpecBuffers b, int64_t n_chunks, int K, int64_t c_from,
+template <int DT, int ORDER, bool SH = false>
+__global__ __launch_bounds__(kStitchBlock) void k_costas_stitch(const CostasArgsT<SH> a, SpecBuffers b, int64_t n_chunks, int K, int64_t c_from,
                                                                  int allow_break) {
     __shared__ uint32_t s_wp[kStitchBlock / 64];    // per-wavefront composition of its chunk maps
     __shared__ int s_fail, s_cand, s_flags;         // first position where the chain ends; broadcast slots
@@ -411,7 +448,7 @@ __global__ __launch_bounds__(kStitchBlock) void k_costas_stitch(const CostasArgs
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int cand = -1;                                  // candidate of chunk c - 1 that is the true trajectory, or -1
     CostasState T = *b.resume;                      // true state at the start of chunk c (valid while cand < 0)
-    if (c_from == 1) { cand = 0; if (tid == 0) { b.T[0] = CostasState{0.0f, 1.5f}; b.gidx[0] = 0; } }   // chunk 0: every candidate is exact
+    if (!SH && c_from == 1) { cand = 0; if (tid == 0) { b.T[0] = CostasState{0.0f, 1.5f}; b.gidx[0] = 0; } }   // chunk 0: every candidate is exact
     int n_map = 0, n_ckpt = 0, n_serial = 0;        // (kept identically by every thread in the fast-forward, by wavefront 0 below)
     int64_t stop_at = n_chunks;
     int64_t c = c_from;
@@ -501,7 +538,7 @@ __global__ __launch_bounds__(kStitchBlock) void k_costas_stitch(const CostasArgs
             }
             if (!done) {
                 // no candidate starts in T: evaluate the chunk from T until the state meets a candidate at a checkpoint
-                const int64_t s0 = chunk_begin(c);
+                const int64_t s0 = chunk_begin_of<SH>(a, c);
                 const int64_t e0 = (s0 + kChunk < a.n) ? s0 + kChunk : a.n;
                 float err = 0.0f;
                 CostasState st = T;
@@ -531,20 +568,22 @@ __global__ __launch_bounds__(kStitchBlock) void k_costas_stitch(const CostasArgs
     if (tid == 0) {
         b.stats[0] += n_map; b.stats[1] += n_ckpt; b.stats[2] += n_serial; b.stats[3] = (int32_t)stop_at;
         *b.resume = T;
+        // the shard's end state: the carrying candidate's, else T (the last chunk ran serially, or is fully gated)
+        if constexpr (SH) b.resume[1] = (cand >= 0) ? b.E[(n_chunks - 1) * K + cand] : T;
     }
 }
 
 // Output pass: every chunk from its TRUE start state.  A chunk that lies on a candidate's trajectory from its first
 // sample (gidx >= 0) is evaluated by kNumCkpt lanes, each from the candidate's checkpoint state (bitwise the true state
 // there); any other chunk by one lane from T[c].
-template <int DT, int ORDER>
-__global__ __launch_bounds__(256) void k_costas_final(const CostasArgs a, SpecBuffers b, int64_t n_chunks, int K) {
+template <int DT, int ORDER, bool SH = false>
+__global__ __launch_bounds__(256) void k_costas_final(const CostasArgsT<SH> a, SpecBuffers b, int64_t n_chunks, int K) {
     const int64_t gid = blockIdx.x * 256ll + threadIdx.x;
     const int64_t c = gid / kNumCkpt;
     const int j = (int)(gid % kNumCkpt);            // segment j = samples [j kCkpt, (j + 1) kCkpt) of the chunk
     if (c >= n_chunks) return;
-    if (gid == 0 && a.n > 0) a.out[0] = -4.0f;      // reference: np.empty, never written (documented in urhgpu.h)
-    const int64_t s0 = chunk_begin(c);
+    if (gid == 0 && a.n > 0 && chunk0_exact<SH>(a)) a.out[0] = -4.0f;      // reference: np.empty, never written (documented in urhgpu.h)
+    const int64_t s0 = chunk_begin_of<SH>(a, c);
     const int64_t e0 = (s0 + kChunk < a.n) ? s0 + kChunk : a.n;
     const int g = b.gidx[c];
     int64_t i0 = s0, i1 = e0;
@@ -587,6 +626,26 @@ size_t costas_scratch_bytes(int64_t n) {
 
 constexpr int kMaxRounds = 24;     // re-speculation rounds before the stitch stops handing back (and runs serially)
 
+// the speculative buffers of nc chunks, carved from costas_scratch_bytes(n) of scratch
+static SpecBuffers spec_buffers(void *scratch, int64_t nc, int K) {
+    char *p = (char *)scratch;
+    auto take = [&](size_t bytes) { char *r = p; p += (bytes + 255) & ~size_t(255); return r; };
+    SpecBuffers b;
+    b.S = (CostasState *)take((size_t)nc * K * sizeof(CostasState));
+    b.E = (CostasState *)take((size_t)nc * K * sizeof(CostasState));
+    b.CP = (CostasState *)take((size_t)nc * kNumCkpt * K * sizeof(CostasState));
+    b.map = (uint32_t *)take((size_t)nc * 4);
+    b.T = (CostasState *)take((size_t)nc * sizeof(CostasState));
+    b.ungated = (int32_t *)take((size_t)nc * 4);
+    b.gidx = (int32_t *)take((size_t)nc * 4);
+    b.run_list = (int32_t *)take((size_t)nc * K * 4);
+    b.is_rep = (uint8_t *)take((size_t)nc * K);
+    b.run_count = (int32_t *)take(64);
+    b.resume = (CostasState *)take(64);
+    b.stats = (int32_t *)take(64);
+    return b;
+}
+
 // NOTE: synchronises the stream (at least once): the host has to learn whether the chunk chain closed.
 template <int DT, int ORDER>
 static int launch_costas_spec(const CostasArgs &a, void *scratch, urhgpu_ctx *ctx);
@@ -607,21 +666,7 @@ static int launch_costas_spec(const CostasArgs &a, void *scratch, urhgpu_ctx *ct
     hipStream_t s = ctx->stream;
     const int K = (a.loop_order == 4) ? 8 : 4;
     const int64_t nc = (a.n - 1 + kChunk - 1) / kChunk;
-    char *p = (char *)scratch;
-    auto take = [&](size_t bytes) { char *r = p; p += (bytes + 255) & ~size_t(255); return r; };
-    SpecBuffers b;
-    b.S = (CostasState *)take((size_t)nc * K * sizeof(CostasState));
-    b.E = (CostasState *)take((size_t)nc * K * sizeof(CostasState));
-    b.CP = (CostasState *)take((size_t)nc * kNumCkpt * K * sizeof(CostasState));
-    b.map = (uint32_t *)take((size_t)nc * 4);
-    b.T = (CostasState *)take((size_t)nc * sizeof(CostasState));
-    b.ungated = (int32_t *)take((size_t)nc * 4);
-    b.gidx = (int32_t *)take((size_t)nc * 4);
-    b.run_list = (int32_t *)take((size_t)nc * K * 4);
-    b.is_rep = (uint8_t *)take((size_t)nc * K);
-    b.run_count = (int32_t *)take(64);
-    b.resume = (CostasState *)take(64);
-    b.stats = (int32_t *)take(64);
+    SpecBuffers b = spec_buffers(scratch, nc, K);
     URH_HIP(hipMemsetAsync(b.stats, 0, 64, s));
     URH_HIP(hipMemsetAsync(b.resume, 0, 64, s));
     int64_t c_from = 0;
@@ -654,9 +699,19 @@ static int launch_costas_spec(const CostasArgs &a, void *scratch, urhgpu_ctx *ct
     return URHGPU_OK;
 }
 
-int launch_costas(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad, void *scratch) {
-    CostasArgs a;
-    a.iq = d_iq; a.n = n; a.out = d_qad;
+// Warm-up: two trajectories in the same lock class contract by about (1 - alpha) per sample once the seeded frequency is close;
+// from a phase error of order 1 down to the last float bit takes ~ 18 / alpha samples (130 at the default bandwidth 0.1), the
+// pull-in before that a few loop time constants: 40 / bandwidth samples, rounded up to a power of two, covers both with margin
+// (512 at 0.1; it was a fixed 1024).  Too short a warm-up only costs time: unmatched chunks are re-speculated / run serially.
+static int costas_warm(float bandwidth) {
+    const double want = 40.0 / std::max(1e-3, std::min(1.0, (double)fabsf(bandwidth)));
+    int w = 256;
+    while (w < want && w < 8192) w *= 2;
+    return w;
+}
+
+// the loop's constants (everything of CostasArgs but the buffers)
+static int costas_args(const urhgpu_params *p, CostasArgs &a) {
     a.noise_sqrd = p->noise_threshold * p->noise_threshold;
     // :253-254 as the reference's generated code evaluates them (damping = (float)(sqrt(2)/2), bandwidth*bandwidth a float product)
     const float bandwidth = p->costas_loop_bandwidth;
@@ -672,19 +727,17 @@ int launch_costas(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_par
         case URHGPU_DT_F32: a.scale = 1.0f; a.shift = 0.0f; break;
         default: return URHGPU_ERR_DTYPE;
     }
-    // Warm-up: two trajectories in the same lock class contract by about (1 - alpha) per sample once the seeded frequency is close;
-    // from a phase error of order 1 down to the last float bit takes ~ 18 / alpha samples (130 at the default bandwidth 0.1), the
-    // pull-in before that a few loop time constants: 40 / bandwidth samples, rounded up to a power of two, covers both with margin
-    // (512 at 0.1; it was a fixed 1024).  Too short a warm-up only costs time: unmatched chunks are re-speculated / run serially.
-    {
-        const double want = 40.0 / std::max(1e-3, std::min(1.0, (double)fabsf(bandwidth)));
-        int w = 256;
-        while (w < want && w < 8192) w *= 2;
-        a.warm = w;
-    }
+    a.warm = costas_warm(bandwidth);
     int order = p->mod_order > 0 ? p->mod_order : (1 << p->bits_per_symbol);
     if (order > 4) order = 4;                                  // :285-287
     a.loop_order = order;
+    return URHGPU_OK;
+}
+
+int launch_costas(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad, void *scratch) {
+    CostasArgs a;
+    a.iq = d_iq; a.n = n; a.out = d_qad;
+    URH_TRY(costas_args(p, a));
     switch (p->dtype) {
         case URHGPU_DT_I8: return launch_costas_dt<URHGPU_DT_I8>(a, scratch, ctx);
         case URHGPU_DT_U8: return launch_costas_dt<URHGPU_DT_U8>(a, scratch, ctx);
@@ -693,6 +746,172 @@ int launch_costas(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_par
         default: return launch_costas_dt<URHGPU_DT_F32>(a, scratch, ctx);
     }
 }
+
+// ---- sharded captures: one rank's Costas pass (include/urhgpu.h, "PSK across shards") ----------------------------------------
+// A shard is the single-GPU problem one level up: its chunk 0 is a chunk whose true start state lives on another GPU.  The rank
+// speculates its chunks (SH instantiations: chunks from the shard's start, walks back into the raw left halo), reduces them to a
+// fixed-size summary, and -- once the ranks have composed the summaries into its true start state -- stitches from that state and
+// runs the output pass.
+
+int64_t costas_halo_samples(const urhgpu_params *p) { return (int64_t)kWarmBackFactor * costas_warm(p->costas_loop_bandwidth); }
+
+// The summary (kCostasSummaryBytes, uint32 words): what the other ranks need to carry the loop state across the shard without its
+// samples.  One workgroup; the chunk maps are composed as in the stitch's fast-forward (map_compose, wave scan), reduced to their total.
+//   0 .. 15   start states {freq, phase} of chunk 0's candidates (float32 bits; candidates >= K: 0)
+//   16 .. 31  end states of the last chunk's candidates (representatives only, others 0)
+//   32        map[n_chunks - 1] o ... o map[1]: chunk-0 candidate -> last-chunk candidate carrying the same trajectory, 0xF = broken
+//   33        bit k: chunk 0's candidate k is a representative (no lower-numbered candidate starts in the same state)
+//   34        1: no un-gated sample in the shard (gated samples freeze the loop: end state = start state)
+//   35        K;  36 .. 37: n_chunks (int64);  38 .. 39: un-gated samples (int64)
+constexpr int kSumBlock = 1024;
+__global__ __launch_bounds__(kSumBlock) void k_costas_shard_summary(SpecBuffers b, int64_t n_chunks, int K, uint32_t *out) {
+    __shared__ uint32_t s_wp[kSumBlock / 64];
+    __shared__ unsigned long long s_ung;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) s_ung = 0;
+    __syncthreads();
+    unsigned long long ung = 0;
+    for (int64_t c = tid; c < n_chunks; c += kSumBlock) ung += (uint32_t)b.ungated[c];
+    atomicAdd(&s_ung, ung);
+    uint32_t R = 0x76543210u;                                   // composition of the maps so far (every thread keeps it)
+    constexpr int Q = 4;
+    for (int64_t c0 = 1; c0 < n_chunks; c0 += (int64_t)kSumBlock * Q) {
+        const int64_t cc0 = c0 + (int64_t)Q * tid;
+        uint32_t P = 0x76543210u;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) if (cc0 + q < n_chunks) P = map_compose(b.map[cc0 + q], P);
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {                      // lane 63: the wavefront's chunks in order
+            const uint32_t u = __shfl_up(P, o);
+            if (lane >= o) P = map_compose(P, u);
+        }
+        if (lane == 63) s_wp[wave] = P;
+        __syncthreads();
+        for (int w = 0; w < kSumBlock / 64; ++w) R = map_compose(s_wp[w], R);
+        __syncthreads();
+    }
+    __syncthreads();
+    if (tid < kCostasSummaryBytes / 4) {
+        const int64_t last = (n_chunks - 1) * K;
+        uint32_t v = 0;
+        if (tid < 16) {
+            const int k = tid >> 1;
+            if (k < K) { const CostasState s = b.S[k]; v = __float_as_uint((tid & 1) ? s.phase : s.freq); }
+        } else if (tid < 32) {
+            const int k = (tid - 16) >> 1;
+            if (k < K && b.is_rep[last + k]) { const CostasState e = b.E[last + k]; v = __float_as_uint((tid & 1) ? e.phase : e.freq); }
+        } else if (tid == 32) {
+            v = R;
+        } else if (tid == 33) {
+            for (int k = 0; k < K; ++k) v |= b.is_rep[k] ? (1u << k) : 0u;
+        } else if (tid == 34) {
+            v = (s_ung == 0) ? 1u : 0u;
+        } else if (tid == 35) {
+            v = (uint32_t)K;
+        } else if (tid < 38) {
+            v = (uint32_t)((uint64_t)n_chunks >> (32 * (tid - 36)));
+        } else {
+            v = (uint32_t)(s_ung >> (32 * (tid - 38)));
+        }
+        out[tid] = v;
+    }
+}
+
+__global__ void k_costas_set_state(CostasState *dst, uint32_t freq_bits, uint32_t phase_bits) {     // bits as given (NaN payloads too)
+    uint32_t *d = (uint32_t *)dst;
+    d[0] = freq_bits; d[1] = phase_bits;
+}
+
+static int costas_shard_args(const CostasShard &cs, CostasArgsSh &a, int64_t &nc) {
+    a.iq = cs.iq; a.n = cs.n; a.out = cs.out;
+    URH_TRY(costas_args(&cs.p, a));
+    if (a.loop_order != 2 && a.loop_order != 4) return URHGPU_ERR_UNSUPPORTED;    // the reference leaves the output unwritten
+    a.halo_end = cs.halo_end; a.origin = cs.origin; a.lo = cs.lo; a.start1 = cs.start1;
+    nc = (cs.n - cs.origin + kChunk - 1) / kChunk;
+    return URHGPU_OK;
+}
+
+template <int DT, int ORDER>
+static int costas_shard_spec_t(urhgpu_ctx *ctx, const CostasArgsSh &a, int64_t nc, void *scratch, void *d_summary) {
+    hipStream_t s = ctx->stream;
+    const int K = (ORDER == 4) ? 8 : 4;
+    const SpecBuffers b = spec_buffers(scratch, nc, K);
+    URH_HIP(hipMemsetAsync(b.stats, 0, 64, s));
+    URH_HIP(hipMemsetAsync(b.resume, 0, 64, s));
+    URH_HIP(hipMemsetAsync(b.run_count, 0, 4, s));
+    const unsigned g = (unsigned)((nc * K + 255) / 256);
+    hipLaunchKernelGGL((k_costas_spec<DT, ORDER, true>), dim3(g), dim3(256), 0, s, a, b, nc, K, (int64_t)0, 0, 0.0f);
+    hipLaunchKernelGGL((k_costas_run<DT, ORDER, true>), dim3(g), dim3(256), 0, s, a, b, K);
+    hipLaunchKernelGGL(k_costas_map, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, b, nc, K, (int64_t)1);
+    hipLaunchKernelGGL(k_costas_shard_summary, dim3(1), dim3(kSumBlock), 0, s, b, nc, K, (uint32_t *)d_summary);
+    URH_HIP(hipGetLastError());
+    return URHGPU_OK;
+}
+
+// NOTE: synchronises the stream once per stitch round (as launch_costas_spec: the host learns whether the chunk chain closed).
+template <int DT, int ORDER>
+static int costas_shard_resolve_t(urhgpu_ctx *ctx, const CostasArgsSh &a, int64_t nc, void *scratch, uint32_t freq_bits, uint32_t phase_bits,
+                                  void *d_end) {
+    hipStream_t s = ctx->stream;
+    const int K = (ORDER == 4) ? 8 : 4;
+    const SpecBuffers b = spec_buffers(scratch, nc, K);
+    hipLaunchKernelGGL(k_costas_set_state, dim3(1), dim3(1), 0, s, b.resume, freq_bits, phase_bits);
+    int64_t c_from = 0;
+    float seed_freq = 0.0f;
+    int32_t *h = (int32_t *)(ctx->h_counts + 12);            // pinned: stats[0..4], then the resume state
+    int rounds = 0;
+    for (int round = 0;; ++round) {
+        if (round > 0) {                                     // the chain broke for good inside the shard: re-speculate the rest
+            const int64_t todo = nc - c_from;
+            URH_HIP(hipMemsetAsync(b.run_count, 0, 4, s));
+            hipLaunchKernelGGL((k_costas_spec<DT, ORDER, true>), dim3((unsigned)((todo * K + 255) / 256)), dim3(256), 0, s, a, b, nc, K, c_from, 1,
+                               seed_freq);
+            hipLaunchKernelGGL((k_costas_run<DT, ORDER, true>), dim3((unsigned)((todo * K + 255) / 256)), dim3(256), 0, s, a, b, K);
+            hipLaunchKernelGGL(k_costas_map, dim3((unsigned)((todo + 255) / 256)), dim3(256), 0, s, b, nc, K, c_from);
+        }
+        hipLaunchKernelGGL((k_costas_stitch<DT, ORDER, true>), dim3(1), dim3(kStitchBlock), 0, s, a, b, nc, K, c_from,
+                           round < kMaxRounds ? 1 : 0);
+        URH_HIP(hipGetLastError());
+        URH_HIP(hipMemcpyAsync(h, b.stats, 20, hipMemcpyDeviceToHost, s));
+        URH_HIP(hipMemcpyAsync(h + 6, b.resume, 8, hipMemcpyDeviceToHost, s));
+        URH_HIP(hipStreamSynchronize(s));
+        const int64_t stop_at = h[3];
+        if (stop_at >= nc) break;
+        c_from = stop_at;                                    // >= 1: the stitch stops in front of the chunk after the one it ran
+        memcpy(&seed_freq, h + 6, 4);
+        rounds = round + 1;
+    }
+    h[4] = rounds;
+    if (d_end) URH_HIP(hipMemcpyAsync(d_end, b.resume + 1, 8, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL((k_costas_final<DT, ORDER, true>), dim3((unsigned)((nc * kNumCkpt + 255) / 256)), dim3(256), 0, s, a, b, nc, K);
+    URH_HIP(hipGetLastError());
+    return URHGPU_OK;
+}
+
+#define URH_COSTAS_SHARD_DISPATCH(FN, ...)                                                                                       \
+    switch (cs.p.dtype) {                                                                                                        \
+        case URHGPU_DT_I8: return a.loop_order == 4 ? FN<URHGPU_DT_I8, 4>(__VA_ARGS__) : FN<URHGPU_DT_I8, 2>(__VA_ARGS__);        \
+        case URHGPU_DT_U8: return a.loop_order == 4 ? FN<URHGPU_DT_U8, 4>(__VA_ARGS__) : FN<URHGPU_DT_U8, 2>(__VA_ARGS__);        \
+        case URHGPU_DT_I16: return a.loop_order == 4 ? FN<URHGPU_DT_I16, 4>(__VA_ARGS__) : FN<URHGPU_DT_I16, 2>(__VA_ARGS__);     \
+        case URHGPU_DT_U16: return a.loop_order == 4 ? FN<URHGPU_DT_U16, 4>(__VA_ARGS__) : FN<URHGPU_DT_U16, 2>(__VA_ARGS__);     \
+        case URHGPU_DT_F32: return a.loop_order == 4 ? FN<URHGPU_DT_F32, 4>(__VA_ARGS__) : FN<URHGPU_DT_F32, 2>(__VA_ARGS__);     \
+        default: return URHGPU_ERR_DTYPE;                                                                                        \
+    }
+
+int launch_costas_shard_spec(urhgpu_ctx *ctx, const CostasShard &cs, void *d_summary) {
+    CostasArgsSh a;
+    int64_t nc = 0;
+    URH_TRY(costas_shard_args(cs, a, nc));
+    URH_COSTAS_SHARD_DISPATCH(costas_shard_spec_t, ctx, a, nc, cs.scratch, d_summary)
+}
+
+int launch_costas_shard_resolve(urhgpu_ctx *ctx, const CostasShard &cs, uint32_t freq_bits, uint32_t phase_bits, void *d_end) {
+    CostasArgsSh a;
+    int64_t nc = 0;
+    URH_TRY(costas_shard_args(cs, a, nc));
+    URH_COSTAS_SHARD_DISPATCH(costas_shard_resolve_t, ctx, a, nc, cs.scratch, freq_bits, phase_bits, d_end)
+}
+#undef URH_COSTAS_SHARD_DISPATCH
 
 // every float with |y| < 120 (bit patterns 0 .. 0x42f00000, both signs): urh_sincosf_fast against urh_sinf / urh_cosf
 __global__ __launch_bounds__(256) void k_test_sincosf_fast(unsigned long long *mismatches) {

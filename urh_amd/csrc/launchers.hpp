@@ -377,5 +377,18 @@ void launch_copy_shape(const float *in, float *out, int64_t n_samples, int shape
 // ---- costas.hip -----------------------------------------------------------------------------------------------
 size_t costas_scratch_bytes(int64_t n);
 int launch_costas(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad, void *scratch);
+// sharded captures: one rank's Costas pass between its two phases (urhgpu_shard_costas_spec_dev / _resolve_dev)
+constexpr int kCostasSummaryBytes = 160;     // == URHGPU_COSTAS_SUMMARY_BYTES
+struct CostasShard {
+    const void *iq;          // the shard (n samples)
+    const void *halo_end;    // one past the raw left halo (rank 0: nullptr)
+    float *out;              // the shard's demodulated signal (n floats)
+    int64_t n, origin, lo, start1;   // see CostasArgsSh (costas.hip)
+    urhgpu_params p;
+    void *scratch;           // costas_scratch_bytes(n): the speculative buffers, kept from the first phase to the second
+};
+int64_t costas_halo_samples(const urhgpu_params *p);       // raw samples before a shard that its walks back may read
+int launch_costas_shard_spec(urhgpu_ctx *ctx, const CostasShard &cs, void *d_summary);
+int launch_costas_shard_resolve(urhgpu_ctx *ctx, const CostasShard &cs, uint32_t freq_bits, uint32_t phase_bits, void *d_end);
 
 }  // namespace urh

@@ -266,6 +266,48 @@ class GpuShardEngine(DevicePipeline):
                                                      C.c_void_p(summary.data_ptr())))
         return summary
 
+    # ---- PSK: the Costas loop across shards (sharding.py, steps 1-4; include/urhgpu.h) ----
+    def costas_spec(self, iq_local, left_raw, pos_base, n_total, rank, world, p):
+        """speculate the shard (its first chunk warms up in left_raw, the raw samples before it; None on rank 0) -> the summary
+        (uint8 device tensor of COSTAS_SUMMARY_BYTES)"""
+        from .sharding import COSTAS_SUMMARY_BYTES
+        torch = self.torch
+        if self.tail_stream is not None:
+            raise ValueError("PSK shards run on an engine that is not pipelined: GpuShardEngine(pipelined=False)")
+        iq, n, cp, o = self._setup(iq_local, p, True, n_total)    # the qad always: the runs phase segments it
+        self._pre = (iq, n, cp, o)
+        halo = None
+        if left_raw is not None:
+            halo = torch.view_as_real(left_raw) if left_raw.dtype == torch.complex64 else left_raw
+            if halo.dtype != iq.dtype or halo.dim() != 2 or halo.shape[1] != 2:
+                raise ValueError("left_raw: raw samples in the shard's dtype, (m, 2) or complex64 (m,)")
+            halo = halo.contiguous()
+            self._keep += (halo,)
+        summary = self._buf("costas_summary", (COSTAS_SUMMARY_BYTES,), torch.uint8)
+        self._costas_end = self._buf("costas_end", (2,), torch.int32)
+        self._costas_end.zero_()
+        _lib.check(_lib.load().urhgpu_shard_costas_spec_dev(
+            self.ctx.handle, C.c_void_p(iq.data_ptr()), n, int(pos_base), int(n_total), int(rank), int(world),
+            C.c_void_p(halo.data_ptr()) if halo is not None else None, int(halo.shape[0]) if halo is not None else 0,
+            C.byref(cp), C.byref(o), C.c_void_p(summary.data_ptr())))
+        return summary
+
+    def costas_resolve(self, start):
+        """stitch the shard from its true start state (freq bits, phase bits) and write its qad"""
+        st = (C.c_uint32 * 2)(int(start[0]), int(start[1]))
+        _lib.check(_lib.load().urhgpu_shard_costas_resolve_dev(self.ctx.handle, st, C.c_void_p(self._costas_end.data_ptr())))
+
+    def costas_end(self):
+        """the shard's true end state (2 x int32: float32 bits) once it has resolved, zeros before"""
+        return self._costas_end
+
+    def costas_last(self):
+        """the shard's last demodulated value (1 float): the next rank's halo of the pulse table"""
+        return self._res.qad[-1:]
+
+    def costas_stats(self):
+        return self.ctx.costas_stats()
+
     def rows(self, summaries):
         torch = self.torch
         self._keep += (summaries,)

@@ -15,8 +15,22 @@ is exchanged with three (ASK: four) small all-gathers -- no data-path collective
 
 The result stays sharded: rank r owns the pulse-table rows that END in its shard and the bits /
 bit_sample_pos those rows expand to; concatenating the ranks' pieces in rank order gives exactly the
-single-GPU (and reference) result (`stitch`).  Costas/PSK carries loop state across the whole capture and
-does not shard ("replicas only").
+single-GPU (and reference) result (`stitch`).
+
+PSK: the Costas loop carries its state {freq, phase} across the whole capture.  A PSK pass (orders 2 and 4) first
+runs the loop across the shards, then the phases above from the shard's demodulated signal:
+
+    0. (no exchange) every rank > 0 is handed the `costas_halo_samples` raw samples before its shard (`left_raw`)
+    1. speculate   candidate trajectories per 4096-sample chunk of the shard (the single-GPU kernels; chunk 0 warms
+                   up in the halo), reduced to a 160-byte summary: chunk 0's candidate start states, the composition of
+                   the shard's chunk maps, the last chunk's end states, "no un-gated sample"
+    2. compose     all-gather the summaries; `costas_compose` (a pure function of the gathered bytes: every rank takes
+                   the same branch) carries the state from {0, 1.5} across the shards by bitwise lookups.  Where it cannot,
+                   the rank at the break resolves and hands its true end state over in one more all-gather of 8 bytes per
+                   rank (`costas_exchange`: rounds <= world; one in the common case)
+    3. resolve     every rank stitches from its true start state and writes its shard's qad
+    4. halo        one all-gather of 4 bytes: every shard's last demodulated value (the seam of the pulse table), then
+                   summary / rows / flags exactly as above.
 
 The orchestration below is engine-agnostic: `engine` is the GPU engine (urh_amd.shard_engine.GpuShardEngine,
 HIP kernels behind the C ABI) in production; the CPU test-suite drives the same orchestration with the executable
@@ -275,6 +289,95 @@ class ThreadComm:
         return out
 
 
+COSTAS_SUMMARY_BYTES = 160                  # URHGPU_COSTAS_SUMMARY_BYTES
+COSTAS_START = (0x00000000, 0x3FC00000)     # the loop's initial state {freq 0.0f, phase 1.5f} as float32 bits (signal_functions.pyx:261)
+_COSTAS_WARM_BACK = 16                      # kWarmBackFactor (costas.hip): a candidate looks back at most 16 x its warm-up
+
+
+def costas_halo_samples(bandwidth, pos_base=None):
+    """urhgpu_costas_halo_samples: raw samples before its shard that a PSK rank > 0 is handed (`left_raw`) -- every sample the
+    warm-up of its first chunk may read: 8 192 at bandwidth 0.1, up to 131 072 at the smallest bandwidths.  pos_base given: no more
+    than the capture holds before the shard from sample 1 on (sample 0 is not part of the loop)."""
+    want = 40.0 / max(1e-3, min(1.0, abs(float(np.float32(bandwidth)))))      # costas_warm (costas.hip), in double
+    w = 256
+    while w < want and w < 8192:
+        w *= 2
+    h = _COSTAS_WARM_BACK * w
+    return h if pos_base is None else min(h, max(int(pos_base) - 1, 0))
+
+
+def pack_costas_summary(starts, ends, cmap, reps, identity=False, n_chunks=1, ungated=None):
+    """One Costas shard summary in the layout k_costas_shard_summary (costas.hip) writes: uint8 (COSTAS_SUMMARY_BYTES,).
+    starts / ends: K states (freq bits, phase bits) of the first chunk's candidates / the last chunk's (None: not a representative);
+    cmap: the composed chunk map (nibble k: last-chunk candidate of first-chunk candidate k, 0xF broken); reps: K flags."""
+    w = np.zeros(COSTAS_SUMMARY_BYTES // 4, np.uint32)
+    for k, s in enumerate(starts):
+        w[2 * k], w[2 * k + 1] = s
+    for k, e in enumerate(ends):
+        if e is not None:
+            w[16 + 2 * k], w[17 + 2 * k] = e
+    w[32] = cmap
+    w[33] = sum(1 << k for k, r in enumerate(reps) if r)
+    w[34] = 1 if identity else 0
+    w[35] = len(starts)
+    w[36:38] = np.array([n_chunks], np.int64).view(np.uint32)
+    w[38:40] = np.array([(0 if identity else 1) if ungated is None else ungated], np.int64).view(np.uint32)
+    return w.view(np.uint8)
+
+
+def costas_compose(summaries, handoff=None):
+    """Carry the Costas loop state across the shards: a pure function of the gathered summaries ((world, COSTAS_SUMMARY_BYTES)
+    bytes, rank order) and of the end states handed over so far (handoff: {rank: (freq bits, phase bits)}), so every rank that
+    evaluates it takes the same branch.  Rank 0 starts in COSTAS_START; a shard without an un-gated sample passes the state on;
+    otherwise the state is looked up BITWISE among the representatives of its first chunk's candidates and the composed map names
+    the last-chunk candidate whose end state comes out.  Returns (starts, pending): starts[r] = the true state at the start of shard
+    r as (freq bits, phase bits), None where not known yet; pending = the first rank whose end state the summaries cannot give (its
+    start state is known: it resolves and hands its end state over), None when every start state is known."""
+    raw = np.ascontiguousarray(np.asarray(summaries, dtype=np.uint8)).reshape(-1, COSTAS_SUMMARY_BYTES)
+    w = raw.view("<u4")
+    handoff = handoff or {}
+    starts = [None] * len(w)
+    state = COSTAS_START
+    for r, row in enumerate(w):
+        starts[r] = state
+        if r in handoff:
+            state = (int(handoff[r][0]), int(handoff[r][1]))
+            continue
+        if row[34]:
+            continue                                  # gated samples freeze the loop: end state = start state
+        K, reps, cmap = int(row[35]), int(row[33]), int(row[32])
+        q = 0xF
+        for k in range(min(K, 8)):
+            if (reps >> k) & 1 and (int(row[2 * k]), int(row[2 * k + 1])) == state:
+                q = (cmap >> (4 * k)) & 0xF
+                break
+        if q >= min(K, 8):                            # no candidate starts in the state, or the map is broken
+            return starts, r
+        state = (int(row[16 + 2 * q]), int(row[17 + 2 * q]))
+    return starts, None
+
+
+def costas_exchange(comm, summary, resolve, end_state):
+    """Steps 2-3 of a PSK pass (module docstring): all-gather the summaries, compose, and let this rank resolve as soon as its start
+    state is known; while the chain breaks at some rank, that rank's end state comes in one more all-gather.  How many all-gathers
+    there are depends on the gathered bytes only (costas_compose): the same on every rank.
+    summary: this rank's summary (uint8 tensor); resolve((freq bits, phase bits)) stitches this rank from its true start state;
+    end_state(): 2 x int32 tensor, the rank's true end state once it has resolved.  Returns the number of rounds."""
+    summaries = comm.all_gather(summary).cpu().numpy()
+    handoff = {}
+    rounds, resolved = 1, False
+    while True:
+        starts, pending = costas_compose(summaries, handoff)
+        if not resolved and starts[comm.rank] is not None:
+            resolve(starts[comm.rank])
+            resolved = True
+        if pending is None:
+            return rounds
+        ends = np.ascontiguousarray(comm.all_gather(end_state()).cpu().numpy()).view(np.uint32).reshape(-1, 2)
+        handoff[pending] = (int(ends[pending, 0]), int(ends[pending, 1]))
+        rounds += 1
+
+
 def shard_bounds(n_total: int, world: int):
     """[begin, end) of every rank's shard: equal shards of ceil(n/world) samples rounded up to a multiple of
     64 (so that every shard starts 16-byte aligned for every IQ dtype), the last rank takes what is left.
@@ -294,6 +397,7 @@ class ShardedPipeline:
     def __init__(self, engine, comm):
         self.engine, self.comm = engine, comm
         self.rank, self.world = comm.rank, comm.world
+        self.last_costas = None                  # PSK: the last pass's Costas exchange (rounds, this rank's chunks by map / checkpoint / serial)
 
     # bench.py / DevicePipeline compatible surface ------------------------------------------------
     @property
@@ -345,11 +449,14 @@ class ShardedPipeline:
         tails = c.all_gather(e.fir_tail(iq_local, m - 1))
         return e.fir(iq_local, taps, tails[self.rank - 1] if self.rank > 0 else None)
 
-    def iq_to_bits(self, iq_local, p, want_qad=True, pos_base=None, n_total=None, halo_given=False, left_halo=None):
+    def iq_to_bits(self, iq_local, p, want_qad=True, pos_base=None, n_total=None, halo_given=False, left_halo=None, left_raw=None):
         """iq_local: this rank's shard.  pos_base / n_total default to equal shards of len(iq_local).
         halo_given (the same on every rank): whoever distributed the capture handed every rank but the first the two samples that
         precede its shard (left_halo: (2, 2) in the shard's dtype, or complex64 (2,)) -- 16 bytes more per rank to read from the
-        file.  The halo exchange is then skipped: two all-gathers per pass (ASK: three) instead of three (four)."""
+        file.  The halo exchange is then skipped: two all-gathers per pass (ASK: three) instead of three (four).
+        PSK: every rank but the first passes left_raw, the costas_halo_samples(p.costas_loop_bandwidth, pos_base) raw samples
+        before its shard ((m, 2) in the shard's dtype, or complex64 (m,); a longer tail is cut to them); halo_given / left_halo do
+        not apply.  The pass's Costas exchange is recorded in `last_costas`; the result always carries the shard's qad."""
         e, c = self.engine, self.comm
         n_local = int(iq_local.shape[0])
         if pos_base is None:
@@ -357,7 +464,7 @@ class ShardedPipeline:
         if n_total is None:
             n_total = self.world * n_local
         if p.modulation_type == "PSK":
-            raise ValueError("the Costas loop carries state across the whole capture: PSK does not shard")
+            return self._iq_to_bits_psk(iq_local, p, int(pos_base), int(n_total), left_raw)
         if halo_given and self.rank > 0 and left_halo is None:
             raise ValueError("halo_given: ranks > 0 pass the two samples before their shard as left_halo")
         pending = left = None
@@ -386,6 +493,31 @@ class ShardedPipeline:
             merged_all = c.all_gather(merge) if merge is not None else None
             flags = e.bits_prepare(merged_all)
             return e.bits_finish(c.all_gather(flags))
+
+    def _iq_to_bits_psk(self, iq_local, p, pos_base, n_total, left_raw):
+        """the PSK pass (module docstring, steps 0-4).  Everything a rank can get wrong on its own is checked before the first collective."""
+        e, c = self.engine, self.comm
+        if n_total <= 2:
+            raise ValueError("PSK: a capture of two samples or fewer does not shard")
+        if self.rank > 0:
+            need = costas_halo_samples(p.costas_loop_bandwidth, pos_base)
+            have = 0 if left_raw is None else int(left_raw.shape[0])
+            if have < need:
+                raise ValueError(f"PSK: rank {self.rank} needs the {need} raw samples before its shard as left_raw (got {have})")
+            left_raw = left_raw[have - need:]
+        else:
+            left_raw = None
+        summary = e.costas_spec(iq_local, left_raw, pos_base, n_total, self.rank, self.world, p)
+        rounds = costas_exchange(c, summary, e.costas_resolve, e.costas_end)
+        by_map, by_ckpt, serial, respec = e.costas_stats()
+        self.last_costas = {"rounds": rounds, "chunks_by_map": by_map, "chunks_by_checkpoint": by_ckpt, "chunks_serial": serial,
+                            "respeculation_rounds": respec}
+        lasts = c.all_gather(e.costas_last())                 # every shard's last demodulated value: the seam of the pulse table
+        left = lasts[self.rank - 1] if self.rank > 0 else None
+        summary = e.runs(iq_local, left, pos_base, n_total, self.rank, self.world, p, True)
+        merge = e.rows(c.all_gather(summary))
+        flags = e.bits_prepare(c.all_gather(merge) if merge is not None else None)
+        return e.bits_finish(c.all_gather(flags))
 
 
 def stitch(pieces):
