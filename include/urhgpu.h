@@ -738,6 +738,20 @@ int64_t urhgpu_test_wide_int_launches(void);
 /* Test hook: elementwise bit-faithful atan2f (the device port of glibc 2.35 atan2f), device pointers. */
 int urhgpu_test_atan2f_dev(urhgpu_ctx *ctx, const float *d_y, const float *d_x, int64_t n, float *d_out);
 
+/* ---- the live mode's pass over an incoming chunk (ProtocolSniffer.__demodulate_data, ProtocolSniffer.py:204-281) --------------------
+ * d_src: n_rows rows of two samples of `dtype` (URHGPU_DT_*), device memory, any row offset into a larger buffer.  In one read of the chunk
+ *   - its first n_store rows (n_store <= n_rows: the reference trims an append that does not fit its buffer) are stored to d_dst (device;
+ *     NULL or == d_src: nothing is stored -- the chunk was uploaded to its place already; otherwise the two ranges must not overlap), and
+ *   - *sum_out = np.sum(data ** 2.0) and *max_out = np.max(data ** 2.0) over the 2 * n_rows components are formed in the reference's
+ *     arithmetic: float32 chunks in float32 (squares not fused into the adds, numpy's pairwise order, NaN as np.max propagates it) and
+ *     widened exactly; integer chunks as exact integers, which is numpy's float64 result as long as the total stays below 2^53
+ *     (beyond: URHGPU_ERR_UNSUPPORTED).  np.mean is *sum_out divided by 2 * n_rows in the chunk's float type.
+ * Two launches whatever n_rows is; the results land in pinned host memory by ordinary stores; synchronous (one stream synchronisation). */
+int urhgpu_chunk_power_stats_dev(urhgpu_ctx *ctx, const void *d_src, int dtype, int64_t n_rows, void *d_dst, int64_t n_store, double *sum_out,
+                                 double *max_out);
+/* Diagnostics: kernel launches urhgpu_chunk_power_stats_dev has issued on this context. */
+int urhgpu_chunk_stats_launches(urhgpu_ctx *ctx, int64_t *n_launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -788,6 +788,8 @@ int urhgpu_ctx_destroy(urhgpu_ctx *ctx) {
     ctx->staging.release();
     ctx->aux.release();
     ctx->fir_work.release();
+    ctx->chunk_work.release();
+    if (ctx->h_chunk) (void)hipHostFree(ctx->h_chunk);
     if (ctx->ev_fir) (void)hipEventDestroy(ctx->ev_fir);
     ctx->arena_alt.release();
     ctx->arena_alt2.release();
@@ -1691,6 +1693,39 @@ int urhgpu_pairwise_sum_f32_dev(urhgpu_ctx *ctx, const float *d_x, int64_t n, in
     URH_HIP(hipSetDevice(ctx->device));
     URH_TRY(join_tail(ctx));
     return pairwise_sum_f32(ctx, d_x, n, mode, mean, sum_out);
+}
+
+int urhgpu_chunk_power_stats_dev(urhgpu_ctx *ctx, const void *d_src, int dtype, int64_t n_rows, void *d_dst, int64_t n_store, double *sum_out,
+                                 double *max_out) {
+    if (!ctx || !d_src || n_rows <= 0 || n_rows > (int64_t(1) << 31) || n_store < 0 || n_store > n_rows || !sum_out || !max_out) return URHGPU_ERR_ARG;
+    if (dtype < URHGPU_DT_I8 || dtype > URHGPU_DT_F32) return URHGPU_ERR_DTYPE;
+    const size_t row = 2 * (size_t)(dtype == URHGPU_DT_F32 ? 4 : (dtype == URHGPU_DT_I16 || dtype == URHGPU_DT_U16) ? 2 : 1);
+    if (d_dst == d_src || n_store == 0) d_dst = nullptr;                                   // the chunk already lies where it belongs: statistics only
+    if (d_dst && (const char *)d_dst < (const char *)d_src + row * n_rows && (const char *)d_src < (const char *)d_dst + row * n_store) return URHGPU_ERR_ARG;
+    URH_HIP(hipSetDevice(ctx->device));
+    if (!ctx->h_chunk) URH_HIP(hipHostMalloc((void **)&ctx->h_chunk, 64));
+    const size_t need = chunk_stats_scratch_bytes(dtype, n_rows);
+    if (need + 256 > ctx->chunk_work.cap) {
+        URH_HIP(hipStreamSynchronize(ctx->stream));
+        URH_TRY(ctx->chunk_work.reserve(2 * need + 4096));
+    }
+    ctx->chunk_work.reset();
+    void *scratch = ctx->chunk_work.take(need);
+    if (!scratch) return URHGPU_ERR_ARG;
+    URH_TRY(launch_chunk_stats(d_src, dtype, n_rows, d_dst, n_store, scratch, ctx->h_chunk, ctx->stream));
+    ctx->chunk_launches += 2;
+    URH_HIP(hipGetLastError());
+    URH_HIP(wait_stream(ctx, ctx->stream));                                // the one synchronisation of a chunk
+    if (ctx->h_chunk[2] != 0.0) return URHGPU_ERR_UNSUPPORTED;             // integer total >= 2^53: numpy's float64 sum would round
+    *sum_out = ctx->h_chunk[0];
+    *max_out = ctx->h_chunk[1];
+    return URHGPU_OK;
+}
+
+int urhgpu_chunk_stats_launches(urhgpu_ctx *ctx, int64_t *n_launches) {
+    if (!ctx || !n_launches) return URHGPU_ERR_ARG;
+    *n_launches = (int64_t)ctx->chunk_launches;
+    return URHGPU_OK;
 }
 
 int urhgpu_histogram_f32_dev(urhgpu_ctx *ctx, const float *d_x, int64_t n, const double *d_edges, int64_t n_edges, int64_t *d_counts) {

@@ -138,6 +138,11 @@ struct urhgpu_ctx {
     hipStream_t bits_stream = nullptr;   // second tail stream of streamed passes: the bits segments, behind the rows they expand
     hipEvent_t ev_rows[3][16] = {};      // [arena slot][bits segment]: the rows below the bits segment's end have been written
     hipEvent_t ev_bits[3] = {nullptr, nullptr, nullptr};   // the pass's last bits segment has been packed
+    // urhgpu_chunk_power_stats_dev (the live sniffer's per-chunk pass): its own partials and pinned results, so that a chunk never waits for or
+    // disturbs what a flush's demodulation pass keeps in the arenas
+    urh::Arena chunk_work;
+    double *h_chunk = nullptr;             // pinned: {sum, max, sum not exact}
+    long long chunk_launches = 0;          // kernel launches issued by urhgpu_chunk_power_stats_dev (urhgpu_chunk_stats_launches)
 };
 constexpr size_t kSegBlockBytes = 4096;      // 16 progress counters on their own 128-byte lines, then the SegState
 

@@ -16,6 +16,7 @@
 
 #include "common.hpp"
 #include "launchers.hpp"
+#include "pairwise.hpp"
 #include "scan.hpp"
 
 namespace urh {
@@ -216,18 +217,11 @@ int launch_minmax(const float *x, int64_t n, float *d_out2, void *scratch, hipSt
 }
 
 // ---- numpy's float32 summation (np.add.reduce, what np.mean / np.var use) -------------------------------------------
-// np.add.reduce walks a contiguous array in chunks of the ufunc buffer size (8192 elements) and accumulates
-//     total = (((0 + pw(chunk 0)) + pw(chunk 1)) + ...)                       [verified against numpy 2.2 on this host]
-// where pw is the pairwise routine of numpy/core/src/umath/loops_utils.h.src (float32 accumulators):
-//   n < 8            : res = 0; res += a[i] in order
-//   n <= 128         : 8 accumulators r[j] = a[j]; r[j] += a[i + j] for i = 8, 16, ... < n - n % 8;
-//                      res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)); then the n % 8 tail in order
-//   n > 128          : n2 = n / 2; n2 -= n2 % 8; pw(a, n2) + pw(a + n2, n - n2)
-// A full chunk is therefore a perfect binary tree over 64 leaves of 128 elements.  Reproducing detect_center's bin
-// width (float(np.var(rect))) bit for bit needs exactly this order: leaves are evaluated one per thread, each full
-// chunk's tree by one thread (k_pairwise_chunks), and the O(n / 8192) chunk totals plus the irregular last chunk
-// are accumulated on the host.  mode 0: a[i] = x[i]; mode 1: a[i] = (x[i] - mean)^2 in float32.
-constexpr int kPwChunk = 8192, kPwLeaf = 128, kPwLeavesPerChunk = kPwChunk / kPwLeaf;
+// The order (pieces of 8192 elements, each a pairwise tree over leaves of <= 128) is written down in pairwise.hpp
+// [verified against numpy 2.2 on this host].  Reproducing detect_center's bin width (float(np.var(rect))) bit for bit needs
+// exactly this order: leaves are evaluated one per thread, each full chunk's tree by one thread (k_pairwise_chunks), and the
+// O(n / 8192) chunk totals plus the irregular last chunk are accumulated on the host.
+// mode 0: a[i] = x[i]; mode 1: a[i] = (x[i] - mean)^2 in float32.
 struct Leaf { int64_t off; int32_t len; int32_t pad; };
 
 __device__ __forceinline__ float pw_elem(const float *x, int64_t i, int mode, float mean) {
@@ -245,23 +239,7 @@ __global__ __launch_bounds__(256) void k_pairwise_leaves(const float *x, int64_t
     int64_t off = k * kPwLeaf;
     int n = kPwLeaf;
     if (k >= n_regular) { off = extra[k - n_regular].off; n = extra[k - n_regular].len; }
-    float res;
-    if (n < 8) {
-        res = 0.f;
-        for (int i = 0; i < n; ++i) res += pw_elem(x, off + i, mode, mean);
-    } else {
-        float r[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = pw_elem(x, off + j, mode, mean);
-        int i;
-        for (i = 8; i < n - (n % 8); i += 8) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) r[j] += pw_elem(x, off + i + j, mode, mean);
-        }
-        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; ++i) res += pw_elem(x, off + i, mode, mean);
-    }
-    sums[k] = res;
+    sums[k] = pw_leaf(n, [&](int i) { return pw_elem(x, off + i, mode, mean); });
 }
 
 // one thread per full chunk: perfect binary tree over its 64 leaf sums, in place order
@@ -281,15 +259,13 @@ __global__ __launch_bounds__(64) void k_pairwise_chunks(const float *leaf_sums, 
 
 static void build_leaves(int64_t off, int64_t n, std::vector<Leaf> &out) {
     if (n <= kPwLeaf) { out.push_back(Leaf{off, (int32_t)n, 0}); return; }
-    int64_t n2 = n / 2;
-    n2 -= n2 % 8;
+    const int64_t n2 = pw_split(n);
     build_leaves(off, n2, out);
     build_leaves(off + n2, n - n2, out);
 }
 static float combine_leaves(int64_t n, const float *sums, int64_t &next) {
     if (n <= kPwLeaf) return sums[next++];
-    int64_t n2 = n / 2;
-    n2 -= n2 % 8;
+    const int64_t n2 = pw_split(n);
     volatile float a = combine_leaves(n2, sums, next);
     volatile float b = combine_leaves(n - n2, sums, next);
     return a + b;
