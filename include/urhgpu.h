@@ -697,7 +697,7 @@ int urhgpu_test_hot_probe(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const ur
                           int graded, int launches, int keep, void *d_chunks_out, int64_t *n_chunks_out, float *dur_ms, float *gap_ms, int bubble_us,
                           int load_kind);
 /* ... bubble_us > 0: a one-wavefront kernel that idles for that long between two hot kernels; load_kind != 0 (event_mode 1 or 2): synthetic
- * company on a second stream beside every hot kernel (capi.hip: arithmetic / random loads on the CUs the hot mask leaves out, thousands of
+ * company on a second stream beside every hot kernel (probes.hip: arithmetic / random loads on the CUs the hot mask leaves out, thousands of
  * short high-priority workgroups, six empty kernels).  The same stamps inside the PRODUCT's passes
  * (tools/inrun_anatomy.py): urhgpu_test_hot_stamps(1) makes every complex64 2-FSK pass run the stamped instantiation (process-wide; the
  * stamps sit in ChunkInfo fields the tile tail does not read), urhgpu_test_fetch_chunk_tables copies the chunk tables of the context's three

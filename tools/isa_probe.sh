@@ -7,7 +7,7 @@ HERE=$(cd "$(dirname "$0")/.." && pwd)
 OUT=/tmp/isa; mkdir -p $OUT
 awk '/^\/\/ ---- host-side launchers/{exit} {print}' $HERE/urh_amd/csrc/demod_runs.hip > $OUT/probe.hip
 cat >> $OUT/probe.hip <<EOT
-bool g_force_state_bytes = false; bool g_stamp_probe = false; thread_local HotEvents g_hot_events;
+bool g_force_state_bytes = false; bool g_stamp_probe = false;
 template __global__ void $INST(const RunArgs);
 }
 EOT

@@ -1,5 +1,5 @@
 // Finds arguments on which the FMA and the non-FMA evaluation of glibc's sinf / cosf round differently (about one float in 10^9):
-// the discriminating inputs of urhgpu_host_libm_check (capi.hip).  Scans every float with |x| < 120.
+// the discriminating inputs of urhgpu_host_libm_check (ctx.hip).  Scans every float with |x| < 120.
 #include <math.h>
 #include <omp.h>
 #include <stdint.h>

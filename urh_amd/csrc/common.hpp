@@ -65,6 +65,7 @@ struct Arena {
     }
     void release();
 };
+inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 }  // namespace urh
 
@@ -101,7 +102,7 @@ struct urhgpu_ctx {
     int prof_used = 0;                     // pairs recorded since urhgpu_ctx_profile_begin
     bool prof_on = false;
     bool prof_bracket = false;             // also bracket the hot launch with stream-level events (URH_PROFILE_BRACKET)
-    void *shard = nullptr;                 // state of a sharded pass between its phases (capi.hip: ShardSession)
+    void *shard = nullptr;                 // state of a sharded pass between its phases (shard.hip: ShardSession)
     // Pipelined mode (urhgpu_ctx_set_pipelined): the hot kernel of a pass runs on `stream`, everything after it on
     // `tail_stream`, with two scratch arenas used alternately, so that the hot kernel of the NEXT pass overlaps the
     // (latency-bound, nearly empty) tail of this one -- and, with three arenas, of the one before.  Outputs are complete after urhgpu_ctx_join / urhgpu_ctx_sync.
@@ -119,7 +120,7 @@ struct urhgpu_ctx {
     int flip = 0;
     bool tail_pending = false;
     int tile_parity = 0;           // which of the two huge-row counters (d_tickets[8..9]) the current pass appends to
-    // streamed passes (urhgpu_stream_*; capi.hip: iq_to_bits_streamed): per scratch arena 16 progress counters + one SegState
+    // streamed passes (urhgpu_stream_*; stream_pass.hip: iq_to_bits_streamed): per scratch arena 16 progress counters + one SegState
     void *d_seg = nullptr;         // 3 x kSegBlockBytes, zero between passes
     bool seg_dirty[3] = {false, false, false};   // a pass failed between its hot launch and its last segment: counters not trusted
     int tune_stream_segments = 7;  // rows segments of a streamed pass's tail (1: no streaming), urhgpu_ctx_set_tuning("stream_segments")
@@ -155,12 +156,23 @@ namespace urh {
 int iq_to_bits_streamed(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, const urhgpu_outputs *out, void *host_blob,
                         int64_t cap_host, hipEvent_t ev_ready, bool *streamed, const void *h_iq, void *stage_blob = nullptr, bool *staged = nullptr,
                         hipEvent_t ev_rows = nullptr, int len16 = 0);
-}
-
-namespace urh {
 // hipStreamSynchronize for the short waits of the estimator calls: the runtime's blocking wait wakes the host tens of microseconds after
 // the stream has drained; polling the stream does not (tuning key "spin_wait" 0 takes the blocking wait; after 5 ms of polling it is
 // taken anyway)
 hipError_t wait_stream(const urhgpu_ctx *ctx, hipStream_t s);
-int join_tail(urhgpu_ctx *ctx);    // capi.hip: the caller's stream waits for the tail of the last pipelined pass
+int join_tail(urhgpu_ctx *ctx);    // ctx.hip: the caller's stream waits for the tail of the last pipelined pass
+// host-buffer entry points: a device mirror of `host` in the staging arena (reserved by the caller), copied on the context's stream
+inline int stage_in(urhgpu_ctx *ctx, const void *host, size_t bytes, void **dev) {
+    void *d = ctx->staging.take(bytes ? bytes : 16);
+    if (!d) return URHGPU_ERR_ARG;
+    if (bytes) URH_HIP(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *dev = d;
+    return URHGPU_OK;
 }
+// ... and a result back into `host`: the copy, then the wait for the context's stream
+inline int fetch_out(urhgpu_ctx *ctx, void *host, const void *dev, size_t bytes) {
+    URH_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    URH_HIP(hipStreamSynchronize(ctx->stream));
+    return URHGPU_OK;
+}
+}  // namespace urh

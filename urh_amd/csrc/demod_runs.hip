@@ -1749,12 +1749,23 @@ __global__ void k_test_atan2f(const float *y, const float *x, int64_t n, float *
 bool g_force_state_bytes = false;
 std::atomic<long long> g_wide_int_launches{0};   // urhgpu_test_wide_int_launches: hot launches that took the WIDEI instantiation
 bool g_stamp_probe = false;          // test hook (urhgpu_test_hot_stamps): complex64 2-FSK passes run the STAMPS instantiation of the bit-plane kernel
-thread_local HotEvents g_hot_events;
+
+// One launch of a bit-plane instantiation: as an extended launch with the dispatch's own events where the caller offered some that no
+// launch has taken yet (HotEvents::used tells the caller), as a plain launch otherwise.  Only order 2 is ever given `ev`.
+template <void (*K)(const RunArgs), int SRC, int MOD>
+static void launch_bp(unsigned grid, const RunArgs &a, hipStream_t s, HotEvents *ev) {
+    const dim3 block(kBlock * bp_waves<SRC, MOD>());
+    if (ev && (ev->start || ev->stop) && !ev->used) {
+        hipExtLaunchKernelGGL(K, dim3(grid), block, (size_t)a.lds_pad, s, ev->start, ev->stop, 0, a);
+        ev->used = true;
+    } else
+        hipLaunchKernelGGL(K, dim3(grid), block, (size_t)a.lds_pad, s, a);
+}
 
 // `a` describes the whole capture (a.n samples, chunk table / slab for n_main + has_tail chunks):
 // one launch over the whole tiles, one one-workgroup launch for the partial tile at the end.
 template <int SRC, int DT, int MOD, bool O2, bool WQ>
-static void launch_runs_4(RunArgs a, hipStream_t s) {
+static void launch_runs_4(RunArgs a, hipStream_t s, HotEvents *ev) {
     // a.launch_part: 0 = every chunk; 1 = every chunk but the first (it alone needs the left halo of a sharded capture,
     // which may still be in flight); 2 = the first chunk only
     const int part = a.launch_part;
@@ -1775,32 +1786,17 @@ static void launch_runs_4(RunArgs a, hipStream_t s) {
         const bool stamps = a.stamp_probe && stamps_ok;
         // integer FSK captures with wide phase steps (RunArgs::wide_int): the instantiation with the wide loop
         constexpr bool widei_ok = SRC == SRC_IQ && (DT == URHGPU_DT_I8 || DT == URHGPU_DT_I16) && MOD == URHGPU_MOD_FSK;      // (unsigned samples are not centred: re > 0)
+        const unsigned grid = (unsigned)(c_hi - c_lo);
         if (widei_ok && a.wide_int && planes_ok && (O2 || a.order == 4)) {
             ++g_wide_int_launches;
-            const bool ev = (g_hot_events.start || g_hot_events.stop) && !g_hot_events.used;
-            if (O2 && ev) {
-                hipExtLaunchKernelGGL((k_demod_runs_bp<SRC, DT, MOD, WQ, true, 1, false, widei_ok>), dim3((unsigned)(c_hi - c_lo)), dim3(kBlock * bp_waves<SRC, MOD>()),
-                                      (size_t)a.lds_pad, s, g_hot_events.start, g_hot_events.stop, 0, a);
-                g_hot_events.used = true;
-            } else if (O2)
-                hipLaunchKernelGGL((k_demod_runs_bp<SRC, DT, MOD, WQ, true, 1, false, widei_ok>), dim3((unsigned)(c_hi - c_lo)), dim3(kBlock * bp_waves<SRC, MOD>()), (size_t)a.lds_pad, s, a);
-            else
-                hipLaunchKernelGGL((k_demod_runs_bp<SRC, DT, MOD, WQ, true, 2, false, widei_ok>), dim3((unsigned)(c_hi - c_lo)), dim3(kBlock * bp_waves<SRC, MOD>()), (size_t)a.lds_pad, s, a);
-        } else
-        if (planes_ok && O2 && stamps && (g_hot_events.start || g_hot_events.stop) && !g_hot_events.used) {
-            hipExtLaunchKernelGGL((k_demod_runs_bp<SRC_IQ, URHGPU_DT_F32, URHGPU_MOD_FSK, true, true, 1, true>), dim3((unsigned)(c_hi - c_lo)), dim3(kBlock * bp_waves<SRC, MOD>()),
-                                  (size_t)a.lds_pad, s, g_hot_events.start, g_hot_events.stop, 0, a);
-            g_hot_events.used = true;
-        } else if (planes_ok && O2 && !stamps && (g_hot_events.start || g_hot_events.stop) && !g_hot_events.used) {
-            hipExtLaunchKernelGGL((k_demod_runs_bp<SRC, DT, MOD, WQ>), dim3((unsigned)(c_hi - c_lo)), dim3(kBlock * bp_waves<SRC, MOD>()),
-                                  (size_t)a.lds_pad, s, g_hot_events.start, g_hot_events.stop, 0, a);
-            g_hot_events.used = true;
+            if (O2) launch_bp<k_demod_runs_bp<SRC, DT, MOD, WQ, true, 1, false, widei_ok>, SRC, MOD>(grid, a, s, ev);
+            else launch_bp<k_demod_runs_bp<SRC, DT, MOD, WQ, true, 2, false, widei_ok>, SRC, MOD>(grid, a, s, nullptr);
         } else if (planes_ok && O2 && stamps)
-            hipLaunchKernelGGL((k_demod_runs_bp<SRC_IQ, URHGPU_DT_F32, URHGPU_MOD_FSK, true, true, 1, true>), dim3((unsigned)(c_hi - c_lo)), dim3(kBlock * bp_waves<SRC, MOD>()), (size_t)a.lds_pad, s, a);
+            launch_bp<k_demod_runs_bp<SRC_IQ, URHGPU_DT_F32, URHGPU_MOD_FSK, true, true, 1, true>, SRC, MOD>(grid, a, s, ev);
         else if (planes_ok && O2)
-            hipLaunchKernelGGL((k_demod_runs_bp<SRC, DT, MOD, WQ>), dim3((unsigned)(c_hi - c_lo)), dim3(kBlock * bp_waves<SRC, MOD>()), (size_t)a.lds_pad, s, a);
+            launch_bp<k_demod_runs_bp<SRC, DT, MOD, WQ>, SRC, MOD>(grid, a, s, ev);
         else if (planes_ok && a.order == 4)
-            hipLaunchKernelGGL((k_demod_runs_bp<SRC, DT, MOD, WQ, true, 2>), dim3((unsigned)(c_hi - c_lo)), dim3(kBlock * bp_waves<SRC, MOD>()), (size_t)a.lds_pad, s, a);
+            launch_bp<k_demod_runs_bp<SRC, DT, MOD, WQ, true, 2>, SRC, MOD>(grid, a, s, nullptr);
         else
             hipLaunchKernelGGL((k_demod_runs<SRC, DT, MOD, O2, WQ, true>), dim3((unsigned)(c_hi - c_lo)), dim3(kBlock), 0, s, a);
     }
@@ -1813,35 +1809,34 @@ static void launch_runs_4(RunArgs a, hipStream_t s) {
 }
 
 template <int SRC, int DT, int MOD>
-static void launch_runs_3(const RunArgs &a, bool write_qad, hipStream_t s) {
-    const bool o2 = (a.order == 2);
-    if (o2) {
-        if (write_qad) launch_runs_4<SRC, DT, MOD, true, true>(a, s);
-        else launch_runs_4<SRC, DT, MOD, true, false>(a, s);
+static void launch_runs_3(const RunArgs &a, bool write_qad, hipStream_t s, HotEvents *ev) {
+    if (a.order == 2) {
+        if (write_qad) launch_runs_4<SRC, DT, MOD, true, true>(a, s, ev);
+        else launch_runs_4<SRC, DT, MOD, true, false>(a, s, ev);
     } else {
-        if (write_qad) launch_runs_4<SRC, DT, MOD, false, true>(a, s);
-        else launch_runs_4<SRC, DT, MOD, false, false>(a, s);
+        if (write_qad) launch_runs_4<SRC, DT, MOD, false, true>(a, s, ev);
+        else launch_runs_4<SRC, DT, MOD, false, false>(a, s, ev);
     }
 }
 
 template <int DT>
-static int launch_runs_2(const RunArgs &a, int mod, bool write_qad, hipStream_t s) {
+static int launch_runs_2(const RunArgs &a, int mod, bool write_qad, hipStream_t s, HotEvents *ev) {
     switch (mod) {
-        case URHGPU_MOD_ASK: launch_runs_3<SRC_IQ, DT, URHGPU_MOD_ASK>(a, write_qad, s); return URHGPU_OK;
-        case URHGPU_MOD_FSK: launch_runs_3<SRC_IQ, DT, URHGPU_MOD_FSK>(a, write_qad, s); return URHGPU_OK;
-        case URHGPU_MOD_OTHER: launch_runs_3<SRC_IQ, DT, URHGPU_MOD_OTHER>(a, write_qad, s); return URHGPU_OK;
+        case URHGPU_MOD_ASK: launch_runs_3<SRC_IQ, DT, URHGPU_MOD_ASK>(a, write_qad, s, ev); return URHGPU_OK;
+        case URHGPU_MOD_FSK: launch_runs_3<SRC_IQ, DT, URHGPU_MOD_FSK>(a, write_qad, s, ev); return URHGPU_OK;
+        case URHGPU_MOD_OTHER: launch_runs_3<SRC_IQ, DT, URHGPU_MOD_OTHER>(a, write_qad, s, ev); return URHGPU_OK;
         default: return URHGPU_ERR_ARG;
     }
 }
 
 // Fused demod + run segmentation over IQ (ASK / FSK / OTHER).
-int launch_demod_runs_iq(const RunArgs &a, int dtype, int mod, bool write_qad, hipStream_t s) {
+int launch_demod_runs_iq(const RunArgs &a, int dtype, int mod, bool write_qad, hipStream_t s, HotEvents *ev) {
     switch (dtype) {
-        case URHGPU_DT_F32: return launch_runs_2<URHGPU_DT_F32>(a, mod, write_qad, s);
-        case URHGPU_DT_I8: return launch_runs_2<URHGPU_DT_I8>(a, mod, write_qad, s);
-        case URHGPU_DT_U8: return launch_runs_2<URHGPU_DT_U8>(a, mod, write_qad, s);
-        case URHGPU_DT_I16: return launch_runs_2<URHGPU_DT_I16>(a, mod, write_qad, s);
-        case URHGPU_DT_U16: return launch_runs_2<URHGPU_DT_U16>(a, mod, write_qad, s);
+        case URHGPU_DT_F32: return launch_runs_2<URHGPU_DT_F32>(a, mod, write_qad, s, ev);
+        case URHGPU_DT_I8: return launch_runs_2<URHGPU_DT_I8>(a, mod, write_qad, s, ev);
+        case URHGPU_DT_U8: return launch_runs_2<URHGPU_DT_U8>(a, mod, write_qad, s, ev);
+        case URHGPU_DT_I16: return launch_runs_2<URHGPU_DT_I16>(a, mod, write_qad, s, ev);
+        case URHGPU_DT_U16: return launch_runs_2<URHGPU_DT_U16>(a, mod, write_qad, s, ev);
         default: return URHGPU_ERR_DTYPE;
     }
 }
@@ -1899,8 +1894,8 @@ bool runs_streamable(const RunArgs &a) {
 }
 
 // Run segmentation over an already demodulated float32 signal (grab_pulse_lens proper).
-int launch_runs_qad(const RunArgs &a, hipStream_t s) {
-    launch_runs_3<SRC_QAD, URHGPU_DT_F32, URHGPU_MOD_OTHER>(a, false, s);
+int launch_runs_qad(const RunArgs &a, hipStream_t s, HotEvents *ev) {
+    launch_runs_3<SRC_QAD, URHGPU_DT_F32, URHGPU_MOD_OTHER>(a, false, s, ev);
     return URHGPU_OK;
 }
 

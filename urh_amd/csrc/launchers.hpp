@@ -1,4 +1,4 @@
-// Argument structs and host-side launcher prototypes shared by the kernel files and capi.hip.
+// Argument structs and host-side launcher prototypes shared by the kernel files and the units behind the C ABI (pass.hpp).
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>
@@ -54,17 +54,16 @@ struct RunArgs {
     int stamp_probe;         // tools/boundary_probe.py: the STAMPS instantiation of the bit-plane kernel (complex64 2-FSK only); 0 in the product
     float thr[kMaxOrder - 1];
 };
-extern bool g_force_state_bytes;
+extern bool g_force_state_bytes;   // test hook: order 2 through the state-byte kernel too
 extern std::atomic<long long> g_wide_int_launches;
 extern bool g_stamp_probe;
 extern int g_tail_skip;            // pulse_table.hip: measurement hook (urhgpu_test_tail_skip)
-// urhgpu_ctx_profile_*: start / stop events attached to the next bit-plane hot-kernel dispatch itself (hipExtLaunchKernelGGL:
-// the kernel's own begin / end timestamps, what rocprofv3 reports); `used` says the launcher took them
+// Start / stop events a caller offers to a hot launch (`ev`): attached to the bit-plane kernel's dispatch itself (hipExtLaunchKernelGGL: the
+// kernel's own begin / end timestamps, what rocprofv3 reports, and its completion signal); `used` says the launcher took them
 struct HotEvents { hipEvent_t start = nullptr, stop = nullptr; bool used = false; };
-extern thread_local HotEvents g_hot_events;   // test hook: order 2 through the state-byte kernel too
 int launch_wide_probe(const void *d_iq, int dtype, int64_t n, float noise_sqrd, int32_t *h_out, hipStream_t s);      // demod_runs.hip: k_wide_probe
-int launch_demod_runs_iq(const RunArgs &a, int dtype, int mod, bool write_qad, hipStream_t s);
-int launch_runs_qad(const RunArgs &a, hipStream_t s);
+int launch_demod_runs_iq(const RunArgs &a, int dtype, int mod, bool write_qad, hipStream_t s, HotEvents *ev = nullptr);
+int launch_runs_qad(const RunArgs &a, hipStream_t s, HotEvents *ev = nullptr);
 bool runs_streamable(const RunArgs &a);       // RunArgs::progress is honoured for these arguments (bit-plane kernel, whole tiles)
 int launch_afp_demod(const RunArgs &a, int dtype, int mod, int grid, hipStream_t s);
 void launch_test_div(uint64_t seed, int reps, unsigned long long *d_mismatches, hipStream_t s);
