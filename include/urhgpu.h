@@ -752,6 +752,35 @@ int urhgpu_chunk_power_stats_dev(urhgpu_ctx *ctx, const void *d_src, int dtype, 
 /* Diagnostics: kernel launches urhgpu_chunk_power_stats_dev has issued on this context. */
 int urhgpu_chunk_stats_launches(urhgpu_ctx *ctx, int64_t *n_launches);
 
+/* ---- the estimators on one rank of a sharded capture (urh_amd/sharding.py: ShardedPipeline.detect_noise_level / detect_center) -------
+ * detect_noise_level (AutoInterpretation.py:60-91): d_iq holds the samples [pos_base, pos_base + n_local) of a capture of n_total; chunk k
+ * (counted from the END of the capture, as in urhgpu_magnitude_chunk_stats_dev) covers [n_total - (k + 1) chunk, n_total - k chunk).
+ * d_sum[k] / d_max[k] (DEVICE double[n_chunks]) = fp64 sum / max of the magnitudes of the samples of chunk k that lie in the shard;
+ * 0.0 and 0.0 where there is none; a NaN magnitude makes the chunk's max NaN.  The caller adds the ranks' sums and folds their maxima. */
+int urhgpu_magnitude_chunk_partials_dev(urhgpu_ctx *ctx, const void *d_iq, int dtype, int64_t n_local, int64_t pos_base, int64_t n_total,
+                                        int64_t chunk, int64_t n_chunks, double *d_sum, double *d_max);
+/* The part of numpy's pairwise float32 sum (urhgpu_pairwise_sum_f32_dev; csrc/pairwise.hpp has the order) that one rank can evaluate:
+ * d_x holds the elements [g_off, g_off + m_local) of a float32 sequence of m_total; mode 0 sums x[i], mode 1 (x[i] - mean)^2.  d_out
+ * (DEVICE float[cap], 8-byte aligned) receives the record below, *n_out (HOST, may be NULL) its length in words, which depends on (m_local,
+ * g_off, m_total) alone: URHGPU_PW_REC_PIECES + the number of full pieces of 8192 elements wholly inside the range
+ * (URHGPU_ERR_CAPACITY when cap is smaller).  Asynchronous on the context's stream.
+ *   words [0:2) g_off, [2:4) m_local (int64); [4] min, [5] max of the rank's elements by util.minmax's comparisons (+inf / -inf when
+ *         no element compares); [6] the rank's first element; [7] the number of words (int32)
+ *   HEAD  the elements, mapped through `mode`, of the leaf that the START of the range cuts (also a range inside one leaf that begins
+ *         before it): fewer than 128
+ *   FIRST / LAST  the first / last piece the range touches without holding all of it: the sums of its leaves that lie wholly inside,
+ *         the leaf whose first multiple of 64 (relative to the piece) is 64 s in slot s (leaves of a piece are 64 .. 128 elements long)
+ *   TAIL  the mapped elements of the leaf that only the END of the range cuts
+ *   PIECES  one sum per full piece wholly inside the range, ascending
+ * Words nobody wrote are zero.  sharding.pairwise_combine finishes the sum from the ranks' records. */
+#define URHGPU_PW_REC_HEAD 8
+#define URHGPU_PW_REC_FIRST 136
+#define URHGPU_PW_REC_LAST 264
+#define URHGPU_PW_REC_TAIL 392
+#define URHGPU_PW_REC_PIECES 520
+int urhgpu_pairwise_partial_f32_dev(urhgpu_ctx *ctx, const float *d_x, int64_t m_local, int64_t g_off, int64_t m_total, int mode, float mean,
+                                    float *d_out, int64_t cap, int64_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -175,6 +175,8 @@ PROTOTYPES = {
     "urhgpu_test_atan2f_dev": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "urhgpu_chunk_power_stats_dev": (_i, [_vp, _vp, _i, _i64, _vp, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "urhgpu_chunk_stats_launches": (_i, [_vp, C.POINTER(_i64)]),
+    "urhgpu_magnitude_chunk_partials_dev": (_i, [_vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "urhgpu_pairwise_partial_f32_dev": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _f, _vp, _i64, C.POINTER(_i64)]),
 }
 
 _lib = None

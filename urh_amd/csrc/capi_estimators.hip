@@ -313,4 +313,44 @@ int urhgpu_magnitude_chunk_stats_dev(urhgpu_ctx *ctx, const void *d_iq, int dtyp
     return URHGPU_OK;
 }
 
+// ---- one rank of a sharded capture (shard_estimators.hip) ------------------------------------------------------
+int urhgpu_magnitude_chunk_partials_dev(urhgpu_ctx *ctx, const void *d_iq, int dtype, int64_t n_local, int64_t pos_base, int64_t n_total,
+                                        int64_t chunk, int64_t n_chunks, double *d_sum, double *d_max) {
+    if (!ctx || n_local < 0 || pos_base < 0 || n_total < 0 || pos_base + n_local > n_total || n_chunks < 0 || (n_chunks > 0 && chunk <= 0) ||
+        (n_chunks > 0 && (!d_sum || !d_max)) || (n_local > 0 && !d_iq))
+        return URHGPU_ERR_ARG;
+    if (n_chunks > 0 && n_chunks > n_total / chunk) return URHGPU_ERR_ARG;          // the chunks lie inside the capture
+    if (dtype_bytes(dtype) == 0) return URHGPU_ERR_DTYPE;
+    if ((uintptr_t)d_iq & (uintptr_t)(dtype_bytes(dtype) - 1)) return URHGPU_ERR_ARG;
+    if (n_chunks == 0) return URHGPU_OK;
+    URH_HIP(hipSetDevice(ctx->device));
+    URH_TRY(join_tail(ctx));
+    URH_TRY(ctx->arena.reserve(sp_mag_scratch_bytes(n_chunks) + 1024));
+    ctx->arena.reset();
+    void *scratch = ctx->arena.take(sp_mag_scratch_bytes(n_chunks));
+    if (!scratch) return URHGPU_ERR_ARG;
+    URH_TRY(launch_mag_chunk_partials(d_iq, dtype, n_local, pos_base, n_total, chunk, n_chunks, d_sum, d_max, scratch, ctx->stream));
+    URH_HIP(hipGetLastError());
+    return URHGPU_OK;
+}
+
+int urhgpu_pairwise_partial_f32_dev(urhgpu_ctx *ctx, const float *d_x, int64_t m_local, int64_t g_off, int64_t m_total, int mode, float mean,
+                                    float *d_out, int64_t cap, int64_t *n_out) {
+    if (!ctx || m_local < 0 || g_off < 0 || m_total < 0 || g_off + m_local > m_total || (mode != 0 && mode != 1) || !d_out ||
+        ((uintptr_t)d_out & 7) || (m_local > 0 && !d_x) || ((uintptr_t)d_x & 3))
+        return URHGPU_ERR_ARG;
+    const int64_t words = pairwise_partial_words(m_local, g_off, m_total);
+    if (n_out) *n_out = words;
+    if (cap < words) return URHGPU_ERR_CAPACITY;
+    URH_HIP(hipSetDevice(ctx->device));
+    URH_TRY(join_tail(ctx));
+    URH_TRY(ctx->arena.reserve(pairwise_partial_scratch_bytes(m_local) + 1024));
+    ctx->arena.reset();
+    void *scratch = ctx->arena.take(pairwise_partial_scratch_bytes(m_local));
+    if (!scratch) return URHGPU_ERR_ARG;
+    URH_TRY(launch_pairwise_partial(d_x, m_local, g_off, m_total, mode, mean, d_out, scratch, ctx->stream));
+    URH_HIP(hipGetLastError());
+    return URHGPU_OK;
+}
+
 }  // extern "C"

@@ -18,6 +18,7 @@
 #include "cmul.hpp"
 #include "common.hpp"
 #include "launchers.hpp"
+#include "magnitude.hpp"
 
 namespace urh {
 
@@ -557,35 +558,6 @@ int launch_iir(const double *a, int64_t M, const double *b, int64_t N, const flo
 // Magnitudes (util.pyx:128-136): float input -> (double) sqrtf(I*I + Q*Q) in fp32; integer input -> products and sum
 // in C `int` (wrapping, as the reference's generated code), sqrt in double.
 // ---------------------------------------------------------------------------------------------------------------
-template <int DT> struct MagLoad;
-template <> struct MagLoad<URHGPU_DT_F32> {
-    static __device__ __forceinline__ double mag(const void *p, int64_t i) {
-        const float2 v = ((const float2 *)p)[i];
-        return (double)__builtin_sqrtf(v.x * v.x + v.y * v.y);
-    }
-};
-template <class T2> __device__ __forceinline__ double int_mag(int re, int im) {
-    const int s = (int)((unsigned)(re * re) + (unsigned)(im * im));
-    return __builtin_sqrt((double)s);
-}
-template <> struct MagLoad<URHGPU_DT_I8> {
-    static __device__ __forceinline__ double mag(const void *p, int64_t i) { const char2 v = ((const char2 *)p)[i]; return int_mag<void>(v.x, v.y); }
-};
-template <> struct MagLoad<URHGPU_DT_U8> {
-    static __device__ __forceinline__ double mag(const void *p, int64_t i) { const uchar2 v = ((const uchar2 *)p)[i]; return int_mag<void>(v.x, v.y); }
-};
-template <> struct MagLoad<URHGPU_DT_I16> {
-    static __device__ __forceinline__ double mag(const void *p, int64_t i) { const short2 v = ((const short2 *)p)[i]; return int_mag<void>(v.x, v.y); }
-};
-template <> struct MagLoad<URHGPU_DT_U16> {
-    static __device__ __forceinline__ double mag(const void *p, int64_t i) {
-        const ushort2 v = ((const ushort2 *)p)[i];
-        // 65535^2 overflows C int: wrap like the reference (unsigned arithmetic, same two's-complement bits)
-        const int s = (int)((unsigned)v.x * (unsigned)v.x + (unsigned)v.y * (unsigned)v.y);
-        return __builtin_sqrt((double)s);
-    }
-};
-
 template <int DT>
 __global__ __launch_bounds__(256) void k_magnitudes(const void *iq, int64_t n, double *out) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)

@@ -362,6 +362,14 @@ int launch_median_filter(const double *data, int64_t n, int k, float *out, hipSt
 constexpr int kDtAboveFlags = 100;       // launch_message_ranges: `d_iq` is a float32 array of 0 / 1 above-noise flags (launch_above_flags)
 int pairwise_sum_f32(urhgpu_ctx *ctx, const float *d_x, int64_t n, int mode, float mean, float *out);
 int launch_hist_edges(const float *x, int64_t n, const double *d_edges, int n_edges, int64_t *d_counts, hipStream_t s);
+// ---- shard_estimators.hip (the estimators' partial reductions on one rank of a sharded capture) ------------------
+size_t sp_mag_scratch_bytes(int64_t n_chunks);
+int launch_mag_chunk_partials(const void *iq, int dtype, int64_t n_local, int64_t pos_base, int64_t n_total, int64_t chunk, int64_t n_chunks,
+                              double *d_sum, double *d_max, void *scratch, hipStream_t s);
+int64_t pairwise_partial_words(int64_t m_local, int64_t g_off, int64_t m_total);
+size_t pairwise_partial_scratch_bytes(int64_t m_local);
+int launch_pairwise_partial(const float *x, int64_t m_local, int64_t g_off, int64_t m_total, int mode, float mean, float *rec, void *scratch,
+                            hipStream_t s);
 // ---- chunk_stats.hip (the live sniffer's pass over an incoming chunk) -------------------------------------------
 size_t chunk_stats_scratch_bytes(int dtype, int64_t n_rows);
 int launch_chunk_stats(const void *d_src, int dtype, int64_t n_rows, void *d_dst, int64_t store_rows, void *scratch, double *h_out, hipStream_t s);

@@ -308,6 +308,78 @@ class GpuShardEngine(DevicePipeline):
     def costas_stats(self):
         return self.ctx.costas_stats()
 
+    def costas_qad(self):
+        """the shard's demodulated signal (float32 (n_local,)) once it has resolved: what an auto-center pass estimates from"""
+        return self._res.qad
+
+    def set_center(self, center):
+        """the center the pass's remaining phases (the pulse table) use instead of the parameters' own"""
+        self._pre[2].center = float(center)
+
+    # ---- the estimators' partial reductions (sharding.py: detect_noise_level / detect_center; csrc/shard_estimators.hip) ----
+    def _own(self, t, what):
+        """everything a rank can get wrong about a shard on its own, refused before anything is exchanged"""
+        if not t.is_cuda or t.device != self.device:
+            raise ValueError(f"{what}: the shard lies on {t.device}, the engine runs on {self.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: the shard must be contiguous")
+        self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def noise_partials(self, iq_local, pos_base, n_total, chunk, n_chunks):
+        """float64 (2, n_chunks): fp64 sum and max of the magnitudes of the intersection of every chunk with the shard"""
+        from .signal_functions import dtype_code
+        torch = self.torch
+        iq = torch.view_as_real(iq_local) if iq_local.dtype == torch.complex64 else iq_local
+        if iq.dim() != 2 or iq.shape[1] != 2:
+            raise ValueError("IQ must be an (N, 2) tensor or complex64 (N,)")
+        code = dtype_code(_torch_dtype(iq))
+        self._own(iq, "detect_noise_level")
+        out = torch.empty((2, int(n_chunks)), dtype=torch.float64, device=self.device)
+        if n_chunks:
+            _lib.check(_lib.load().urhgpu_magnitude_chunk_partials_dev(
+                self.ctx.handle, C.c_void_p(iq.data_ptr()), code, int(iq.shape[0]), int(pos_base), int(n_total), int(chunk), int(n_chunks),
+                C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr())))
+        out._urh_keep = iq
+        return out
+
+    def compact_gt(self, x, thr):
+        """x[x > thr], order kept -> (float32 tensor of len(x) whose first `count` elements are the kept ones, int64 (1,) count)"""
+        torch = self.torch
+        if x.dtype != torch.float32 or x.dim() != 1:
+            raise ValueError("detect_center: a float32 1-D tensor (the shard's demodulated signal)")
+        self._own(x, "detect_center")
+        n = int(x.shape[0])
+        kept = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
+        _lib.check(_lib.load().urhgpu_compact_gt_dev(self.ctx.handle, C.c_void_p(x.data_ptr()), n, float(thr), C.c_void_p(kept.data_ptr()),
+                                                     C.c_void_p(cnt.data_ptr())))
+        kept._urh_keep = x
+        return kept, cnt
+
+    def pairwise_partial(self, x, g_off, m_total, mode, mean, words):
+        """the record of urhgpu_pairwise_partial_f32_dev for x = elements [g_off, g_off + len(x)) of a sequence of m_total, padded with
+        zeros to `words` float32 (every rank gathers the same shape)"""
+        torch = self.torch
+        self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        rec = torch.zeros(int(words), dtype=torch.float32, device=self.device)
+        n_out = C.c_int64(0)
+        _lib.check(_lib.load().urhgpu_pairwise_partial_f32_dev(self.ctx.handle, C.c_void_p(x.data_ptr()) if x.numel() else None, int(x.shape[0]),
+                                                               int(g_off), int(m_total), int(mode), float(mean), C.c_void_p(rec.data_ptr()),
+                                                               int(words), C.byref(n_out)))
+        rec._urh_keep = x
+        return rec
+
+    def histogram(self, x, edges):
+        """np.histogram(x, bins=edges) of the rank's elements: int64 (len(edges) - 1,) on the device"""
+        torch = self.torch
+        self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        d_edges = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.float64)).to(self.device)
+        counts = torch.empty(len(edges) - 1, dtype=torch.int64, device=self.device)
+        _lib.check(_lib.load().urhgpu_histogram_f32_dev(self.ctx.handle, C.c_void_p(x.data_ptr()) if x.numel() else None, int(x.shape[0]),
+                                                        C.c_void_p(d_edges.data_ptr()), len(edges), C.c_void_p(counts.data_ptr())))
+        counts._urh_keep = (x, d_edges)
+        return counts
+
     def rows(self, summaries):
         torch = self.torch
         self._keep += (summaries,)

@@ -32,6 +32,11 @@ runs the loop across the shards, then the phases above from the shard's demodula
     4. halo        one all-gather of 4 bytes: every shard's last demodulated value (the seam of the pulse table), then
                    summary / rows / flags exactly as above.
 
+Estimators: `detect_noise_level` and `detect_center` of the whole capture from the ranks' shards -- partial reductions per rank and small
+all-gathers (one for the noise level; four for the center: kept counts, two records of numpy's float32 pairwise sum evaluated from the
+rank's global offset, histogram counts), every result a pure function of gathered data (`pairwise_combine`, `center_parts`).  A PSK
+pass detects its own center with `auto_center=True`.
+
 The orchestration below is engine-agnostic: `engine` is the GPU engine (urh_amd.shard_engine.GpuShardEngine,
 HIP kernels behind the C ABI) in production; the CPU test-suite drives the same orchestration with the executable
 model of the kernels (tests/model_shard.py) over a world_size-2 gloo group.
@@ -378,6 +383,178 @@ def costas_exchange(comm, summary, resolve, end_state):
         rounds += 1
 
 
+# ---- numpy's float32 summation tree across ranks (csrc/pairwise.hpp has the order; csrc/shard_estimators.hip writes the records) ----
+PW_PIECE, PW_LEAF = 8192, 128               # kPwChunk, kPwLeaf
+PW_REC_HEAD, PW_REC_FIRST, PW_REC_LAST, PW_REC_TAIL, PW_REC_PIECES = 8, 136, 264, 392, 520      # URHGPU_PW_REC_* (include/urhgpu.h)
+HIST_GATHER_BINS = 1 << 22                  # bins per all-gather of detect_center's histogram (32 MiB of int64 per rank)
+
+
+def pairwise_inside_pieces(g_off: int, m_local: int, m_total: int):
+    """[pa, pb): the full pieces of PW_PIECE elements that lie wholly inside [g_off, g_off + m_local) of a sequence of m_total"""
+    pa = -(-g_off // PW_PIECE)
+    pb = min((g_off + m_local) // PW_PIECE, m_total // PW_PIECE)
+    return pa, max(pa, pb)
+
+
+def pairwise_record_words(g_off: int, m_local: int, m_total: int) -> int:
+    """length in float32 words of the record urhgpu_pairwise_partial_f32_dev writes for that range"""
+    pa, pb = pairwise_inside_pieces(g_off, m_local, m_total)
+    return PW_REC_PIECES + pb - pa
+
+
+def pairwise_piece_leaves(p: int, m_total: int):
+    """the leaves of piece p as (offset in the piece, length): 64 leaves of 128 for a full piece, pw's recursive split (the left part
+    is n // 2 rounded down to a multiple of 8) for the irregular last one"""
+    if p < m_total // PW_PIECE:
+        return [(k * PW_LEAF, PW_LEAF) for k in range(PW_PIECE // PW_LEAF)]
+    out = []
+
+    def split(off, n):
+        if n <= PW_LEAF:
+            out.append((off, n))
+            return
+        n2 = n // 2
+        n2 -= n2 % 8
+        split(off, n2)
+        split(off + n2, n - n2)
+    split(0, m_total % PW_PIECE)
+    return out
+
+
+def pairwise_leaf_sum(a) -> np.float32:
+    """pw over one leaf (len(a) <= PW_LEAF) in float32, as pw_leaf (csrc/pairwise.hpp): 8 strided accumulators, their fixed tree, the
+    len % 8 tail in order; fewer than 8 elements: in order from 0"""
+    a = np.asarray(a, dtype=np.float32)
+    n = len(a)
+    with np.errstate(all="ignore"):
+        if n < 8:
+            res = np.float32(0.0)
+            for v in a:
+                res = np.float32(res + v)
+            return res
+        nb = n - n % 8
+        r = np.add.accumulate(a[:nb].reshape(-1, 8), axis=0, dtype=np.float32)[-1]       # r[j] += a[i + j], row after row
+        res = np.float32(np.float32(np.float32(r[0] + r[1]) + np.float32(r[2] + r[3])) +
+                         np.float32(np.float32(r[4] + r[5]) + np.float32(r[6] + r[7])))
+        for v in a[nb:]:
+            res = np.float32(res + v)
+        return res
+
+
+def pairwise_tree(leaf_sums, lengths) -> np.float32:
+    """pw's additions above the leaves: leaf_sums[i] is the sum of a leaf of lengths[i] elements, in order"""
+    vals = [np.float32(v) for v in leaf_sums]
+    pos = 0
+
+    def node(n):
+        nonlocal pos
+        if n <= PW_LEAF:
+            v = vals[pos]
+            pos += 1
+            return v
+        n2 = n // 2
+        n2 -= n2 % 8
+        left = node(n2)
+        right = node(n - n2)
+        return np.float32(left + right)
+    with np.errstate(all="ignore"):
+        return node(int(sum(lengths)))
+
+
+def _record_headers(records):
+    recs = np.ascontiguousarray(records, dtype=np.float32)
+    recs = recs.reshape(len(recs), -1)
+    hdr = np.ascontiguousarray(recs[:, 0:4]).view(np.int64)
+    return recs, [int(v) for v in hdr[:, 0]], [int(v) for v in hdr[:, 1]]
+
+
+def pairwise_combine(records, m_total: int) -> np.float32:
+    """np.add.reduce of a float32 sequence of m_total elements from the ranks' records (urhgpu_pairwise_partial_f32_dev; rank order,
+    rows padded to one length): a pure function of its arguments, so every rank that evaluates it gets the same bits.  Leaves that
+    a shard boundary cuts are finished from the ranks' raw elements with pw_leaf's arithmetic, pieces that one cuts from their leaf
+    sums, and the pieces are accumulated left to right -- all in float32 (numpy float32 scalars: no excess precision)."""
+    recs, g_offs, m_locals = _record_headers(records)
+    m_total = int(m_total)
+    if m_total <= 0:
+        return np.float32(0.0)
+    ranks = [r for r in range(len(recs)) if m_locals[r] > 0]
+    at = 0
+    for r in ranks:
+        if g_offs[r] != at:
+            raise ValueError("pairwise_combine: the ranks' ranges do not tile the sequence")
+        at += m_locals[r]
+    if at != m_total:
+        raise ValueError("pairwise_combine: the ranks' ranges do not tile the sequence")
+    n_pieces = -(-m_total // PW_PIECE)
+    sums = np.zeros(n_pieces + 1, dtype=np.float32)          # sums[0]: the 0 np.add.reduce starts from
+    have = np.zeros(n_pieces, dtype=bool)
+    for r in ranks:
+        pa, pb = pairwise_inside_pieces(g_offs[r], m_locals[r], m_total)
+        sums[1 + pa:1 + pb] = recs[r, PW_REC_PIECES:PW_REC_PIECES + pb - pa]
+        have[pa:pb] = True
+    ends = np.array([g_offs[r] + m_locals[r] for r in ranks], dtype=np.int64)
+    for p in np.nonzero(~have)[0].tolist():
+        leaves = pairwise_piece_leaves(p, m_total)
+        vals = []
+        for off, ln in leaves:
+            l0, l1 = p * PW_PIECE + off, p * PW_PIECE + off + ln
+            k = int(np.searchsorted(ends, l0, side="right"))      # the rank that holds element l0
+            r = ranks[k]
+            if ends[k] >= l1:                                      # the leaf lies wholly inside that rank
+                area = PW_REC_FIRST if p == g_offs[r] // PW_PIECE else PW_REC_LAST
+                vals.append(recs[r, area + (off + 63) // 64])
+                continue
+            raw = []
+            while k < len(ranks) and g_offs[ranks[k]] < l1:
+                r = ranks[k]
+                lo, hi = max(l0, g_offs[r]), min(l1, int(ends[k]))
+                src = PW_REC_HEAD if l0 < g_offs[r] else PW_REC_TAIL
+                raw.append(recs[r, src:src + hi - lo])
+                k += 1
+            vals.append(pairwise_leaf_sum(np.concatenate(raw)))
+        sums[1 + p] = pairwise_tree(vals, [ln for _, ln in leaves])
+    with np.errstate(all="ignore"):
+        return np.add.accumulate(sums, dtype=np.float32)[-1]      # ((0 + piece 0) + piece 1) + ...: left to right
+
+
+def minmax_combine(records):
+    """util.minmax (util.pyx:20-36) of the whole sequence from the records' words 4-6: seeded with the sequence's first element, a NaN
+    never replaces a value -- so a NaN first element stays, and any other is ignored.  Returns (min, max) as floats, None when every
+    rank is empty."""
+    recs, _, m_locals = _record_headers(records)
+    ranks = [r for r in range(len(recs)) if m_locals[r] > 0]
+    if not ranks:
+        return None
+    mn = mx = recs[ranks[0], 6]
+    for r in ranks:
+        if recs[r, 4] < mn:
+            mn = recs[r, 4]
+        if recs[r, 5] > mx:
+            mx = recs[r, 5]
+    return float(mn), float(mx)
+
+
+def center_parts(kept_counts, max_size=None):
+    """detect_center's trimmed sequence S = R[int(0.05 K) : int(0.95 K)] (cut to max_size) of the ranks' kept samples R, from the gathered
+    kept counts: (m, [(local begin, g_r, m_r) per rank]) -- rank r's part of S is kept_r[begin : begin + m_r], elements [g_r, g_r + m_r) of
+    S (m_r may be 0).  A pure function of the gathered counts."""
+    counts = [int(v) for v in kept_counts]
+    total = sum(counts)
+    a, b = int(0.05 * total), int(0.95 * total)                    # AutoInterpretation.py:231
+    m = b - a
+    if max_size is not None and m > max_size:                      # :233-234
+        m = int(max_size)
+    parts, c0 = [], 0
+    for k in counts:
+        lo, hi = max(c0, a), min(c0 + k, a + m)
+        if hi > lo:
+            parts.append((lo - c0, lo - a, hi - lo))
+        else:
+            parts.append((0, min(max(c0 - a, 0), m), 0))
+        c0 += k
+    return m, parts
+
+
 def shard_bounds(n_total: int, world: int):
     """[begin, end) of every rank's shard: equal shards of ceil(n/world) samples rounded up to a multiple of
     64 (so that every shard starts 16-byte aligned for every IQ dtype), the last rank takes what is left.
@@ -398,6 +575,7 @@ class ShardedPipeline:
         self.engine, self.comm = engine, comm
         self.rank, self.world = comm.rank, comm.world
         self.last_costas = None                  # PSK: the last pass's Costas exchange (rounds, this rank's chunks by map / checkpoint / serial)
+        self.last_center = None                  # the center the last pass's pulse table was built with (auto_center: the detected one)
 
     # bench.py / DevicePipeline compatible surface ------------------------------------------------
     @property
@@ -449,22 +627,110 @@ class ShardedPipeline:
         tails = c.all_gather(e.fir_tail(iq_local, m - 1))
         return e.fir(iq_local, taps, tails[self.rank - 1] if self.rank > 0 else None)
 
-    def iq_to_bits(self, iq_local, p, want_qad=True, pos_base=None, n_total=None, halo_given=False, left_halo=None, left_raw=None):
+    # the estimators that feed the pipelines: partial reductions per rank + small all-gathers -------------------
+    def _estimator_engine(self, *names):
+        missing = [n for n in names if not hasattr(self.engine, n)]
+        if missing:
+            raise NotImplementedError(f"the engine offers no {', '.join(missing)}")
+        return self.engine
+
+    def detect_noise_level(self, iq_local, pos_base=None, n_total=None):
+        """AutoInterpretation.detect_noise_level(get_magnitudes(capture)) (AutoInterpretation.py:60-91) for the capture whose shard
+        [pos_base, pos_base + n_local) this rank holds; pos_base / n_total default as in iq_to_bits.  The chunk geometry is the
+        capture's (estimators.noise_chunks(n_total): chunks counted from the end, the front remainder dropped): a chunk may straddle
+        any number of shards.  Every rank reduces the intersection of every chunk with its shard to an fp64 sum and a max
+        (urhgpu_magnitude_chunk_partials_dev), ONE all-gather moves 2 * n_chunks doubles per rank, and every rank adds the sums in
+        rank order and folds the maxima (a NaN stays) before the decision of the single-GPU function.  A capture of three samples or
+        fewer gives 0 without a collective; on one rank the value is detect_noise_level_dev's.
+        The sums are fp64 sums in another order than numpy's pairwise one ("detect_noise_level"): the float32-cast chunk
+        means agree with numpy's unless an fp64 sum lies within an ulp of a float32 rounding boundary."""
+        from .estimators import noise_chunks, noise_level_from_chunk_stats
+        e, c = self._estimator_engine("noise_partials"), self.comm
+        n_local = int(iq_local.shape[0])
+        pos_base = self.rank * n_local if pos_base is None else int(pos_base)
+        n_total = self.world * n_local if n_total is None else int(n_total)
+        if pos_base < 0 or pos_base + n_local > n_total:
+            raise ValueError("detect_noise_level: the shard does not lie inside the capture")
+        chunk, n_chunks = noise_chunks(n_total) if n_total > 3 else (1, 0)
+        part = e.noise_partials(iq_local, pos_base, n_total, chunk, n_chunks)     # checks the shard before anything is exchanged
+        if n_total <= 3:                                                          # :61-62
+            return 0
+        both = np.asarray(c.all_gather(part).cpu().numpy(), dtype=np.float64).reshape(self.world, 2, n_chunks)
+        sums = np.zeros(n_chunks, np.float64)
+        for r in range(self.world):
+            sums = sums + both[r, 0]
+        maxs = both[:, 1].max(axis=0)                                             # np.max: a NaN stays, as within a rank
+        return noise_level_from_chunk_stats(sums, maxs, chunk)
+
+    def detect_center(self, qad_local, max_size=None):
+        """AutoInterpretation.detect_center(qad, max_size) (AutoInterpretation.py:226-277) where qad is the concatenation of the ranks'
+        qad_local (float32, 1-D, on the rank's device) in rank order: bit-equal to estimators.detect_center_dev on the whole signal,
+        None on every rank where that gives None.  max_size must be the same on every rank.  Four all-gathers at most:
+            1. the kept counts of the local compaction qad > -4 -> the trim [int(0.05 K), int(0.95 K)) and every rank's part of it
+            2. the records of np.mean's float32 sum (urhgpu_pairwise_partial_f32_dev, which also takes min / max in that pass)
+            3. the records of np.var's second sum, (x - mean)^2 in float32
+            4. the int64 counts of np.histogram over the edges every rank computes from the same scalars (more than HIST_GATHER_BINS
+               bins -- a nearly constant signal -- go in blocks of that many)
+        The sums are numpy's float32 pairwise sums bit for bit (pairwise_combine finishes what the shard boundaries cut).  Every
+        early return is decided from gathered data."""
+        from .estimators import peaks_center
+        e, c = self._estimator_engine("compact_gt", "pairwise_partial", "histogram"), self.comm
+        if max_size is not None and int(max_size) < 0:
+            raise ValueError("detect_center: max_size must not be negative")
+        kept, cnt = e.compact_gt(qad_local, -4.0)                                 # checks the shard before anything is exchanged
+        counts = c.all_gather(cnt).cpu().numpy().reshape(-1)
+        m, parts = center_parts(counts, max_size)
+        if m == 0:
+            return None             # np.var of an empty slice is nan -> np.arange raises ValueError -> None (:246-248)
+        begin, g_r, m_r = parts[self.rank]
+        mine = kept[begin:begin + m_r]
+        words = max(pairwise_record_words(g, k, m) for _, g, k in parts)
+        recs = c.all_gather(e.pairwise_partial(mine, g_r, m, 0, 0.0, words)).cpu().numpy()
+        hist_min, hist_max = minmax_combine(recs)
+        with np.errstate(all="ignore"):
+            mean = pairwise_combine(recs, m) / np.float32(m)                      # np.mean: float32 sum / float32 count
+            recs = c.all_gather(e.pairwise_partial(mine, g_r, m, 1, float(mean), words)).cpu().numpy()
+            hist_step = float(pairwise_combine(recs, m) / np.float32(m))          # float(np.var(rect)) (:240)
+        try:
+            with np.errstate(all="ignore"):
+                edges = np.arange(hist_min, hist_max + hist_step, hist_step)      # :243-245
+            if len(edges) < 2:
+                return None         # np.histogram with fewer than 2 edges raises ValueError -> None (:246-248)
+        except (ZeroDivisionError, ValueError):
+            return None
+        local = e.histogram(mine, edges)
+        n_bins = len(edges) - 1
+        total = np.zeros(n_bins, np.int64)
+        for b0 in range(0, n_bins, HIST_GATHER_BINS):
+            b1 = min(n_bins, b0 + HIST_GATHER_BINS)
+            total[b0:b1] = c.all_gather(local[b0:b1]).cpu().numpy().reshape(self.world, -1).sum(axis=0)
+        return peaks_center(total, edges)
+
+    def iq_to_bits(self, iq_local, p, want_qad=True, pos_base=None, n_total=None, halo_given=False, left_halo=None, left_raw=None, auto_center=False):
         """iq_local: this rank's shard.  pos_base / n_total default to equal shards of len(iq_local).
         halo_given (the same on every rank): whoever distributed the capture handed every rank but the first the two samples that
         precede its shard (left_halo: (2, 2) in the shard's dtype, or complex64 (2,)) -- 16 bytes more per rank to read from the
         file.  The halo exchange is then skipped: two all-gathers per pass (ASK: three) instead of three (four).
         PSK: every rank but the first passes left_raw, the costas_halo_samples(p.costas_loop_bandwidth, pos_base) raw samples
         before its shard ((m, 2) in the shard's dtype, or complex64 (m,); a longer tail is cut to them); halo_given / left_halo do
-        not apply.  The pass's Costas exchange is recorded in `last_costas`; the result always carries the shard's qad."""
+        not apply.  The pass's Costas exchange is recorded in `last_costas`; the result always carries the shard's qad.
+        auto_center (the same on every rank: it adds collectives): a PSK pass calls `detect_center` on the demodulated signal once the
+        Costas exchange has written it and builds its pulse table with the detected center (p.center where detection gives None);
+        `last_center` is the value used.  ASK / FSK raise ValueError: their fused hot kernel needs the center before the demodulated
+        signal exists.  The recipe there is two passes: one with want_qad=True, `detect_center(result.qad)`, then a second pass with
+        that center."""
         e, c = self.engine, self.comm
+        if auto_center and p.modulation_type != "PSK":
+            raise ValueError("auto_center needs a PSK pass: for ASK / FSK run a pass with want_qad=True, detect_center(result.qad), "
+                             "then a second pass with that center")
         n_local = int(iq_local.shape[0])
         if pos_base is None:
             pos_base = self.rank * n_local
         if n_total is None:
             n_total = self.world * n_local
         if p.modulation_type == "PSK":
-            return self._iq_to_bits_psk(iq_local, p, int(pos_base), int(n_total), left_raw)
+            return self._iq_to_bits_psk(iq_local, p, int(pos_base), int(n_total), left_raw, bool(auto_center))
+        self.last_center = p.center
         if halo_given and self.rank > 0 and left_halo is None:
             raise ValueError("halo_given: ranks > 0 pass the two samples before their shard as left_halo")
         pending = left = None
@@ -494,9 +760,11 @@ class ShardedPipeline:
             flags = e.bits_prepare(merged_all)
             return e.bits_finish(c.all_gather(flags))
 
-    def _iq_to_bits_psk(self, iq_local, p, pos_base, n_total, left_raw):
+    def _iq_to_bits_psk(self, iq_local, p, pos_base, n_total, left_raw, auto_center=False):
         """the PSK pass (module docstring, steps 0-4).  Everything a rank can get wrong on its own is checked before the first collective."""
         e, c = self.engine, self.comm
+        if auto_center:
+            self._estimator_engine("costas_qad", "set_center", "compact_gt", "pairwise_partial", "histogram")
         if n_total <= 2:
             raise ValueError("PSK: a capture of two samples or fewer does not shard")
         if self.rank > 0:
@@ -514,6 +782,12 @@ class ShardedPipeline:
                             "respeculation_rounds": respec}
         lasts = c.all_gather(e.costas_last())                 # every shard's last demodulated value: the seam of the pulse table
         left = lasts[self.rank - 1] if self.rank > 0 else None
+        self.last_center = p.center
+        if auto_center:
+            center = self.detect_center(e.costas_qad())
+            if center is not None:
+                self.last_center = float(center)
+                e.set_center(self.last_center)
         summary = e.runs(iq_local, left, pos_base, n_total, self.rank, self.world, p, True)
         merge = e.rows(c.all_gather(summary))
         flags = e.bits_prepare(c.all_gather(merge) if merge is not None else None)
