@@ -113,6 +113,11 @@ int urhgpu_ctx_set_pipelined(urhgpu_ctx *ctx, int enable, void *tail_stream);
  *   "wide_int"                 1: one-shot and sharded passes over SIGNED INTEGER FSK captures take the hot kernel's instantiation with the
  *                              wide loop (phase steps beyond the fast loop's window, e.g. +-100 kHz at 1 MS/s: a quarter faster there, 5 %
  *                              slower on narrow captures); capture streams decide by themselves from a probe of their captures.  default 0
+ *   "costas_dev_rounds"        who drives the re-speculation rounds of the parallel Costas loop (PSK, more than 8192 samples).  -1, default: the
+ *                              host for one-shot passes on a context that is not pipelined (one stream synchronisation per round), the device in
+ *                              capture streams and on pipelined contexts, with a number of rounds queued that follows from the capture's length.
+ *                              0 .. 24: the device everywhere, with exactly that many re-speculation rounds queued behind the first; a chain still
+ *                              open after them is finished serially.  The demodulated signal is the same bit for bit whatever the value.
  *   "shard_summary_generic"    1: the local pass of urhgpu_shard_runs_dev as the three generic resolve launches instead of the one-launch
  *                              summary kernel (A/B and test use: the summaries are byte-equal).  default 0
  * Unknown key: URHGPU_ERR_ARG. */
@@ -136,9 +141,15 @@ int urhgpu_host_libm_check(int64_t *out4);
  * resolved -- out4 = {chunks whose true start state matched a speculative candidate, chunks evaluated serially until they
  * met a candidate's checkpoint, chunks evaluated serially to the end (or fully gated), re-speculation rounds}.
  * Synchronises the stream.  Diagnostics only: the output is exact in every case.
- * (The PSK path of urhgpu_afp_demod_dev / urhgpu_iq_to_bits_dev synchronises the stream itself: the host has to learn
- * whether the chunk chain closed before it launches the final pass.) */
+ * (A one-shot PSK pass on a context that is not pipelined synchronises the stream itself, once per round: the host learns whether the
+ * chunk chain closed before it launches the next round or the final pass.  On a pipelined context, in a capture stream and with the
+ * tuning key "costas_dev_rounds" >= 0 the rounds are driven from the device and the host waits for nothing: the stats are then copied
+ * behind the pass's Costas kernels, asynchronously, and are valid once the pass has been synchronised by whoever consumes its result --
+ * which these two calls do.)
+ * urhgpu_ctx_costas_stats5: the five counters as the kernels keep them -- out5 = {by candidate, by checkpoint, serial, chunk the last
+ * stitch stopped in front of (the chunk count: finished), re-speculation rounds}; synchronises every stream of the context. */
 int urhgpu_ctx_costas_stats(urhgpu_ctx *ctx, int32_t *out4);
+int urhgpu_ctx_costas_stats5(urhgpu_ctx *ctx, int32_t *out5);
 
 /* Time the dominant kernel (demod + run segmentation) of subsequent fused / grab_pulse_lens calls with
  * HIP events on the context's stream: begin(max_records) arms up to max_records records (one per call); end()
@@ -329,7 +340,9 @@ int urhgpu_iq_to_bits_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const ur
  * stream, urhgpu_ctx_set_pipelined: the stream switches the context to that mode) and the pack kernel + D2H copy of pass i - 2's blob
  * (third stream / copy engine, pinned memory owned by the stream).  Three output slots rotate.
  *   urhgpu_stream_create   n_max: largest capture (samples, < 2^31); p: demodulation + slicing parameters of every pass (ASK / FSK /
- *                          OTHER; PSK synchronises with the host inside the Costas loop: URHGPU_ERR_UNSUPPORTED); want_qad: the
+ *                          OTHER / PSK -- a PSK pass runs its Costas kernels on the context's stream with the re-speculation rounds driven
+ *                          from the device, and the segmentation of the demodulated signal, bits and pack behind them on the tail stream;
+ *                          the Costas scratch for n_max is reserved here); want_qad: the
  *                          demodulated signal is materialised (stays in HBM: urhgpu_host_result::d_qad); want_pos: bit_sample_pos
  *                          is produced and shipped; cap_rows: 0 = the default (urhgpu_stream_capacities), else the pulse-table capacity.
  *   urhgpu_stream_push     queue pass i on d_iq (device; must stay valid until the pass has run), its pack kernel and its D2H copy and
@@ -375,6 +388,8 @@ int urhgpu_stream_flush(urhgpu_stream *st, urhgpu_host_result *out3, int *n_out)
 /* Diagnostics: out4 = {passes pushed, passes whose predicted copy size fell short (their rest was fetched when the result was handed
  * out), bytes the next copy is sized for, blob capacity}. */
 int urhgpu_stream_stats(urhgpu_stream *st, int64_t *out4);
+/* PSK streams: the Costas stats (urhgpu_ctx_costas_stats5's five counters) summed over the passes whose results have been handed out. */
+int urhgpu_stream_costas_stats(urhgpu_stream *st, int64_t *out5);
 /* passes of the stream whose hot kernel was the instantiation with the wide loop for integer captures (signed integer FSK streams probe their
  * captures -- the share of phase steps beyond atan(7/16) per sample -- and pick it from 1 % on; 0 for every other stream) */
 int urhgpu_stream_wide_passes(urhgpu_stream *st, int64_t *n_passes);
@@ -734,6 +749,13 @@ int urhgpu_test_force_tiles_per_chunk(int tiles);
 /* Test hook: hot launches of this process that took the signed-integer instantiation WITH the wide loop (capture streams by their probe,
  * one-shot and sharded passes by the tuning key "wide_int"): what a test of that instantiation checks it has exercised. */
 int64_t urhgpu_test_wide_int_launches(void);
+
+/* Test hooks of the Costas loop.  urhgpu_test_costas_host_syncs: stream synchronisations of this process made by the Costas launchers (the
+ * host-driven rounds of one-shot and sharded passes; the device-driven loop makes none).  urhgpu_test_costas_scratch: out3 = {scratch bytes
+ * reserved for a capture of n samples, one past the device-driven loop's control block as the buffers are carved for loop order 2 / 4, the
+ * block's size}.  Host arithmetic; works without a GPU. */
+int64_t urhgpu_test_costas_host_syncs(void);
+int urhgpu_test_costas_scratch(int64_t n, int loop_order, int64_t *out3);
 
 /* Test hook: elementwise bit-faithful atan2f (the device port of glibc 2.35 atan2f), device pointers. */
 int urhgpu_test_atan2f_dev(urhgpu_ctx *ctx, const float *d_y, const float *d_x, int64_t n, float *d_out);

@@ -83,6 +83,7 @@ PROTOTYPES = {
     "urhgpu_ctx_reserve": (_i, [_vp, _i64, _i]),
     "urhgpu_ctx_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i64), C.c_char_p, _i]),
     "urhgpu_ctx_costas_stats": (_i, [_vp, C.POINTER(C.c_int32)]),
+    "urhgpu_ctx_costas_stats5": (_i, [_vp, C.POINTER(C.c_int32)]),
     "urhgpu_ctx_profile_begin": (_i, [_vp, _i]),
     "urhgpu_ctx_profile_end": (_i, [_vp, C.POINTER(C.c_float), _i, C.POINTER(_i)]),
     "urhgpu_get_magnitudes": (_i, [_vp, _vp, _i, _i64, _vp]),
@@ -112,6 +113,7 @@ PROTOTYPES = {
     "urhgpu_stream_flush": (_i, [_vp, C.POINTER(HostResult), C.POINTER(_i)]),
     "urhgpu_stream_stats": (_i, [_vp, C.POINTER(_i64)]),
     "urhgpu_stream_wide_passes": (_i, [_vp, C.POINTER(_i64)]),
+    "urhgpu_stream_costas_stats": (_i, [_vp, C.POINTER(_i64)]),
     "urhgpu_shard_runs_dev": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _i, _vp, C.POINTER(Params), C.POINTER(Outputs), _vp]),
     "urhgpu_shard_prelaunch_dev": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _i, C.POINTER(Params), C.POINTER(Outputs)]),
     "urhgpu_shard_launch_dev": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _i, _vp, C.POINTER(Params), C.POINTER(Outputs)]),
@@ -171,6 +173,8 @@ PROTOTYPES = {
     "urhgpu_test_force_state_bytes": (_i, [_i]),
     "urhgpu_test_force_tiles_per_chunk": (_i, [_i]),
     "urhgpu_test_wide_int_launches": (_i64, []),
+    "urhgpu_test_costas_host_syncs": (_i64, []),
+    "urhgpu_test_costas_scratch": (_i, [_i64, _i, C.POINTER(_i64)]),
     "urhgpu_test_force_generic_tail": (_i, [_i]),
     "urhgpu_test_atan2f_dev": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "urhgpu_chunk_power_stats_dev": (_i, [_vp, _vp, _i, _i64, _vp, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -320,6 +324,13 @@ class Context:
         """(chunks matched by a candidate, met at a checkpoint, evaluated serially, re-speculation rounds) of the last PSK pass"""
         out = (C.c_int32 * 4)()
         check(load().urhgpu_ctx_costas_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def costas_stats5(self):
+        """the five counters of the last PSK pass as the kernels keep them: (by candidate, by checkpoint, serial, chunk the last stitch
+        stopped in front of -- the chunk count when the chain closed --, re-speculation rounds)"""
+        out = (C.c_int32 * 5)()
+        check(load().urhgpu_ctx_costas_stats5(self._h, out))
         return tuple(int(v) for v in out)
 
     def close(self):

@@ -86,6 +86,10 @@ struct urhgpu_ctx {
     bool tune_spin_wait = true;    // wait_stream polls (see there)
     bool tune_wide_int = false;    // one-shot / sharded passes over signed integer FSK captures take the wide-loop instantiation (RunArgs::wide_int)
     bool tune_shard_summary_generic = false;   // urhgpu_shard_runs_dev: the local pass as launch_resolve (A/B, tests) instead of launch_shard_summary
+    int tune_costas_dev_rounds = -1;   // Costas loop: -1 host-driven rounds for one-shot passes, device-driven on a pipelined context; 0 .. 24: device-driven
+                                   // everywhere with exactly that many re-speculation rounds queued (urhgpu_ctx_set_tuning "costas_dev_rounds")
+    int32_t *costas_stats_next = nullptr;   // the next PSK pass copies its Costas stats here (pinned, 24 bytes; set by urhgpu_stream_*) instead of h_counts[12..]
+    hipStream_t last_tail = nullptr;        // the stream the last urhgpu_iq_to_bits_dev pass queued its last kernel on (the tail stream, or the caller's)
     int wide_int_next = 0;         // the next streamed pass over a signed integer FSK capture takes the wide-loop instantiation (set by urhgpu_stream_*, RunArgs::wide_int)
     char *h_small = nullptr;       // pinned landing zone of the estimators' small results (kSmallPinned bytes): copies into it are truly asynchronous
     int32_t *d_tickets = nullptr;  // 8 zeroed ints: elections of the fused scan kernels (scan.hpp)
@@ -160,6 +164,8 @@ int iq_to_bits_streamed(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhg
 // the stream has drained; polling the stream does not (tuning key "spin_wait" 0 takes the blocking wait; after 5 ms of polling it is
 // taken anyway)
 hipError_t wait_stream(const urhgpu_ctx *ctx, hipStream_t s);
+// pass.hip: room for PSK passes of up to n_max samples -- the Costas scratch, and in the three arenas a pass's scratch plus (without want_qad) its demodulated signal
+int reserve_psk_pass(urhgpu_ctx *ctx, int64_t n_max, int tolerance, bool want_qad);
 int join_tail(urhgpu_ctx *ctx);    // ctx.hip: the caller's stream waits for the tail of the last pipelined pass
 // host-buffer entry points: a device mirror of `host` in the staging arena (reserved by the caller), copied on the context's stream
 inline int stage_in(urhgpu_ctx *ctx, const void *host, size_t bytes, void **dev) {

@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <math.h>
 #include <string.h>
 #include <type_traits>
@@ -219,8 +220,22 @@ struct SpecBuffers {
     int32_t *ungated;      // [n_chunks] un-gated samples in the chunk
     CostasState *resume;   // [1] true state at the start of chunk stats[3] when the stitch hands back to the host
     int32_t *stats;        // [0] chunks resolved by the map, [1] by a checkpoint inside a serial run, [2] fully serial,
-                           // [3] chunk the stitch stopped in front of (n_chunks: finished), [4] re-speculation rounds
+                           // [3] chunk the stitch stopped in front of (n_chunks: finished), [4] re-speculation rounds;
+                           // 64 bytes further on: the device-driven loop's control block (costas_ctl)
 };
+// What the host-driven loop (launch_costas_spec) learns from the stitch and hands to the next round's kernels as arguments, kept on the
+// device instead: the DEV instantiations of the round kernels read it, their stitch rewrites it on exit -- a break stores the next round's
+// {c_from, use_seed = 1, seed_freq = the true loop's frequency there} and counts the round, a closed chain sets `done`, and every round
+// kernel queued behind that returns on this one load.  Zeroed with the stats (one memset): round 0 is {c_from 0, no seed, not done}.
+struct CostasCtl {
+    int64_t c_from;
+    int32_t use_seed;
+    float seed_freq;
+    int32_t done;
+    int32_t rounds;
+};
+// (no pointer of its own in SpecBuffers: the stitch keeps b.stats to its last instruction anyway, a second one cost it two more scalar registers)
+__host__ __device__ __forceinline__ CostasCtl *costas_ctl(const SpecBuffers &b) { return (CostasCtl *)(b.stats + 16); }
 
 __device__ __forceinline__ bool same_state(CostasState a, CostasState b) {
     return __float_as_uint(a.freq) == __float_as_uint(b.freq) && __float_as_uint(a.phase) == __float_as_uint(b.phase);
@@ -252,9 +267,14 @@ template <bool SH, class A> __device__ __forceinline__ bool chunk0_exact(const A
 // Candidates of the chunks c >= c_from.  use_seed: all candidates start with freq = seed_freq (the true loop's own
 // frequency where the chain last broke) instead of the estimate from the data.
 // SH (a shard): the walk back reads into the halo and stops at global sample 1, exactly where the single-GPU walk does.
-template <int DT, int ORDER, bool SH = false>
+// DEV: c_from / use_seed / seed_freq come from the control block (the arguments are ignored), nothing to do once the chain has closed.
+template <int DT, int ORDER, bool SH = false, bool DEV = false>
 __global__ __launch_bounds__(256) void k_costas_spec(const CostasArgsT<SH> a, SpecBuffers b, int64_t n_chunks, int K, int64_t c_from,
                                                       int use_seed, float seed_freq) {
+    if constexpr (DEV) {
+        if (costas_ctl(b)->done) return;
+        c_from = costas_ctl(b)->c_from; use_seed = costas_ctl(b)->use_seed; seed_freq = costas_ctl(b)->seed_freq;
+    }
     const int64_t gid = blockIdx.x * 256ll + threadIdx.x;
     const int64_t c = c_from + gid / K;
     const int k = (int)(gid % K);
@@ -396,7 +416,12 @@ __global__ __launch_bounds__(256) void k_costas_run(const CostasArgsT<SH> a, Spe
     if (k == 0) b.ungated[c] = ung;
 }
 
+template <bool DEV = false>
 __global__ __launch_bounds__(256) void k_costas_map(SpecBuffers b, int64_t n_chunks, int K, int64_t c_from) {
+    if constexpr (DEV) {
+        if (costas_ctl(b)->done) return;
+        c_from = costas_ctl(b)->c_from > 1 ? costas_ctl(b)->c_from : 1;
+    }
     const int64_t c = c_from + blockIdx.x * 256ll + threadIdx.x;
     if (c >= n_chunks) return;
     uint32_t m = 0xFFFFFFFFu;
@@ -438,9 +463,17 @@ __device__ __forceinline__ uint32_t map_compose(uint32_t later, uint32_t earlier
 // SH (a shard): chunk 0 is never taken as exact -- the walk starts at c_from from the true state *b.resume, for c_from == 0 the
 // state the ranks before this one hand over -- and the true state after the shard's last sample is left in b.resume[1].
 constexpr int kStitchBlock = 1024;              // 16 wavefronts: the fast-forward composes 4096 chunk maps per round
-template <int DT, int ORDER, bool SH = false>
+// DEV: c_from comes from the control block, which the exit rewrites for the round queued behind this one (see CostasCtl); the host
+// passes allow_break = 0 to the last stitch it has queued, so the chain always closes.
+template <int DT, int ORDER, bool SH = false, bool DEV = false>
 __global__ __launch_bounds__(kStitchBlock) void k_costas_stitch(const CostasArgsT<SH> a, SpecBuffers b, int64_t n_chunks, int K, int64_t c_from,
                                                                  int allow_break) {
+    if constexpr (DEV) {
+        const int done = costas_ctl(b)->done;
+        c_from = costas_ctl(b)->c_from > 1 ? costas_ctl(b)->c_from : 1;
+        __syncthreads();                            // (every thread has read the block before thread 0 may rewrite it)
+        if (done) return;
+    }
     __shared__ uint32_t s_wp[kStitchBlock / 64];    // per-wavefront composition of its chunk maps
     __shared__ int s_fail, s_cand, s_flags;         // first position where the chain ends; broadcast slots
     __shared__ CostasState s_T;
@@ -570,6 +603,12 @@ __global__ __launch_bounds__(kStitchBlock) void k_costas_stitch(const CostasArgs
         *b.resume = T;
         // the shard's end state: the carrying candidate's, else T (the last chunk ran serially, or is fully gated)
         if constexpr (SH) b.resume[1] = (cand >= 0) ? b.E[(n_chunks - 1) * K + cand] : T;
+        if constexpr (DEV) {
+            CostasCtl *ctl = costas_ctl(b);
+            if (stop_at < n_chunks) { ctl->c_from = stop_at; ctl->use_seed = 1; ctl->seed_freq = T.freq; ctl->rounds += 1; }
+            else ctl->done = 1;
+            b.stats[4] = ctl->rounds;
+        }
     }
 }
 
@@ -618,13 +657,16 @@ __global__ __launch_bounds__(256) void k_costas_final(const CostasArgsT<SH> a, S
     for (; i < i1; ++i) a.out[i] = costas_step_bf<DT == URHGPU_DT_F32, ORDER>(CostasLoad<DT>::at(a.iq, i), st, err, a);
 }
 
+constexpr size_t kCtlSlot = 64;    // the control block's place behind the stats (spec_buffers)
+static_assert(sizeof(CostasCtl) <= kCtlSlot, "control block");
 size_t costas_scratch_bytes(int64_t n) {
     const int64_t nc = (std::max<int64_t>(n - 1, 0) + kChunk - 1) / kChunk + 1;
     return (size_t)nc * kMaxCand * sizeof(CostasState) * 2 + (size_t)nc * kNumCkpt * kMaxCand * sizeof(CostasState) +
-           (size_t)nc * 4 * 3 + (size_t)nc * sizeof(CostasState) + (size_t)nc * kMaxCand * 5 + 3 * 64 + 16 * 256;
+           (size_t)nc * 4 * 3 + (size_t)nc * sizeof(CostasState) + (size_t)nc * kMaxCand * 5 + 3 * 64 + kCtlSlot + 16 * 256;
 }
 
 constexpr int kMaxRounds = 24;     // re-speculation rounds before the stitch stops handing back (and runs serially)
+std::atomic<long long> g_costas_host_syncs{0};     // urhgpu_test_costas_host_syncs: hipStreamSynchronize calls of the host-driven loops
 
 // the speculative buffers of nc chunks, carved from costas_scratch_bytes(n) of scratch
 static SpecBuffers spec_buffers(void *scratch, int64_t nc, int K) {
@@ -642,23 +684,81 @@ static SpecBuffers spec_buffers(void *scratch, int64_t nc, int K) {
     b.is_rep = (uint8_t *)take((size_t)nc * K);
     b.run_count = (int32_t *)take(64);
     b.resume = (CostasState *)take(64);
-    b.stats = (int32_t *)take(64);
+    b.stats = (int32_t *)take(64 + kCtlSlot);           // stats and control block: zeroed by one memset
     return b;
+}
+// (test hook) scratch bytes reserved for n samples / one past the control block as spec_buffers carves it / the block's size
+void costas_scratch_layout(int64_t n, int K, int64_t out3[3]) {
+    const int64_t nc = (std::max<int64_t>(n - 1, 0) + kChunk - 1) / kChunk;
+    const SpecBuffers b = spec_buffers(nullptr, nc, K);
+    out3[0] = (int64_t)costas_scratch_bytes(n);
+    out3[1] = (int64_t)(uintptr_t)costas_ctl(b) + (int64_t)sizeof(CostasCtl);
+    out3[2] = (int64_t)sizeof(CostasCtl);
 }
 
 // NOTE: synchronises the stream (at least once): the host has to learn whether the chunk chain closed.
 template <int DT, int ORDER>
 static int launch_costas_spec(const CostasArgs &a, void *scratch, urhgpu_ctx *ctx);
+// ... and the same rounds driven from the device: nothing but launches and one asynchronous copy of the stats.
+template <int DT, int ORDER>
+static int launch_costas_dev(const CostasArgs &a, void *scratch, urhgpu_ctx *ctx, int rounds, int32_t *h_stats);
 
+// Re-speculation rounds the device-driven loop queues for a capture of nc chunks when nobody says (tuning key costas_dev_rounds = -1).
+// A round that finds the chain closed is a 4-byte memset and four launches that return on one load: kEmptyRoundUs.  Too few rounds have a
+// cliff -- behind the last one the rest of the capture is walked by one wavefront, 1.5 ms per chunk --, so the rule spends what is cheap: as
+// many rounds as fit into kEmptyRoundsShare of the pass's own Costas time, kCostasBaseUs (the latency of one chunk's candidate, run and
+// output pass: what the shortest parallel capture already pays) plus kCostasUsPerChunk for every chunk; never fewer than 2, never more
+// than the host loop's 24.  That is 7 rounds for the shortest parallel capture and 13 for 2^27 samples.
+// NOT MEASURED YET: the three figures are estimates -- five stream packets at about 5 us each; (512 warm-up + 4096 + 256) steps of 94
+// dependent instructions at 9.5 cycles and 2.4 GHz (the step anatomy above costas_step_bf); the 3.3 ms Costas time of 32 768 chunks
+// (profiles/r04f_costas_1gib_kernel_stats.csv).  tools/psk_stream_probe.py measures all three ((c), and (c)'s 0-round times over the
+// sizes); replace them by its figures.
+constexpr double kEmptyRoundUs = 25.0, kCostasBaseUs = 1800.0, kCostasUsPerChunk = 0.046, kEmptyRoundsShare = 0.10;
+static int costas_auto_rounds(int64_t nc) {
+    const double fit = kEmptyRoundsShare * (kCostasBaseUs + kCostasUsPerChunk * (double)nc) / kEmptyRoundUs;
+    return (int)std::min<double>(kMaxRounds, std::max<double>(2.0, fit));
+}
+
+// Which loop: the host-driven one for one-shot passes on a context that is not pipelined; the device-driven one on pipelined contexts
+// (capture streams switch theirs) and wherever the tuning key costas_dev_rounds names a number of rounds.
+// The stats land in ctx->costas_stats_next where a capture stream has named a place of its pass's own, else in h_counts[12..].
 template <int DT>
 static int launch_costas_dt(const CostasArgs &a, void *scratch, urhgpu_ctx *ctx) {
     const bool parallel = (a.loop_order == 2 || a.loop_order == 4) && a.n > 2 * kChunk && scratch != nullptr;
+    int32_t *h_stats = ctx->costas_stats_next ? ctx->costas_stats_next : (int32_t *)(ctx->h_counts + 12);
     if (!parallel) {
         hipLaunchKernelGGL(k_costas<DT>, dim3(1), dim3(64), 0, ctx->stream, a);
-        ctx->h_counts[12] = ctx->h_counts[13] = ctx->h_counts[14] = 0;
+        memset(h_stats, 0, 24);
         return URHGPU_OK;
     }
+    if (ctx->tune_costas_dev_rounds >= 0 || ctx->pipelined) {
+        const int rounds = ctx->tune_costas_dev_rounds >= 0 ? ctx->tune_costas_dev_rounds : costas_auto_rounds((a.n - 1 + kChunk - 1) / kChunk);
+        return a.loop_order == 4 ? launch_costas_dev<DT, 4>(a, scratch, ctx, rounds, h_stats) : launch_costas_dev<DT, 2>(a, scratch, ctx, rounds, h_stats);
+    }
     return a.loop_order == 4 ? launch_costas_spec<DT, 4>(a, scratch, ctx) : launch_costas_spec<DT, 2>(a, scratch, ctx);
+}
+
+template <int DT, int ORDER>
+static int launch_costas_dev(const CostasArgs &a, void *scratch, urhgpu_ctx *ctx, int rounds, int32_t *h_stats) {
+    hipStream_t s = ctx->stream;
+    const int K = (a.loop_order == 4) ? 8 : 4;
+    const int64_t nc = (a.n - 1 + kChunk - 1) / kChunk;
+    SpecBuffers b = spec_buffers(scratch, nc, K);
+    URH_HIP(hipMemsetAsync(b.stats, 0, 64 + kCtlSlot, s));   // the stats and the control block: round 0 starts at chunk 0, unseeded
+    URH_HIP(hipMemsetAsync(b.resume, 0, 64, s));
+    // every round's grids cover all nc chunks: where a round starts is known on the device only
+    const dim3 g_cand((unsigned)((nc * K + 255) / 256)), g_chunk((unsigned)((nc + 255) / 256));
+    for (int round = 0; round <= rounds; ++round) {
+        URH_HIP(hipMemsetAsync(b.run_count, 0, 4, s));       // (a round that finds the chain closed appends nothing: k_costas_run sees 0 entries)
+        hipLaunchKernelGGL((k_costas_spec<DT, ORDER, false, true>), g_cand, dim3(256), 0, s, a, b, nc, K, (int64_t)0, 0, 0.0f);
+        hipLaunchKernelGGL((k_costas_run<DT, ORDER>), g_cand, dim3(256), 0, s, a, b, K);
+        hipLaunchKernelGGL(k_costas_map<true>, g_chunk, dim3(256), 0, s, b, nc, K, (int64_t)1);
+        hipLaunchKernelGGL((k_costas_stitch<DT, ORDER, false, true>), dim3(1), dim3(kStitchBlock), 0, s, a, b, nc, K, (int64_t)1, round < rounds ? 1 : 0);
+    }
+    hipLaunchKernelGGL((k_costas_final<DT, ORDER>), dim3((unsigned)((nc * kNumCkpt + 255) / 256)), dim3(256), 0, s, a, b, nc, K);
+    URH_HIP(hipGetLastError());
+    URH_HIP(hipMemcpyAsync(h_stats, b.stats, 20, hipMemcpyDeviceToHost, s));     // valid once the pass has been synchronised
+    return URHGPU_OK;
 }
 
 template <int DT, int ORDER>
@@ -680,13 +780,14 @@ static int launch_costas_spec(const CostasArgs &a, void *scratch, urhgpu_ctx *ct
         hipLaunchKernelGGL((k_costas_spec<DT, ORDER>), dim3((unsigned)((todo * K + 255) / 256)), dim3(256), 0, s, a, b, nc, K, c_from, use_seed,
                            seed_freq);
         hipLaunchKernelGGL((k_costas_run<DT, ORDER>), dim3((unsigned)((todo * K + 255) / 256)), dim3(256), 0, s, a, b, K);
-        hipLaunchKernelGGL(k_costas_map, dim3((unsigned)((todo + 255) / 256)), dim3(256), 0, s, b, nc, K, std::max<int64_t>(c_from, 1));
+        hipLaunchKernelGGL(k_costas_map<false>, dim3((unsigned)((todo + 255) / 256)), dim3(256), 0, s, b, nc, K, std::max<int64_t>(c_from, 1));
         hipLaunchKernelGGL((k_costas_stitch<DT, ORDER>), dim3(1), dim3(kStitchBlock), 0, s, a, b, nc, K, std::max<int64_t>(c_from, 1),
                            round < kMaxRounds ? 1 : 0);
         URH_HIP(hipGetLastError());
         URH_HIP(hipMemcpyAsync(h, b.stats, 20, hipMemcpyDeviceToHost, s));
         URH_HIP(hipMemcpyAsync(h + 6, b.resume, 8, hipMemcpyDeviceToHost, s));
         URH_HIP(hipStreamSynchronize(s));
+        ++g_costas_host_syncs;
         const int64_t stop_at = h[3];
         if (stop_at >= nc) break;
         c_from = stop_at;
@@ -842,7 +943,7 @@ static int costas_shard_spec_t(urhgpu_ctx *ctx, const CostasArgsSh &a, int64_t n
     const unsigned g = (unsigned)((nc * K + 255) / 256);
     hipLaunchKernelGGL((k_costas_spec<DT, ORDER, true>), dim3(g), dim3(256), 0, s, a, b, nc, K, (int64_t)0, 0, 0.0f);
     hipLaunchKernelGGL((k_costas_run<DT, ORDER, true>), dim3(g), dim3(256), 0, s, a, b, K);
-    hipLaunchKernelGGL(k_costas_map, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, b, nc, K, (int64_t)1);
+    hipLaunchKernelGGL(k_costas_map<false>, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, b, nc, K, (int64_t)1);
     hipLaunchKernelGGL(k_costas_shard_summary, dim3(1), dim3(kSumBlock), 0, s, b, nc, K, (uint32_t *)d_summary);
     URH_HIP(hipGetLastError());
     return URHGPU_OK;
@@ -867,7 +968,7 @@ static int costas_shard_resolve_t(urhgpu_ctx *ctx, const CostasArgsSh &a, int64_
             hipLaunchKernelGGL((k_costas_spec<DT, ORDER, true>), dim3((unsigned)((todo * K + 255) / 256)), dim3(256), 0, s, a, b, nc, K, c_from, 1,
                                seed_freq);
             hipLaunchKernelGGL((k_costas_run<DT, ORDER, true>), dim3((unsigned)((todo * K + 255) / 256)), dim3(256), 0, s, a, b, K);
-            hipLaunchKernelGGL(k_costas_map, dim3((unsigned)((todo + 255) / 256)), dim3(256), 0, s, b, nc, K, c_from);
+            hipLaunchKernelGGL(k_costas_map<false>, dim3((unsigned)((todo + 255) / 256)), dim3(256), 0, s, b, nc, K, c_from);
         }
         hipLaunchKernelGGL((k_costas_stitch<DT, ORDER, true>), dim3(1), dim3(kStitchBlock), 0, s, a, b, nc, K, c_from,
                            round < kMaxRounds ? 1 : 0);
@@ -875,6 +976,7 @@ static int costas_shard_resolve_t(urhgpu_ctx *ctx, const CostasArgsSh &a, int64_
         URH_HIP(hipMemcpyAsync(h, b.stats, 20, hipMemcpyDeviceToHost, s));
         URH_HIP(hipMemcpyAsync(h + 6, b.resume, 8, hipMemcpyDeviceToHost, s));
         URH_HIP(hipStreamSynchronize(s));
+        ++g_costas_host_syncs;
         const int64_t stop_at = h[3];
         if (stop_at >= nc) break;
         c_from = stop_at;                                    // >= 1: the stitch stops in front of the chunk after the one it ran

@@ -229,6 +229,10 @@ int urhgpu_ctx_set_pipelined(urhgpu_ctx *ctx, int enable, void *tail_stream) {
 //   wide_int                 1: passes over SIGNED INTEGER FSK captures take the hot kernel's instantiation with the wide loop (captures whose phase
 //                            steps leave the fast loop's window, DESIGN 4: a quarter faster there, 5 % slower on narrow ones).  Capture streams
 //                            decide by themselves (k_wide_probe); one-shot and sharded passes have no probe to go by: this key is the caller's word.  default 0
+//   costas_dev_rounds        who drives the re-speculation rounds of the parallel Costas loop (costas.hip).  -1 (default): the host for one-shot passes on
+//                            a context that is not pipelined (it synchronises the stream once per round), the device inside capture streams and on
+//                            pipelined contexts, with as many rounds queued as the capture's chunk count affords (costas_auto_rounds).  0 .. 24: the
+//                            device everywhere, with exactly that many re-speculation rounds queued; what they leave is walked serially by the stitch
 //   shard_summary_generic    1: the local pass of urhgpu_shard_runs_dev as the three generic resolve launches instead of k_shard_summary; default 0
 int urhgpu_ctx_set_tuning(urhgpu_ctx *ctx, const char *key, int value) {
     if (!ctx || !key) return URHGPU_ERR_ARG;
@@ -243,6 +247,7 @@ int urhgpu_ctx_set_tuning(urhgpu_ctx *ctx, const char *key, int value) {
     else if (!strcmp(key, "spin_wait")) { ctx->tune_spin_wait = value != 0; }
     else if (!strcmp(key, "shard_summary_generic")) { ctx->tune_shard_summary_generic = value != 0; }
     else if (!strcmp(key, "wide_int")) { ctx->tune_wide_int = value != 0; }
+    else if (!strcmp(key, "costas_dev_rounds")) { if (value < -1 || value > 24) return URHGPU_ERR_ARG; ctx->tune_costas_dev_rounds = value; }
     else if (!strcmp(key, "upload_pieces")) { if (value < 2 || value > kMaxSegments) return URHGPU_ERR_ARG; ctx->tune_upload_pieces = value; }
     else return URHGPU_ERR_ARG;
     return URHGPU_OK;
@@ -354,6 +359,14 @@ int urhgpu_ctx_costas_stats(urhgpu_ctx *ctx, int32_t *out4) {
     URH_HIP(hipStreamSynchronize(ctx->stream));
     const int32_t *h = (const int32_t *)(ctx->h_counts + 12);
     out4[0] = h[0]; out4[1] = h[1]; out4[2] = h[2]; out4[3] = h[4];
+    return URHGPU_OK;
+}
+
+int urhgpu_ctx_costas_stats5(urhgpu_ctx *ctx, int32_t *out5) {
+    if (!ctx || !out5) return URHGPU_ERR_ARG;
+    URH_HIP(hipSetDevice(ctx->device));
+    URH_TRY(urhgpu_ctx_sync(ctx));
+    memcpy(out5, ctx->h_counts + 12, 20);
     return URHGPU_OK;
 }
 

@@ -387,6 +387,8 @@ void launch_copy_shape(const float *in, float *out, int64_t n_samples, int shape
 // ---- costas.hip -----------------------------------------------------------------------------------------------
 size_t costas_scratch_bytes(int64_t n);
 int launch_costas(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad, void *scratch);
+extern std::atomic<long long> g_costas_host_syncs;        // hipStreamSynchronize calls of the Costas launchers (urhgpu_test_costas_host_syncs)
+void costas_scratch_layout(int64_t n, int K, int64_t out3[3]);     // urhgpu_test_costas_scratch
 // sharded captures: one rank's Costas pass between its two phases (urhgpu_shard_costas_spec_dev / _resolve_dev)
 constexpr int kCostasSummaryBytes = 160;     // == URHGPU_COSTAS_SUMMARY_BYTES
 struct CostasShard {

@@ -297,6 +297,17 @@ int end_pipelined_pass(urhgpu_ctx *ctx) {
     return URHGPU_OK;
 }
 
+int reserve_psk_pass(urhgpu_ctx *ctx, int64_t n_max, int tolerance, bool want_qad) {
+    URH_TRY(ctx->aux.reserve(costas_scratch_bytes(n_max) + 1024));
+    const Plan pl = make_plan(ctx, n_max, tolerance);
+    // (as urhgpu_ctx_reserve sizes them: the densest pulse table there can be)
+    const size_t bytes = digitize_scratch_bytes(pl, n_max / ((int64_t)tolerance + 1) + 2, true, true) + (want_qad ? 0 : align256((size_t)n_max * 4));
+    URH_TRY(ctx->arena.reserve(bytes));
+    URH_TRY(ctx->arena_alt.reserve(bytes));
+    URH_TRY(ctx->arena_alt2.reserve(bytes));
+    return URHGPU_OK;
+}
+
 }  // namespace urh
 
 using namespace urh;
@@ -311,6 +322,18 @@ int urhgpu_get_center_thresholds(float center, float spacing, int modulation_ord
     return URHGPU_OK;
 }
 
+// The Costas loop of a PSK pass on the context's stream, its scratch from ctx->aux.  Every Costas kernel of a context runs on that one
+// stream, in order, so the one scratch serves passes that overlap further down (a pipelined pass's tail only reads the demodulated signal).
+// (A capture longer than any before lets the arena grow: hipFree waits for the device first.  Capture streams reserve for n_max up front.)
+static int costas_demod(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad) {
+    URH_TRY(ctx->aux.reserve(costas_scratch_bytes(n) + 1024));
+    ctx->aux.reset();
+    void *scratch = ctx->aux.take(costas_scratch_bytes(n));
+    URH_TRY(launch_costas(ctx, d_iq, n, p, d_qad, scratch));
+    URH_HIP(hipGetLastError());
+    return URHGPU_OK;
+}
+
 // ---- device-pointer entry points -------------------------------------------------------------------
 int urhgpu_afp_demod_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad) {
     if (!ctx || !p || n < 0 || (n > 0 && (!d_iq || !d_qad))) return URHGPU_ERR_ARG;
@@ -322,14 +345,7 @@ int urhgpu_afp_demod_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urh
         return URHGPU_OK;
     }
     if (((uintptr_t)d_iq & 15) || ((uintptr_t)d_qad & 7)) return URHGPU_ERR_ARG;
-    if (p->mod == URHGPU_MOD_PSK) {
-        URH_TRY(ctx->aux.reserve(costas_scratch_bytes(n) + 1024));
-        ctx->aux.reset();
-        void *scratch = ctx->aux.take(costas_scratch_bytes(n));
-        URH_TRY(launch_costas(ctx, d_iq, n, p, d_qad, scratch));
-        URH_HIP(hipGetLastError());
-        return URHGPU_OK;
-    }
+    if (p->mod == URHGPU_MOD_PSK) return costas_demod(ctx, d_iq, n, p, d_qad);
     RunArgs a;
     memset(&a, 0, sizeof(a));
     a.in = d_iq; a.qad = d_qad; a.n = n; a.left_halo = nullptr;
@@ -403,7 +419,10 @@ int urhgpu_iq_to_bits_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const ur
     const Plan pl = make_plan(ctx, n, p->tolerance);
     const bool ask = (p->mod == URHGPU_MOD_ASK);
     const bool fused = !(n <= 2 || p->mod == URHGPU_MOD_PSK);
-    const bool piped = ctx->pipelined && fused;
+    // a PSK pass on a pipelined context: the Costas kernels on the caller's stream (the device drives their rounds: the host never waits),
+    // everything behind them -- segmentation of the demodulated signal, bits, pack -- on the tail stream, the arenas rotating as for fused passes
+    const bool psk_piped = ctx->pipelined && ctx->tail_stream && p->mod == URHGPU_MOD_PSK && n > 2;
+    const bool piped = ctx->pipelined && (fused || psk_piped);
     if (piped) URH_TRY(begin_pipelined_pass(ctx)); else URH_TRY(join_tail(ctx));
     URH_TRY(ctx->arena.reserve(digitize_scratch_bytes(pl, out->cap_rows, ask, true) + (out->qad ? 0 : align256((size_t)n * 4))));
     ctx->arena.reset();
@@ -416,10 +435,20 @@ int urhgpu_iq_to_bits_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const ur
     if (!fused) {
         // no fused kernel: demodulate (zeros for n <= 2, Costas loop for PSK), then segment the qad
         float *qad = out->qad;
-        if (!qad) { qad = (float *)ctx->arena.take((size_t)n * 4); if (!qad) return URHGPU_ERR_ARG; }
-        URH_TRY(urhgpu_afp_demod_dev(ctx, d_iq, n, p, qad));
-        URH_TRY(digitize(ctx, false, qad, n, p, nullptr, out->rows, out->cap_rows, d_n_rows, ctx->d_counts + 8,
-                         ctx->d_counts + 9, pl, 0, nullptr, want_bits ? &tile_bp : nullptr, want_bits ? &tile : nullptr));
+        if (!qad) { qad = (float *)ctx->arena.take((size_t)n * 4); if (!qad) return URHGPU_ERR_ARG; }      // (piped: the rotating arena's, not a later pass's)
+        hipStream_t caller = ctx->stream;
+        if (psk_piped) {
+            URH_TRY(costas_demod(ctx, d_iq, n, p, qad));
+            URH_HIP(hipEventRecord(ctx->ev_hot, ctx->stream));
+            URH_HIP(hipStreamWaitEvent(ctx->tail_stream, ctx->ev_hot, 0));
+            ctx->stream = ctx->tail_stream;
+        } else {
+            URH_TRY(urhgpu_afp_demod_dev(ctx, d_iq, n, p, qad));
+        }
+        const int sd = digitize(ctx, false, qad, n, p, nullptr, out->rows, out->cap_rows, d_n_rows, ctx->d_counts + 8,
+                                ctx->d_counts + 9, pl, 0, nullptr, want_bits ? &tile_bp : nullptr, want_bits ? &tile : nullptr);
+        ctx->stream = caller;
+        URH_TRY(sd);
     } else {
         URH_TRY(digitize(ctx, true, d_iq, n, p, out->qad, out->rows, out->cap_rows, d_n_rows, ctx->d_counts + 8,
                          ctx->d_counts + 9, pl, 0, piped ? ctx->tail_stream : nullptr, want_bits ? &tile_bp : nullptr,
@@ -446,6 +475,7 @@ int urhgpu_iq_to_bits_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const ur
     } else if (out->blob) {
         st = URHGPU_ERR_ARG;                               // the blob mirrors the bit outputs: all of them must be given
     }
+    ctx->last_tail = piped ? ctx->tail_stream : ctx->stream;
     if (piped) URH_TRY(end_pipelined_pass(ctx));
     return st;
 }

@@ -195,6 +195,12 @@ int urhgpu_test_hot_probe(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const ur
 int urhgpu_test_force_state_bytes(int on) { urh::g_force_state_bytes = (on != 0); return URHGPU_OK; }
 int urhgpu_test_force_generic_tail(int on) { urh::g_tile_tail = (on == 0); return URHGPU_OK; }
 int64_t urhgpu_test_wide_int_launches(void) { return (int64_t)urh::g_wide_int_launches.load(); }
+int64_t urhgpu_test_costas_host_syncs(void) { return (int64_t)urh::g_costas_host_syncs.load(); }
+int urhgpu_test_costas_scratch(int64_t n, int loop_order, int64_t *out3) {
+    if (!out3 || n < 0 || (loop_order != 2 && loop_order != 4)) return URHGPU_ERR_ARG;
+    urh::costas_scratch_layout(n, loop_order == 4 ? 8 : 4, out3);
+    return URHGPU_OK;
+}
 
 int urhgpu_test_force_tiles_per_chunk(int tiles) {
     if (tiles < 0 || tiles > 4) return URHGPU_ERR_ARG;

@@ -31,7 +31,8 @@ struct urhgpu_stream {
         char *h_blob2[2] = {nullptr, nullptr};   // pinned, used alternately by the slot's passes: the result handed out at push i (pass i - 3)
                                                  // stays untouched while pass i's copy lands in the other one
         char *h_blob = nullptr;            // the one the slot's current pass copies into
-        int64_t *h_counts = nullptr;       // pinned int64[8]
+        int64_t *h_counts = nullptr;       // pinned int64[8], then ...
+        int32_t *h_costas = nullptr;       // ... PSK: the Costas stats of the slot's current pass (copied behind its Costas kernels)
         hipEvent_t ev_tail = nullptr, ev_copy = nullptr, ev_rows = nullptr, ev_shipped = nullptr;   // ev_shipped: a staged pass's copies are through
         int64_t seq = -1, n = 0, copied = 0;
         bool staged = false;               // the pass's blob arrived in the split layout: copied = head bytes, copied_rows / copied_pos = elements
@@ -62,6 +63,7 @@ struct urhgpu_stream {
     int64_t predicted_rows = 0, predicted_pos = 0;   // staged passes: rows, positions the next pass's copies are sized for
     int64_t short_copies = 0;              // passes whose prediction fell short (diagnostics)
     bool was_pipelined = false;
+    int64_t costas_sum[5] = {0, 0, 0, 0, 0};   // PSK: Costas stats summed over the passes handed out (urhgpu_stream_costas_stats)
 };
 
 namespace {
@@ -70,6 +72,8 @@ size_t a256(size_t x) { return (x + 255) & ~size_t(255); }
 
 void fill_result(urhgpu_stream *st, urhgpu_stream::Slot &s, urhgpu_host_result *r) {
     memset(r, 0, sizeof(*r));
+    if (st->p.mod == URHGPU_MOD_PSK)                         // (the copy was queued in front of the pass's tail: long through)
+        for (int k = 0; k < 5; ++k) st->costas_sum[k] += s.h_costas[k];
     r->seq = s.seq;
     const int64_t *hdr = (const int64_t *)s.h_blob;
     r->n_samples = s.n;
@@ -99,7 +103,6 @@ void fill_result(urhgpu_stream *st, urhgpu_stream::Slot &s, urhgpu_host_result *
     r->pos32 = (hdr[7] & 1) ? (const uint32_t *)(s.h_blob + hdr[14]) : nullptr;
     r->blob = s.h_blob;
     r->d_qad = s.qad;
-    (void)st;
 }
 
 // Queue the pack kernel and the copy of the slot's blob behind the pass's tail, WITHOUT involving the host: the copy stream waits for
@@ -201,7 +204,6 @@ int urhgpu_stream_capacities(int64_t n_max, const urhgpu_params *p, int64_t *cap
 
 int urhgpu_stream_create(urhgpu_ctx *ctx, int64_t n_max, const urhgpu_params *p, int want_qad, int want_pos, int64_t cap_rows, urhgpu_stream **out) {
     if (!ctx || !p || !out || n_max <= 0 || n_max > INT32_MAX) return URHGPU_ERR_ARG;      // int32 row lengths, uint32 positions
-    if (p->mod == URHGPU_MOD_PSK) return URHGPU_ERR_UNSUPPORTED;                       // the Costas path synchronises with the host
     URH_HIP(hipSetDevice(ctx->device));
     urhgpu_stream *st = new (std::nothrow) urhgpu_stream();
     if (!st) return URHGPU_ERR_ARG;
@@ -232,6 +234,9 @@ int urhgpu_stream_create(urhgpu_ctx *ctx, int64_t n_max, const urhgpu_params *p,
     st->was_pipelined = ctx->pipelined;
     if (!ctx->pipelined) { status = urhgpu_ctx_set_pipelined(ctx, 1, nullptr); if (status != URHGPU_OK) { delete st; return status; } }
     status = urhgpu_ctx_reserve(ctx, n_max, p->tolerance);
+    // PSK: the Costas scratch and (without want_qad) the demodulated signal's place in the rotating arenas, for n_max, now -- an arena that
+    // grows later is freed under the passes queued before
+    if (status == URHGPU_OK && p->mod == URHGPU_MOD_PSK) status = urh::reserve_psk_pass(ctx, n_max, p->tolerance, st->want_qad != 0);
     if (status != URHGPU_OK) { urhgpu_stream_destroy(st); return status; }
     if (hipStreamCreateWithFlags(&st->copy_stream, hipStreamNonBlocking) != hipSuccess) { urhgpu_stream_destroy(st); return URHGPU_ERR_HIP; }
     const size_t b_qad = st->want_qad ? a256((size_t)n_max * 4) : 0, b_rows = a256((size_t)st->cap_rows * 16), b_bits = a256((size_t)st->cap_bits),
@@ -243,7 +248,7 @@ int urhgpu_stream_create(urhgpu_ctx *ctx, int64_t n_max, const urhgpu_params *p,
         memset(&s.out, 0, sizeof(s.out));
         if (hipMalloc(&s.dev, b_rows + b_bits + 3 * b_off + b_pos + 256 + 2 * b_blob) != hipSuccess ||
             hipHostMalloc((void **)&s.h_blob2[0], (size_t)(st->cap_blob + st->esc_extra)) != hipSuccess ||
-            hipHostMalloc((void **)&s.h_blob2[1], (size_t)(st->cap_blob + st->esc_extra)) != hipSuccess || hipHostMalloc((void **)&s.h_counts, 64) != hipSuccess ||
+            hipHostMalloc((void **)&s.h_blob2[1], (size_t)(st->cap_blob + st->esc_extra)) != hipSuccess || hipHostMalloc((void **)&s.h_counts, 128) != hipSuccess ||
             hipEventCreateWithFlags(&s.ev_tail, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&s.ev_copy, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&s.ev_rows, hipEventDisableTiming) != hipSuccess ||
@@ -261,7 +266,8 @@ int urhgpu_stream_create(urhgpu_ctx *ctx, int64_t n_max, const urhgpu_params *p,
         s.out.counts = (int64_t *)d; d += 256;
         s.out.blob = d; s.out.cap_blob = st->cap_blob; d += b_blob;
         s.stage = d;
-        memset(s.h_counts, 0, 64);
+        memset(s.h_counts, 0, 128);
+        s.h_costas = (int32_t *)(s.h_counts + 8);
     }
     *out = st;
     return URHGPU_OK;
@@ -397,8 +403,11 @@ static int stream_push(urhgpu_stream *st, const void *h_iq, const void *d_iq, in
         const size_t bps = st->p.dtype == URHGPU_DT_F32 ? 8 : (st->p.dtype == URHGPU_DT_I16 || st->p.dtype == URHGPU_DT_U16) ? 4 : 2;
         URH_HIP(hipMemcpyAsync(const_cast<void *>(d_iq), h_iq, (size_t)n * bps, hipMemcpyHostToDevice, ctx->stream));
     }
-    URH_TRY(urhgpu_iq_to_bits_dev(ctx, d_iq, n, &st->p, &pass_out));
-    URH_HIP(hipEventRecord(s.ev_tail, ctx->tail_stream));
+    ctx->costas_stats_next = s.h_costas;                   // (PSK: this pass's Costas stats, beside the slot's counts)
+    const int ordinary_status = urhgpu_iq_to_bits_dev(ctx, d_iq, n, &st->p, &pass_out);
+    ctx->costas_stats_next = nullptr;
+    URH_TRY(ordinary_status);
+    URH_HIP(hipEventRecord(s.ev_tail, ctx->last_tail));    // the stream the pass's last kernel went to: the tail stream for pipelined passes
     s.state = 1; s.seq = i; s.n = n;
     st->seq = i + 1;
     URH_TRY(queue_copy(st, s));                            // pack + copy behind this pass's tail, on the copy stream; the host does not wait
@@ -416,6 +425,12 @@ int urhgpu_stream_stats(urhgpu_stream *st, int64_t *out4) {
     out4[0] = st->seq; out4[1] = st->short_copies; out4[2] = st->predicted_bytes; out4[3] = st->cap_blob;
     // passes whose compact sections were written by the tail's own kernels (segments, direct, staged): their count, negated
     if (st->streamed_passes + st->staged_passes > 0) out4[2] = -(st->streamed_passes + st->staged_passes);
+    return URHGPU_OK;
+}
+
+int urhgpu_stream_costas_stats(urhgpu_stream *st, int64_t *out5) {
+    if (!st || !out5) return URHGPU_ERR_ARG;
+    for (int k = 0; k < 5; ++k) out5[k] = st->costas_sum[k];
     return URHGPU_OK;
 }
 

@@ -539,8 +539,10 @@ class CaptureStream:
         _lib.check(_lib.load().urhgpu_stream_stats(self._h, out))
         wide = C.c_int64(0)
         _lib.check(_lib.load().urhgpu_stream_wide_passes(self._h, C.byref(wide)))
+        costas = (C.c_int64 * 5)()
+        _lib.check(_lib.load().urhgpu_stream_costas_stats(self._h, costas))
         return {"pushed": int(out[0]), "short_copies": int(out[1]), "predicted_bytes": int(out[2]), "blob_capacity": int(out[3]),
-                "wide_passes": int(wide.value)}
+                "wide_passes": int(wide.value), "costas": tuple(int(v) for v in costas)}
 
     def close(self):
         if self._h:

@@ -109,8 +109,8 @@ class Signal:
         as they land (urhgpu_stream_push_upload); when the call returns the Signal holds the capture, its demodulated signal and the
         digitisation for the given parameters (`bits()` / `get_protocol()` cost nothing more).  params: the Signal's parameters
         (modulation_type, samples_per_symbol, center, tolerance, noise_threshold, ...) plus the constructor's keywords.
-        Float32 / signed captures of ASK-less, PSK-less modulations take this route; everything else (unsigned sample types, which the
-        reference converts first; ASK; PSK) falls back to from_file + the ordinary lazy passes -- same results either way.
+        Float32 / signed FSK and PSK captures take this route; everything else (unsigned sample types, which the reference converts
+        first; ASK) falls back to from_file + the ordinary lazy passes -- same results either way.
         pinned: an optional dict that keeps the pinned read buffer AND the capture stream (three output slots, six pinned blobs: what a
         stream costs to build) between calls -- a file browser opening capture after capture with the same parameters; the stream is
         rebuilt when the parameters, the sample type or the size class change, `pinned["stream"].close()` releases it."""
@@ -129,7 +129,7 @@ class Signal:
         dt = np.dtype(next((t for ext, t in signed.items() if filename.endswith(ext)), np.float32))
         lo, hi = _limits(dt)
         gated = not (s.noise_threshold < (2 * max(lo ** 2, hi ** 2)) ** 0.5)      # quad_demod's zeros(2) case (:474-484)
-        if filename.endswith(unsigned) or s.modulation_type != "FSK" or gated:
+        if filename.endswith(unsigned) or s.modulation_type not in ("FSK", "PSK") or gated:
             from .iq_array import from_file
             s.iq = from_file(filename, device=s.pipe.device)
             return s
