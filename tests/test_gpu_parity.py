@@ -122,7 +122,7 @@ def test_afp_demod_streaming_kernel_and_remainder(sf, oracle, mod):
 
 
 def test_afp_demod_signed_zero_and_nonfinite(sf, oracle):
-    vals = np.array([0.0, -0.0, 1.0, -1.0, 1e-40, -1e-40, 1e-30, 3e38, -3e38, 0.5, -0.25], dtype=np.float32)
+    vals = np.array([0.0, -0.0, 1.0, -1.0, 1e-40, -1e-40, 1e-30, 3e38, -3e38, 0.5, -0.25, np.inf, -np.inf, np.nan], dtype=np.float32)
     rng = np.random.default_rng(5)
     iq = vals[rng.integers(0, len(vals), size=(100000, 2))]
     for mod in ("FSK", "ASK"):

@@ -457,6 +457,14 @@ def test_estimate_frequency_equals_numpy(pipe):
                 assert max(cand) >= mags[idx] * (1 - 2e-5), (case, log2len, start, got, want)
             if log2len >= 12:
                 assert got == want, (case, log2len, start, got, want)
+            if case == 1 and log2len == 14:                  # the bin itself, at a clearly negative frequency: |frequency| would let a mirrored spectrum pass
+                import ctypes as C
+                import torch
+                from urh_amd import _lib
+                win = torch.from_numpy(np.ascontiguousarray(iq[start:start + (1 << 14)])).cuda()
+                peak = C.c_int64(-1)
+                _lib.check(_lib.load().urhgpu_fft_peak_dev(pipe.ctx.handle, C.c_void_p(win.data_ptr()), 1 << 14, C.byref(peak)))
+                assert int(peak.value) == idx and idx > (1 << 13) and abs(idx / (1 << 14) - 1 - f0) < 1e-3, (int(peak.value), idx)
     assert sig.estimate_frequency(100, 100, 1e6) == 100e3 and sig.estimate_frequency(200, 100, 1e6) == 100e3
     noise = (rng.standard_normal((1 << 16, 2))).astype(np.float32)
     sig = Signal(noise, pipe=pipe)

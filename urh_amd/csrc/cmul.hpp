@@ -5,7 +5,7 @@
 namespace urh {
 
 // ---- complex64 product exactly as GCC emits it for std::complex<float> / float _Complex --------------------
-__device__ __noinline__ inline float2 mulsc3_recover(float a, float b, float c, float d, float2 r) {
+__device__ __forceinline__ float2 mulsc3_recover_inline(float a, float b, float c, float d, float2 r) {
     // libgcc __mulsc3 (C99 G.5.1): only reached when both parts are NaN
     const float ac = a * c, bd = b * d, ad = a * d, bc = b * c;
     bool recalc = false;
@@ -34,6 +34,7 @@ __device__ __noinline__ inline float2 mulsc3_recover(float a, float b, float c, 
     }
     return r;
 }
+__device__ __noinline__ inline float2 mulsc3_recover(float a, float b, float c, float d, float2 r) { return mulsc3_recover_inline(a, b, c, d, r); }
 __device__ __forceinline__ float2 cmul(float2 x, float2 h) {
     float2 r;
     r.x = x.x * h.x - x.y * h.y;

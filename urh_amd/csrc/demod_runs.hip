@@ -31,6 +31,7 @@
 
 #include <algorithm>
 
+#include "cmul.hpp"
 #include "common.hpp"
 #include "fdlibm_atan2f.h"
 #include "launchers.hpp"
@@ -162,6 +163,19 @@ __device__ __forceinline__ void conj_mul(float a, float b, float c, float d, flo
     float D = 0.0f + d;              // 0 + (0*0 + 1*d)
     re = A * C - B * D;
     im = A * D + B * C;
+}
+// ... with libgcc's recovery where both parts of the product come out NaN (__mulsc3, C99 G.5.1), as the reference's generated C++ has it:
+// the general forms (demod_one, fsk_row_general).  An infinite imaginary part makes A or C a NaN (0 * inf); the reference then recovers
+// infinite parts and its atan2f gives +-pi/4 or +-3pi/4, not NaN.  (The sites that settle exact zeros keep conj_mul: their products are
+// finite.)  Inlined: the hot kernel stays without a call.
+__device__ __forceinline__ void conj_mul_general(float a, float b, float c, float d, float &re, float &im) {
+    const float A = a - 0.0f * b, B = 0.0f - (0.0f + b), C = c + 0.0f * d, D = 0.0f + d;
+    re = A * C - B * D;
+    im = A * D + B * C;
+    if (__builtin_expect((re != re) & (im != im), 0)) {
+        const float2 r = mulsc3_recover_inline(A, B, C, D, make_float2(re, im));
+        re = r.x; im = r.y;
+    }
 }
 
 // Message segmentation (seg_mode) on integer captures: util.get_magnitudes computes I*I + Q*Q in C `int` (wrapping) and
@@ -398,7 +412,7 @@ __device__ __forceinline__ float demod_one(float pc, float pd, float c, float d,
     if (MOD == URHGPU_MOD_ASK) return __builtin_sqrtf(mag) / p.max_magnitude;   // (double)sqrtf/(double) == fp32 div
     if (MOD == URHGPU_MOD_FSK) {
         float re, im;
-        conj_mul(pc, pd, c, d, re, im);
+        conj_mul_general(pc, pd, c, d, re, im);
         return atan2f_dev(im, re);
     }
     return 0.0f;   // MOD_OTHER: np.zeros stays
@@ -604,7 +618,7 @@ __device__ __forceinline__ void fsk_row_general(const RowIn &r, float prev_c, fl
         const float a = s ? r.c0 : pc, b = s ? r.d0 : pd, c = s ? r.c1 : r.c0, d = s ? r.d1 : r.d0;
         float re, im, q = p.noise_val;
         if (!(c * c + d * d <= p.noise_sqrd)) {
-            conj_mul(a, b, c, d, re, im);
+            conj_mul_general(a, b, c, d, re, im);
             q = atan2f_dev(im, re);
         }
         if (s) out[1] = q; else out[0] = q;
