@@ -118,6 +118,9 @@ int urhgpu_ctx_set_pipelined(urhgpu_ctx *ctx, int enable, void *tail_stream);
  *                              capture streams and on pipelined contexts, with a number of rounds queued that follows from the capture's length.
  *                              0 .. 24: the device everywhere, with exactly that many re-speculation rounds queued behind the first; a chain still
  *                              open after them is finished serially.  The demodulated signal is the same bit for bit whatever the value.
+ *   "auto_center_max_bins"     1 .. 2^20, default 4096: bins the histogram pool of the automatic center holds for its one range
+ *                              (urhgpu_detect_center_dev, urhgpu_iq_to_bits_auto_center_dev; also the room a capture stream leaves for a tied
+ *                              histogram, so set it before urhgpu_stream_set_auto_center).  A histogram with more bins comes back as flag 2
  *   "shard_summary_generic"    1: the local pass of urhgpu_shard_runs_dev as the three generic resolve launches instead of the one-launch
  *                              summary kernel (A/B and test use: the summaries are byte-equal).  default 0
  * Unknown key: URHGPU_ERR_ARG. */
@@ -334,6 +337,47 @@ int urhgpu_ppseq_to_bits_dev(urhgpu_ctx *ctx, const int64_t *d_rows, const int64
 int urhgpu_iq_to_bits_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p,
                           const urhgpu_outputs *out);
 
+/* ---- automatic center inside a pass, decided on the device --------------------------------------------------------------------
+ * The reference's live mode detects the center again for every buffer it demodulates (ProtocolSniffer.py:246-249:
+ * detect_center(qad, max_size=150 * samples_per_symbol)); for ASK the center follows the received amplitude, so captures that differ
+ * cannot share one.  These entry points run AutoInterpretation.detect_center (AutoInterpretation.py:226-277) for the ONE range [0, n) of
+ * a demodulated signal as a chain of kernels that is queued and never waited for: noise removal (x > -4), the 5 % trim, max_size
+ * (max_size < 0: none; the trimmed range keeps its first max_size samples, :233-234; 0 leaves nothing: no center), min / max, float32 np.var,
+ * the np.arange edges, the histogram, the peak picking.  The chain's scratch is the context's own (not the pass arenas'), and every chain of
+ * a context runs on one stream in order: the tail stream of a pipelined context, the context's stream otherwise.
+ *   flag 1  center = detect_center's value
+ *   flag 0  detect_center returns None (nothing left after the trim, zero or NaN variance, fewer than two edges, no strict peak)
+ *   flag 2  the histogram has more bins than the pool holds (tuning key "auto_center_max_bins"): the caller decides (host path)
+ *   flag 3  the second and third most populated peaks hold the same count: the reference's result then follows np.argsort's order of
+ *           equal keys, which only numpy can tell -- the histogram is handed out (n_counts counts behind the header, when n_bins fits
+ *           hist_cap) and the caller settles it with numpy.  Not rare on noisy captures (5 - 13 % of synthetic FSK captures).
+ * A result block is a urhgpu_center_result followed by room for hist_cap uint32 counts (hist_cap may be 0). */
+typedef struct urhgpu_center_result {
+    double center;               /* flag 1: the center; else 0 */
+    int64_t flag;
+    int64_t n_bins;              /* bins of the histogram (0: there is none) */
+    double e0, delta;            /* its edges: e0 + i * delta, i = 0 .. n_bins (np.arange's fill) */
+    int64_t kept, trimmed;       /* samples > -4; samples histogrammed (after the trim and max_size) */
+    int64_t n_counts;            /* uint32 counts that follow this header: n_bins when flag == 3 and n_bins <= hist_cap, else 0 */
+} urhgpu_center_result;
+/* The chain alone on d_qad (device, float32[n]); d_result: device memory, sizeof(urhgpu_center_result) + 4 * hist_cap bytes, complete when
+ * the work queued so far on the context's stream is.  Asynchronous: no read-back, no wait. */
+int urhgpu_detect_center_dev(urhgpu_ctx *ctx, const float *d_qad, int64_t n, int64_t max_size, void *d_result, int64_t hist_cap);
+/* IQ -> bits with the center detected inside the pass: demodulate into out->qad (required: URHGPU_ERR_ARG without; k_afp_demod for ASK /
+ * FSK / OTHER, the Costas loop for PSK), run the chain on it, derive the slicing thresholds on the device -- urhgpu_get_center_thresholds'
+ * arithmetic on (float)center --, segment the demodulated signal with them, bits, pack.  On a pipelined context everything behind the
+ * demodulation runs on the tail stream.  The pass never waits for the device and reads nothing back (PSK on a context that is not
+ * pipelined keeps the host-driven Costas rounds unless "costas_dev_rounds" says otherwise).
+ * WITH FLAG 0, 2 OR 3 THE QUEUED SLICING USED p->center: the outputs are then those of urhgpu_iq_to_bits_dev with the configured center,
+ * and a caller that wants the reference's result for flag 2 / 3 settles the center on the host and slices out->qad again
+ * (urhgpu_grab_pulse_lens_dev + urhgpu_ppseq_to_bits_dev).
+ * d_result: as above.  h_result: optional pinned host mirror of the same block, written by a kernel of the pass and valid once the pass
+ * is over, as out->h_counts is. */
+int urhgpu_iq_to_bits_auto_center_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, int64_t max_size,
+                                      const urhgpu_outputs *out, void *d_result, void *h_result, int64_t hist_cap);
+/* bins the context's histogram pool holds ("auto_center_max_bins"): the hist_cap that never loses a tied histogram */
+int64_t urhgpu_center_hist_cap(urhgpu_ctx *ctx);
+
 /* ---- a stream of captures, results on the host -------------------------------------------------------------------------------
  * SURVEY.md §8(d)'s window for this path ends with the compact outputs ON THE HOST.  For capture after capture (the reference's live
  * mode is such a consumer: ProtocolSniffer.py:161-202) three things overlap: the hot kernel of pass i, the tail of pass i - 1 (second
@@ -385,6 +429,16 @@ int urhgpu_stream_push(urhgpu_stream *st, const void *d_iq, int64_t n, urhgpu_ho
  * untouched, until the pass's result has been handed out (a later push's `ready`, or urhgpu_stream_flush). */
 int urhgpu_stream_push_upload(urhgpu_stream *st, const void *h_iq, void *d_iq, int64_t n, urhgpu_host_result *ready);
 int urhgpu_stream_flush(urhgpu_stream *st, urhgpu_host_result *out3, int *n_out);
+/* Every pass of the stream detects its own center (urhgpu_iq_to_bits_auto_center_dev with this max_size; < 0: none).  Before the first push:
+ * the chain's scratch for n_max is reserved here.  The stream must have been created with want_qad.  Such passes take the ordinary route
+ * (tail behind the demodulation, pack + copy behind the tail), urhgpu_stream_push_upload one copy in front of the pass. */
+int urhgpu_stream_set_auto_center(urhgpu_stream *st, int enable, int64_t max_size);
+/* The center of a pass whose result has been handed out (by a push's `ready` or by urhgpu_stream_flush), valid as long as that result:
+ * center and flag as above; for flag 3 *hist = the n_bins counts of the histogram (pinned host memory; NULL otherwise, or when the
+ * histogram did not fit) with its edges e0 + i * delta.  With flag 0, 2 or 3 the result's rows and bits are those of the configured
+ * center: the caller settles flag 2 / 3 and slices d_qad again. */
+int urhgpu_stream_center(urhgpu_stream *st, int64_t seq, double *center, int64_t *flag, const uint32_t **hist, int64_t *n_bins, double *e0,
+                         double *delta);
 /* Diagnostics: out4 = {passes pushed, passes whose predicted copy size fell short (their rest was fetched when the result was handed
  * out), bytes the next copy is sized for, blob capacity}. */
 int urhgpu_stream_stats(urhgpu_stream *st, int64_t *out4);
@@ -755,6 +809,12 @@ int64_t urhgpu_test_wide_int_launches(void);
  * reserved for a capture of n samples, one past the device-driven loop's control block as the buffers are carved for loop order 2 / 4, the
  * block's size}.  Host arithmetic; works without a GPU. */
 int64_t urhgpu_test_costas_host_syncs(void);
+/* how often code reached from the automatic-center entry points (urhgpu_detect_center_dev, urhgpu_iq_to_bits_auto_center_dev,
+ * urhgpu_stream_set_auto_center, and through them the passes of such a stream) made the host wait for the device: counted in the library
+ * beside every wait below those entry points -- stream, event and device synchronisations (the bounded run-ahead of pipelined passes,
+ * host-driven Costas rounds), scratch that grows (hipFree waits for the device).  A pass whose scratch is in place does not move it.
+ * Handing a result out and settling flag 2 / 3 on the host are not the pass: their waits belong to the calls that make them. */
+int64_t urhgpu_test_center_host_syncs(void);
 int urhgpu_test_costas_scratch(int64_t n, int loop_order, int64_t *out3);
 
 /* Test hook: elementwise bit-faithful atan2f (the device port of glibc 2.35 atan2f), device pointers. */

@@ -52,6 +52,12 @@ class Outputs(C.Structure):
     ]
 
 
+class CenterResult(C.Structure):
+    """struct urhgpu_center_result (include/urhgpu.h); uint32 counts of a tied histogram follow it"""
+    _fields_ = [("center", C.c_double), ("flag", C.c_int64), ("n_bins", C.c_int64), ("e0", C.c_double), ("delta", C.c_double),
+                ("kept", C.c_int64), ("trimmed", C.c_int64), ("n_counts", C.c_int64)]
+
+
 class HostResult(C.Structure):
     """struct urhgpu_host_result (include/urhgpu.h); pointers are pinned host memory owned by the stream"""
     _fields_ = [
@@ -102,6 +108,13 @@ PROTOTYPES = {
     "urhgpu_grab_pulse_lens_dev": (_i, [_vp, _vp, _i64, C.POINTER(Params), _vp, _i64, _vp]),
     "urhgpu_ppseq_to_bits_dev": (_i, [_vp, _vp, _vp, _i64, C.POINTER(Params), C.POINTER(Outputs)]),
     "urhgpu_iq_to_bits_dev": (_i, [_vp, _vp, _i64, C.POINTER(Params), C.POINTER(Outputs)]),
+    "urhgpu_detect_center_dev": (_i, [_vp, _vp, _i64, _i64, _vp, _i64]),
+    "urhgpu_iq_to_bits_auto_center_dev": (_i, [_vp, _vp, _i64, C.POINTER(Params), _i64, C.POINTER(Outputs), _vp, _vp, _i64]),
+    "urhgpu_center_hist_cap": (_i64, [_vp]),
+    "urhgpu_stream_set_auto_center": (_i, [_vp, _i, _i64]),
+    "urhgpu_stream_center": (_i, [_vp, _i64, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(_vp), C.POINTER(_i64), C.POINTER(C.c_double),
+                                  C.POINTER(C.c_double)]),
+    "urhgpu_test_center_host_syncs": (_i64, []),
     "urhgpu_blob_capacity": (_i64, [_i64, _i64, _i64, _i64, _i]),
     "urhgpu_outputs_to_host": (_i, [_vp, C.POINTER(Outputs), _i, _vp, _i64, C.POINTER(_i64)]),
     "urhgpu_host_libm_check": (_i, [C.POINTER(_i64)]),

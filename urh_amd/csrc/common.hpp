@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <atomic>
 #include <vector>
 
 #include "../../include/urhgpu.h"
@@ -66,6 +67,14 @@ struct Arena {
     void release();
 };
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+// urhgpu_test_center_host_syncs: how often code reached from the automatic-center entry points (a CenterScope is open on this thread) made
+// the host wait for the device.  Every place below those entry points that can block the host -- a stream / event / device synchronisation, an
+// arena that grows (hipFree waits for the device) -- calls center_note_wait() beside its wait.
+extern std::atomic<long long> g_center_host_syncs;
+extern thread_local int g_center_scope;
+inline void center_note_wait() { if (g_center_scope > 0) ++g_center_host_syncs; }
+struct CenterScope { CenterScope() { ++g_center_scope; } ~CenterScope() { --g_center_scope; } };
 
 }  // namespace urh
 
@@ -148,6 +157,12 @@ struct urhgpu_ctx {
     urh::Arena chunk_work;
     double *h_chunk = nullptr;             // pinned: {sum, max, sum not exact}
     long long chunk_launches = 0;          // kernel launches issued by urhgpu_chunk_power_stats_dev (urhgpu_chunk_stats_launches)
+    // automatic center inside a pass (urhgpu_detect_center_dev, urhgpu_iq_to_bits_auto_center_dev; msg_estimators.hip "center chain"): the
+    // chain's scratch -- kept samples, tile tables, histogram pool, thresholds -- is its own, NOT the rotating pass arenas': every center
+    // chain of a context runs on one stream, in order (center_stream), so the one scratch serves passes that overlap further down
+    urh::Arena center_work;
+    int tune_center_max_bins = 4096;       // bins the pool holds for the single range (urhgpu_ctx_set_tuning "auto_center_max_bins")
+    hipEvent_t ev_center = nullptr;        // urhgpu_detect_center_dev on a pipelined context: hand-over between the caller's stream and the tail stream
 };
 constexpr size_t kSegBlockBytes = 4096;      // 16 progress counters on their own 128-byte lines, then the SegState
 

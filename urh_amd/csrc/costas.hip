@@ -788,6 +788,7 @@ static int launch_costas_spec(const CostasArgs &a, void *scratch, urhgpu_ctx *ct
         URH_HIP(hipMemcpyAsync(h + 6, b.resume, 8, hipMemcpyDeviceToHost, s));
         URH_HIP(hipStreamSynchronize(s));
         ++g_costas_host_syncs;
+        center_note_wait();
         const int64_t stop_at = h[3];
         if (stop_at >= nc) break;
         c_from = stop_at;
@@ -977,6 +978,7 @@ static int costas_shard_resolve_t(urhgpu_ctx *ctx, const CostasArgsSh &a, int64_
         URH_HIP(hipMemcpyAsync(h + 6, b.resume, 8, hipMemcpyDeviceToHost, s));
         URH_HIP(hipStreamSynchronize(s));
         ++g_costas_host_syncs;
+        center_note_wait();
         const int64_t stop_at = h[3];
         if (stop_at >= nc) break;
         c_from = stop_at;                                    // >= 1: the stitch stops in front of the chunk after the one it ran

@@ -8,10 +8,12 @@
 namespace urh {
 
 thread_local char g_hip_err[256] = "";
+std::atomic<long long> g_center_host_syncs{0};
+thread_local int g_center_scope = 0;
 
 int Arena::reserve(size_t bytes) {
     if (bytes <= cap) return URHGPU_OK;
-    if (base) { URH_HIP(hipFree(base)); base = nullptr; cap = 0; }
+    if (base) { center_note_wait(); URH_HIP(hipFree(base)); base = nullptr; cap = 0; }      // (hipFree waits for the device)
     const size_t want = (bytes + (size_t(1) << 20)) & ~((size_t(1) << 20) - 1);
     URH_HIP(hipMalloc(&base, want));
     cap = want;
@@ -23,6 +25,7 @@ void Arena::release() {
 }
 
 hipError_t wait_stream(const urhgpu_ctx *ctx, hipStream_t s) {
+    center_note_wait();
     if (ctx->tune_spin_wait) {
         const auto t0 = std::chrono::steady_clock::now();
         for (int it = 0;; ++it) {
@@ -119,6 +122,8 @@ int urhgpu_ctx_destroy(urhgpu_ctx *ctx) {
     ctx->aux.release();
     ctx->fir_work.release();
     ctx->chunk_work.release();
+    ctx->center_work.release();
+    if (ctx->ev_center) (void)hipEventDestroy(ctx->ev_center);
     if (ctx->h_chunk) (void)hipHostFree(ctx->h_chunk);
     if (ctx->ev_fir) (void)hipEventDestroy(ctx->ev_fir);
     ctx->arena_alt.release();
@@ -233,6 +238,8 @@ int urhgpu_ctx_set_pipelined(urhgpu_ctx *ctx, int enable, void *tail_stream) {
 //                            a context that is not pipelined (it synchronises the stream once per round), the device inside capture streams and on
 //                            pipelined contexts, with as many rounds queued as the capture's chunk count affords (costas_auto_rounds).  0 .. 24: the
 //                            device everywhere, with exactly that many re-speculation rounds queued; what they leave is walked serially by the stitch
+//   auto_center_max_bins     bins the histogram pool of the automatic center (urhgpu_detect_center_dev, urhgpu_iq_to_bits_auto_center_dev) holds
+//                            for its one range; a histogram with more comes back as flag 2.  default 4096 (what k_me_hist keeps in LDS)
 //   shard_summary_generic    1: the local pass of urhgpu_shard_runs_dev as the three generic resolve launches instead of k_shard_summary; default 0
 int urhgpu_ctx_set_tuning(urhgpu_ctx *ctx, const char *key, int value) {
     if (!ctx || !key) return URHGPU_ERR_ARG;
@@ -249,6 +256,7 @@ int urhgpu_ctx_set_tuning(urhgpu_ctx *ctx, const char *key, int value) {
     else if (!strcmp(key, "wide_int")) { ctx->tune_wide_int = value != 0; }
     else if (!strcmp(key, "costas_dev_rounds")) { if (value < -1 || value > 24) return URHGPU_ERR_ARG; ctx->tune_costas_dev_rounds = value; }
     else if (!strcmp(key, "upload_pieces")) { if (value < 2 || value > kMaxSegments) return URHGPU_ERR_ARG; ctx->tune_upload_pieces = value; }
+    else if (!strcmp(key, "auto_center_max_bins")) { if (value < 1 || value > (1 << 20)) return URHGPU_ERR_ARG; ctx->tune_center_max_bins = value; }
     else return URHGPU_ERR_ARG;
     return URHGPU_OK;
 }

@@ -393,9 +393,18 @@ __device__ __forceinline__ float atan2f_small(float r, float y, float x) {
     return __uint_as_float((__float_as_uint(base) & 0x7fffffffu) | (__float_as_uint(y) & 0x80000000u));
 }
 
-template <bool ORDER2>
+// DTHR (the qad-input instantiations): the thresholds may live in device memory (RunArgs::d_thr) -- plain loads of a uniform address
+template <bool ORDER2, bool DTHR = false>
 __device__ __forceinline__ uint32_t classify(float q, const RunArgs &p, bool check_noise = true) {
     if (check_noise && q == p.noise_val) return kStPause;
+    if (DTHR && p.d_thr) {
+        const float *t = p.d_thr;
+        if (ORDER2) return (q <= t[0]) ? 1u : 2u;
+        int st = p.order - 1;
+        for (int k = 0; k < p.order - 1; ++k)
+            if (q <= t[k]) { st = k; break; }
+        return (uint32_t)st + 1u;
+    }
     if (ORDER2) return (q <= p.thr[0]) ? 1u : 2u;
     int st = p.order - 1;
     for (int k = 0; k < p.order - 1; ++k)
@@ -882,8 +891,8 @@ __device__ __forceinline__ uint32_t chunk_prologue(const RunArgs &p, int64_t a0,
     uint32_t st = kStNone;
     if (SRC == SRC_QAD) {
         const float *q = (const float *)p.in;
-        if (a0 > 0) st = classify<ORDER2>(q[a0 - 1], p);
-        else if (!global_start) st = classify<ORDER2>(((const float *)p.left_halo)[0], p);
+        if (a0 > 0) st = classify<ORDER2, SRC == SRC_QAD>(q[a0 - 1], p);
+        else if (!global_start) st = classify<ORDER2, SRC == SRC_QAD>(((const float *)p.left_halo)[0], p);
     } else {
         // qad[a0-1] needs IQ[a0-1] and (FSK) IQ[a0-2]
         float pc = 0, pd = 0;
@@ -901,7 +910,7 @@ __device__ __forceinline__ uint32_t chunk_prologue(const RunArgs &p, int64_t a0,
         }
         if (have) {
             const float q = is_global0 ? p.noise_val : demod_one<MOD, DT>(pc, pd, prev_c, prev_d, p);
-            st = classify<ORDER2>(q, p);
+            st = classify<ORDER2, SRC == SRC_QAD>(q, p);
         }
     }
     return st;
@@ -916,12 +925,12 @@ __device__ __forceinline__ uint32_t chunk_init_state(const RunArgs &p, int64_t c
         bool first_is_noise;
         if (SRC == SRC_QAD) first_is_noise = (((const float *)p.in)[0] == p.noise_val);
         else first_is_noise = true;                            // afp_demod: result[0] = NOISE
-        init = first_is_noise ? kStPause : classify<ORDER2>(0.0f, p, false);   // literal 0.0: thresholds only
-        if (SRC == SRC_QAD && p.seg_mode) init = classify<ORDER2>(((const float *)p.in)[0], p);   // segmentation: the state of sample 0 itself
+        init = first_is_noise ? kStPause : classify<ORDER2, SRC == SRC_QAD>(0.0f, p, false);   // literal 0.0: thresholds only
+        if (SRC == SRC_QAD && p.seg_mode) init = classify<ORDER2, SRC == SRC_QAD>(((const float *)p.in)[0], p);   // segmentation: the state of sample 0 itself
         if (SRC == SRC_IQ && p.seg_mode) {
             float c = 0.f, d = 0.f;
             Iq<DT>::load1(p.in, 0, c, d);
-            init = classify<ORDER2>(demod_one<MOD, DT>(0.f, 0.f, c, d, p), p);
+            init = classify<ORDER2, SRC == SRC_QAD>(demod_one<MOD, DT>(0.f, 0.f, c, d, p), p);
         }
     }
     return init;
@@ -1042,9 +1051,9 @@ __global__ __launch_bounds__(kBlock, URH_MINWAVES) void k_demod_runs(const RunAr
                     }
                     uint32_t st0, st1;
                     if (((gated >> j) & 1u) || (j == 0 && rb == 0 && ta == 0 && global_start)) {
-                        st0 = classify<ORDER2>(q0[j], p); st1 = classify<ORDER2>(q1[j], p);
+                        st0 = classify<ORDER2, SRC == SRC_QAD>(q0[j], p); st1 = classify<ORDER2, SRC == SRC_QAD>(q1[j], p);
                     } else {                                            // nothing gated: thresholds only
-                        st0 = classify<ORDER2>(q0[j], p, false); st1 = classify<ORDER2>(q1[j], p, false);
+                        st0 = classify<ORDER2, SRC == SRC_QAD>(q0[j], p, false); st1 = classify<ORDER2, SRC == SRC_QAD>(q1[j], p, false);
                     }
                     *(uint16_t *)(s_state + 16 + off) = (uint16_t)(st0 | (st1 << 8));   // bytes beyond tv are masked in phase 2
                 }
@@ -1329,6 +1338,13 @@ void k_demod_runs_bp(const RunArgs p) {
 
     // ================= phase 1: demodulate, one compare mask per plane and parity, parked in lane `row` ==============
     uint32_t spec_hint = 0;                                    // demod_batch: batches left that skip the speculative pass
+    // qad input: the thresholds of a pass that slices with the center it has just detected come from device memory (RunArgs::d_thr)
+    float dthr[3] = {0.f, 0.f, 0.f};
+    const bool use_dthr = SRC == SRC_QAD && p.d_thr != nullptr;
+    if (SRC == SRC_QAD && use_dthr) {
+#pragma unroll
+        for (int k = 0; k < (NPL == 1 ? 1 : 3); ++k) dthr[k] = p.d_thr[k];
+    }
     uint32_t pl[NPL + 1][2][2] = {};                          // [state planes ..., PAUSE][even, odd samples][low, high word]: lane r <- row r
     // what follows the demodulation of a batch: qad stores (wavefront-uniform row base + the lane's 32-bit offset: no VALU address
     // arithmetic), the compare masks, their parking
@@ -1362,14 +1378,17 @@ void k_demod_runs_bp(const RunArgs p) {
             if (!RUNS) continue;
             uint64_t X[NPL][2];                                // [plane][parity]
             if (NPL == 1) {
-                X[0][0] = __builtin_amdgcn_ballot_w64(q0[j] <= p.thr[0]); X[0][1] = __builtin_amdgcn_ballot_w64(q1[j] <= p.thr[0]);
+                const float t0 = (SRC == SRC_QAD && use_dthr) ? dthr[0] : p.thr[0];
+                X[0][0] = __builtin_amdgcn_ballot_w64(q0[j] <= t0); X[0][1] = __builtin_amdgcn_ballot_w64(q1[j] <= t0);
             } else {
                 // order 4: state - 1 = the first k with q <= thr[k], else 3 (signal_functions.pyx:438-442), as two bits
                 const float qq[2] = {q0[j], q1[j]};
 #pragma unroll
                 for (int par = 0; par < 2; ++par) {
-                    const uint64_t m0 = __builtin_amdgcn_ballot_w64(qq[par] <= p.thr[0]), m1 = __builtin_amdgcn_ballot_w64(qq[par] <= p.thr[1]),
-                                   m2 = __builtin_amdgcn_ballot_w64(qq[par] <= p.thr[2]);
+                    const float t0 = (SRC == SRC_QAD && use_dthr) ? dthr[0] : p.thr[0], t1 = (SRC == SRC_QAD && use_dthr) ? dthr[1] : p.thr[1],
+                                t2 = (SRC == SRC_QAD && use_dthr) ? dthr[2] : p.thr[2];
+                    const uint64_t m0 = __builtin_amdgcn_ballot_w64(qq[par] <= t0), m1 = __builtin_amdgcn_ballot_w64(qq[par] <= t1),
+                                   m2 = __builtin_amdgcn_ballot_w64(qq[par] <= t2);
                     X[NPL - 1][par] = ~m0 & ~m1;               // bit 1
                     X[0][par] = ~m0 & (m1 | ~m2);              // bit 0
                 }

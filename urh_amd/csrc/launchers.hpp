@@ -53,6 +53,9 @@ struct RunArgs {
     int wide_int;            // integer FSK captures: take the bit-plane kernel's instantiation with the wide loop (capture streams set it from k_wide_probe's count)
     int stamp_probe;         // tools/boundary_probe.py: the STAMPS instantiation of the bit-plane kernel (complex64 2-FSK only); 0 in the product
     float thr[kMaxOrder - 1];
+    // qad-input launches only (launch_runs_qad): not nullptr -- the kernels load their order - 1 thresholds from THIS device array instead of thr[]
+    // (a pass that slices with the center it has just detected: k_ac_publish writes them on the same stream, msg_estimators.hip)
+    const float *d_thr;
 };
 extern bool g_force_state_bytes;   // test hook: order 2 through the state-byte kernel too
 extern std::atomic<long long> g_wide_int_launches;

@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "launchers.hpp"
+#include "pass.hpp"
 
 namespace urh {
 
@@ -51,7 +52,10 @@ struct MsgState {            // one per message, device resident between the sta
     int64_t skip;            // 1: the message's first sample is filtered (x <= -4: afp_demod's result[0] = NOISE of FSK / PSK) -- k_me_first
     int64_t pairs_base;      // urhgpu_msg_plateau_decisions: first (value, count) pair of the message's plateau lengths in the pool ...
     int64_t pairs_n;         // ... and how many; -1: more distinct lengths than the table holds / the pool is full (the sequence decides)
+    int64_t cut;             // detect_center's max_size (AutoInterpretation.py:233-234): 0 none, else max_size + 1 -- the trimmed range keeps its first max_size samples
 };
+// the trimmed range's length after the cut (every place that derives L from the kept count goes through here)
+__host__ __device__ inline int64_t me_cut(const MsgState &m, int64_t L) { return (m.cut > 0 && L > m.cut - 1) ? m.cut - 1 : L; }
 // nothing filtered but (possibly) the first sample: the kept samples ARE x[start + skip : end], no compaction needed
 __host__ __device__ inline bool me_clean(const MsgState &m) { return m.kept == (m.end - m.start) - m.skip; }
 
@@ -112,7 +116,7 @@ __global__ __launch_bounds__(kMeBlock) void k_me_first(const float *x, MsgState 
     if (t.idx == 0 && threadIdx.x == 0) st[t.msg].skip = skip;
     const int64_t len = m.end - m.start - skip;
     const int64_t a = (int64_t)(0.05 * (double)len), b = (int64_t)(0.95 * (double)len);       // k_me_trim's arithmetic with k = len
-    const int64_t L = b > a ? b - a : 0;
+    const int64_t L = me_cut(m, b > a ? b - a : 0);
     const int64_t full = m.end - m.start;
     const int64_t nt = ((full > 1 ? full : 1) + kMeTile - 1) / kMeTile;       // tiles of the message (build_batch)
     const float *src = x + m.start + skip;
@@ -268,7 +272,7 @@ __global__ __launch_bounds__(kMeScanBlock) void k_me_tile_scan(const int32_t *cn
         st[m].kept = k;
         const int64_t a = (int64_t)(0.05 * (double)k), b = (int64_t)(0.95 * (double)k);     // int(0.05 * len), int(0.95 * len) (:231)
         st[m].a = a;
-        st[m].L = b > a ? b - a : 0;
+        st[m].L = me_cut(st[m], b > a ? b - a : 0);
         if (k != len - st[m].skip) *any_dirty = 1u;
     }
 }
@@ -1216,6 +1220,110 @@ __global__ void k_me_chain_center(const MsgState *st1, MsgState *st2, int n_msgs
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= n_msgs) return;
     st2[m].center = (st1[m].peak_flag == 1) ? (double)(float)st1[m].peak_center : __builtin_nan("");
+}
+
+
+// ---- the center chain: detect_center of ONE range, asynchronously, for a pass that uses the center it has just found --------------------
+// The launches of center_stats_batch for the range [0, n) of a demodulated signal, with the state built on the device (k_ac_init), no
+// read-back and no wait: what the pass needs of the result stays on the device (k_ac_publish: the slicing thresholds), what the host
+// needs of it lands in a result block the caller names (device and, optionally, pinned host memory).
+__global__ void k_ac_init(MsgState *st, int64_t n, int64_t cut) {
+    MsgState z;
+    memset(&z, 0, sizeof(z));
+    z.start = 0; z.end = n; z.first_tile = 0; z.window = n; z.center = __builtin_nan(""); z.cut = cut;
+    *st = z;
+}
+// One wavefront behind k_me_peaks: the thresholds of the pass's slicing -- urhgpu_get_center_thresholds' arithmetic (int -> float
+// conversion, fp32 multiply and add / sub; the library is built without contraction) on (float)peak_center when the device has decided
+// (flag 1), on the pass's configured center otherwise --, and the result block (include/urhgpu.h: urhgpu_center_result, then the counts of
+// a histogram whose second and third peak tie -- the host settles those with numpy -- when the caller has left room for them).
+__global__ __launch_bounds__(64) void k_ac_publish(const MsgState *st, const unsigned int *hist, int64_t hist_cap, float cfg_center, float spacing, int order,
+                                                    float *thr, char *d_res, char *h_res) {
+    const MsgState s = st[0];
+    const int lane = threadIdx.x;
+    const bool decided = s.peak_flag == 1;
+    if (thr) {
+        const float c = decided ? (float)s.peak_center : cfg_center;
+        const int half = order / 2;
+        for (int i = lane; i < order - 1; i += 64) thr[i] = (i < half) ? c - (float)(half - (i + 1)) * spacing : c + (float)(i + 1 - half) * spacing;
+    }
+    const int64_t nb = s.n_edges >= 2 ? s.n_edges - 1 : 0;
+    const bool ship = s.peak_flag == 3 && nb <= hist_cap;
+    urhgpu_center_result r;
+    r.center = decided ? s.peak_center : 0.0; r.flag = s.peak_flag; r.n_bins = nb; r.e0 = s.e0; r.delta = s.delta;
+    r.kept = s.kept; r.trimmed = s.L; r.n_counts = ship ? nb : 0;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        char *dst = k ? h_res : d_res;
+        if (!dst) continue;
+        if (lane == 0) *(urhgpu_center_result *)dst = r;
+        if (ship) for (int64_t i = lane; i < nb; i += 64) ((unsigned int *)(dst + sizeof(urhgpu_center_result)))[i] = hist[i];
+    }
+}
+
+static size_t center_pool_bytes(int64_t max_bins) { return ((size_t)max_bins * 4 + 256 + 255) & ~size_t(255); }
+static int64_t center_tiles(int64_t n) { return (std::max<int64_t>(n, 1) + kMeTile - 1) / kMeTile; }
+size_t center_chain_bytes(int64_t n, int64_t max_bins) {
+    const size_t nt = (size_t)center_tiles(n);
+    return sizeof(MsgState) + (nt + 1) * (sizeof(MsgTile) + 4 + 8 + 8 + 4 + kLeavesPerTile * 4) + (size_t)std::max<int64_t>(n, 1) * 4 + center_pool_bytes(max_bins) +
+           (size_t)(kMaxOrder - 1) * 4 + 16 * 256;
+}
+int reserve_center_chain(urhgpu_ctx *ctx, int64_t n_max) { return ctx->center_work.reserve(center_chain_bytes(n_max, ctx->tune_center_max_bins)); }
+
+// queue the chain on stream s (the context's center stream); nothing here waits for the device
+int center_chain_async(urhgpu_ctx *ctx, const float *d_x, int64_t n, int64_t max_size, hipStream_t s, CenterChain *out) {
+    const int64_t max_bins = ctx->tune_center_max_bins, n_tiles = center_tiles(n);
+    if (n_tiles > INT32_MAX) return URHGPU_ERR_UNSUPPORTED;
+    URH_TRY(reserve_center_chain(ctx, n));                   // (a capture longer than any before lets the arena grow: hipFree waits for the device first)
+    Arena &w = ctx->center_work;
+    w.reset();
+    MsgState *d_st = (MsgState *)w.take(sizeof(MsgState));
+    MsgTile *d_tiles = (MsgTile *)w.take((size_t)n_tiles * sizeof(MsgTile));
+    int64_t *d_pre = (int64_t *)w.take((size_t)(n_tiles + 1) * 8);
+    float2 *d_mm = (float2 *)w.take((size_t)n_tiles * 8);
+    float *d_half = (float *)w.take((size_t)(n_tiles + 1) * 4);
+    float *d_leaf = (float *)w.take((size_t)n_tiles * kLeavesPerTile * 4);
+    float *d_kept = (float *)w.take((size_t)std::max<int64_t>(n, 1) * 4);
+    int *d_wide = (int *)w.take(4);
+    float *d_thr = (float *)w.take((size_t)(kMaxOrder - 1) * 4);
+    const size_t pool_bytes = center_pool_bytes(max_bins);
+    unsigned int *d_hist = (unsigned int *)w.take(pool_bytes + (size_t)n_tiles * 4);
+    if (!d_st || !d_tiles || !d_pre || !d_mm || !d_half || !d_leaf || !d_kept || !d_wide || !d_thr || !d_hist) return URHGPU_ERR_ARG;
+    unsigned int *d_any_wide = d_hist + (size_t)max_bins, *d_any_dirty = d_any_wide + 1;
+    int32_t *d_cnt = (int32_t *)((char *)d_hist + pool_bytes);
+    out->d_st = d_st; out->d_hist = d_hist; out->d_thr = d_thr;
+    hipLaunchKernelGGL(k_ac_init, dim3(1), dim3(1), 0, s, d_st, std::max<int64_t>(n, 0), max_size < 0 ? (int64_t)0 : max_size + 1);
+    if (n > 0) {
+        hipLaunchKernelGGL(k_me_fill_tiles, dim3((unsigned)((n_tiles + 255) / 256)), dim3(256), 0, s, d_st, 1, d_tiles, n_tiles);
+        URH_HIP(hipMemsetAsync(d_hist, 0, pool_bytes + (size_t)n_tiles * 4, s));
+        const unsigned gt = (unsigned)n_tiles;
+        hipLaunchKernelGGL(k_me_first, dim3(gt), dim3(kMeBlock), 0, s, d_x, d_st, d_tiles, d_cnt, d_mm, d_half);
+        hipLaunchKernelGGL(k_me_tile_scan, dim3(1), dim3(kMeScanBlock), 0, s, d_cnt, n_tiles, d_pre, d_st, 1, d_any_dirty);
+        hipLaunchKernelGGL(k_me_compact, dim3((unsigned)((n_tiles + kMeCompactGroup - 1) / kMeCompactGroup)), dim3(kMeBlock), 0, s, d_x, d_st, d_tiles, n_tiles, d_pre,
+                           d_kept, d_leaf, d_mm, d_any_dirty);
+        hipLaunchKernelGGL(k_me_dirty_trees, dim3((unsigned)((n_tiles + kMeBlock / 64 - 1) / (kMeBlock / 64))), dim3(kMeBlock), 0, s, d_kept, d_st, d_tiles, n_tiles,
+                           d_leaf, d_half, d_any_dirty);
+        hipLaunchKernelGGL(k_me_sum_fin, dim3(1), dim3(kMeSumBlock), 0, s, d_x, d_kept, d_st, d_half, d_mm, 0);
+        hipLaunchKernelGGL(k_me_leaves, dim3(gt), dim3(kMeBlock), 0, s, d_x, d_kept, d_st, d_tiles, d_half);
+        hipLaunchKernelGGL(k_me_sum_fin, dim3(1), dim3(kMeSumBlock), 0, s, d_x, d_kept, d_st, d_half, d_mm, 1);
+        hipLaunchKernelGGL(k_me_bins, dim3(1), dim3(64), 0, s, d_st, 1, max_bins, d_any_wide, d_wide);
+        hipLaunchKernelGGL((k_me_hist<kMeHistSmall>), dim3((unsigned)((n_tiles + kMeHistGroup - 1) / kMeHistGroup)), dim3(kMeBlock), 0, s, d_x, d_kept, d_st, d_tiles,
+                           n_tiles, max_bins, d_hist, d_any_wide, d_wide);
+        hipLaunchKernelGGL((k_me_hist<kMeHistLds>), dim3((unsigned)std::min<int64_t>((n_tiles + kMeHistGroup - 1) / kMeHistGroup, 1024)), dim3(kMeBlock), 0, s, d_x,
+                           d_kept, d_st, d_tiles, n_tiles, max_bins, d_hist, d_any_wide, d_wide);
+    }
+    hipLaunchKernelGGL(k_me_peaks, dim3(1), dim3(kMeBlock), 0, s, d_st, d_hist, max_bins);       // (n == 0: no edges, flag 0)
+    URH_HIP(hipGetLastError());
+    return URHGPU_OK;
+}
+
+// thresholds (p != nullptr: into c.d_thr, from the chain's center or p->center) and the result block, behind the chain on the same stream
+int center_publish(const CenterChain &c, const urhgpu_params *p, void *d_result, void *h_result, int64_t hist_cap, hipStream_t s) {
+    const int order = p ? 1 << p->bits_per_symbol : 0;
+    hipLaunchKernelGGL(k_ac_publish, dim3(1), dim3(64), 0, s, (const MsgState *)c.d_st, c.d_hist, hist_cap, p ? p->center : 0.f, p ? p->center_spacing : 0.f, order,
+                       p ? c.d_thr : (float *)nullptr, (char *)d_result, (char *)h_result);
+    URH_HIP(hipGetLastError());
+    return URHGPU_OK;
 }
 
 }  // namespace urh

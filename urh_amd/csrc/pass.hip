@@ -150,6 +150,12 @@ int tile_tail_mem(urhgpu_ctx *ctx, int64_t n_entries, bool expands_bits, TileTai
     tm->parity = expands_bits ? (ctx->tile_parity ^= 1) : ctx->tile_parity;   // only passes that expand bits consume a counter
     tm->d_row_base = nullptr;
     if (!tm->mem) return URHGPU_ERR_ARG;
+    URH_TRY(reserve_rdesc(ctx, n_entries));
+    tm->rdesc = ctx->d_rdesc; tm->epoch = ++ctx->scan_epoch;
+    return URHGPU_OK;
+}
+// look-back descriptors of the tile tail's resolve scan over a table of n_entries chunks: dedicated memory, zeroed when (re)allocated
+int reserve_rdesc(urhgpu_ctx *ctx, int64_t n_entries) {
     const size_t rd = tile_rdesc_bytes(n_entries);
     if (rd > ctx->rdesc_cap) {
         if (ctx->d_rdesc) { URH_HIP(hipFree(ctx->d_rdesc)); ctx->d_rdesc = nullptr; ctx->rdesc_cap = 0; }
@@ -159,11 +165,22 @@ int tile_tail_mem(urhgpu_ctx *ctx, int64_t n_entries, bool expands_bits, TileTai
         // (the memset is work of the NULL stream: it runs behind everything queued on the blocking streams -- a hot kernel that waits for
         // an upload --, and the tail's non-blocking streams do not wait for it: descriptors published by the pass's first kernels were
         // wiped by it.  Allocation time only: wait until it has happened.)
+        center_note_wait();
         URH_HIP(hipDeviceSynchronize());
         ctx->rdesc_cap = want;
     }
-    tm->rdesc = ctx->d_rdesc; tm->epoch = ++ctx->scan_epoch;
     return URHGPU_OK;
+}
+// every allocation an auto-center pass over up to n_max samples would otherwise make when it first needs it (each one waits for the device):
+// the center chain's scratch and the descriptor memory of the tail's scans.  Capture streams call it before their first push.
+int reserve_auto_center_pass(urhgpu_ctx *ctx, int64_t n_max, int tolerance, int64_t cap_rows) {
+    URH_TRY(reserve_center_chain(ctx, n_max));
+    const Plan pl = make_plan(ctx, n_max, tolerance);
+    // chunks of a shorter capture: at most one per tile up to the plan's target, see make_plan
+    const int64_t n_chunks = std::max<int64_t>(pl.n_chunks, (int64_t)ctx->prop.multiProcessorCount * 16 + 2);
+    URH_TRY(reserve_rdesc(ctx, n_chunks));
+    ScanState ss;
+    return scan_state(ctx, tile_desc_cap(std::max<int64_t>(cap_rows, 1), n_chunks), &ss);
 }
 
 // resolve / emit arguments over the chunk table of a single-GPU pass: every chunk local, no summaries, the table's last row written here
@@ -184,13 +201,14 @@ void table_args(urhgpu_ctx *ctx, const urhgpu_params *p, const Plan &pl, int64_t
 // scratch must come from ctx->arena (already reserved by the caller).
 int digitize(urhgpu_ctx *ctx, bool from_iq, const void *d_in, int64_t n, const urhgpu_params *p, float *d_qad, int64_t *d_rows, int64_t cap_rows,
              int64_t *d_n_rows, int64_t *d_n_rows_needed, int64_t *d_n_acc, const Plan &pl, int seg_mode, hipStream_t s_tail, const BitsParams *tile_bp,
-             TileTailMem *tile_out) {
+             TileTailMem *tile_out, const float *d_thr) {
     hipStream_t s = ctx->stream;
     if (s_tail && from_iq) URH_TRY(hot_stream_begin(ctx, &s));
     if (tile_out) tile_out->mem = nullptr;
     RunArgs a;
     URH_TRY(hot_run_args(ctx, p, pl, n, 0, from_iq, &a));
     a.in = d_in; a.qad = d_qad;
+    if (d_thr) { if (from_iq) return URHGPU_ERR_ARG; a.d_thr = d_thr; }      // (thresholds in device memory: the qad-input kernels only)
     a.lds_pad = ctx->pipelined ? ctx->hot_lds_pad : 0;
     if (seg_mode) {
         // message segmentation: state = (|sample| > noise threshold) with the 10-sample outlier tolerance.  Reuses the
@@ -262,6 +280,7 @@ int scan_state(urhgpu_ctx *ctx, int64_t cap_rows, ScanState *out) {
         const size_t want = (need + (size_t(1) << 20)) & ~((size_t(1) << 20) - 1);
         URH_HIP(hipMalloc(&ctx->d_desc, want));
         URH_HIP(hipMemset(ctx->d_desc, 0, want));
+        center_note_wait();
         URH_HIP(hipDeviceSynchronize());                   // (see tile_tail_mem: the NULL stream's memset must not land behind the pass's kernels)
         ctx->desc_cap = want;
     }
@@ -284,6 +303,7 @@ int begin_pipelined_pass(urhgpu_ctx *ctx) {
     const hipError_t q = hipEventQuery(ctx->ev_tail[ctx->flip]);
     if (q == hipErrorNotReady) {
         (void)hipGetLastError();                   // "not ready" is an answer, not an error: keep it out of the sticky last-error slot
+        center_note_wait();
         URH_HIP(hipEventSynchronize(ctx->ev_tail[ctx->flip]));
     } else if (q != hipSuccess) {
         URH_HIP(q);
@@ -335,11 +355,8 @@ static int costas_demod(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhg
 }
 
 // ---- device-pointer entry points -------------------------------------------------------------------
-int urhgpu_afp_demod_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad) {
-    if (!ctx || !p || n < 0 || (n > 0 && (!d_iq || !d_qad))) return URHGPU_ERR_ARG;
-    if (dtype_bytes(p->dtype) == 0) return URHGPU_ERR_DTYPE;
-    URH_HIP(hipSetDevice(ctx->device));
-    URH_TRY(join_tail(ctx));
+// afp_demod on the context's stream as it is: no wait for an earlier pass's tail (the demodulation takes no scratch from the pass arenas)
+static int afp_demod_queue(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad) {
     if (n <= 2) {                                   // signal_functions.pyx:335-336
         if (n > 0) URH_HIP(hipMemsetAsync(d_qad, 0, (size_t)n * 4, ctx->stream));
         return URHGPU_OK;
@@ -357,6 +374,14 @@ int urhgpu_afp_demod_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urh
     URH_TRY(launch_afp_demod(a, p->dtype, p->mod, grid, ctx->stream));
     URH_HIP(hipGetLastError());
     return URHGPU_OK;
+}
+
+int urhgpu_afp_demod_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad) {
+    if (!ctx || !p || n < 0 || (n > 0 && (!d_iq || !d_qad))) return URHGPU_ERR_ARG;
+    if (dtype_bytes(p->dtype) == 0) return URHGPU_ERR_DTYPE;
+    URH_HIP(hipSetDevice(ctx->device));
+    URH_TRY(join_tail(ctx));
+    return afp_demod_queue(ctx, d_iq, n, p, d_qad);
 }
 
 int urhgpu_grab_pulse_lens_dev(urhgpu_ctx *ctx, const float *d_qad, int64_t n, const urhgpu_params *p,
@@ -479,6 +504,99 @@ int urhgpu_iq_to_bits_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const ur
     if (piped) URH_TRY(end_pipelined_pass(ctx));
     return st;
 }
+
+// ---- automatic center inside a pass ------------------------------------------------------------------------------------------
+// Every center chain of a context runs on ONE stream, in order -- the tail stream of a pipelined context, the caller's otherwise --, so the one
+// scratch (ctx->center_work) serves passes that overlap further down.
+static hipStream_t center_stream(urhgpu_ctx *ctx) { return (ctx->pipelined && ctx->tail_stream) ? ctx->tail_stream : ctx->stream; }
+
+int urhgpu_detect_center_dev(urhgpu_ctx *ctx, const float *d_qad, int64_t n, int64_t max_size, void *d_result, int64_t hist_cap) {
+    if (!ctx || n < 0 || (n > 0 && !d_qad) || !d_result || hist_cap < 0) return URHGPU_ERR_ARG;
+    CenterScope scope;                                       // (host waits below here are counted: urhgpu_test_center_host_syncs)
+    URH_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = center_stream(ctx);
+    if (s != ctx->stream) {                                  // the signal is the caller's stream's work: hand over, by events
+        if (!ctx->ev_center) URH_HIP(hipEventCreateWithFlags(&ctx->ev_center, hipEventDisableTiming));
+        URH_HIP(hipEventRecord(ctx->ev_center, ctx->stream));
+        URH_HIP(hipStreamWaitEvent(s, ctx->ev_center, 0));
+    }
+    CenterChain c;
+    URH_TRY(center_chain_async(ctx, d_qad, n, max_size, s, &c));
+    URH_TRY(center_publish(c, nullptr, d_result, nullptr, hist_cap, s));
+    if (s != ctx->stream) {                                  // ... and back: what the caller queues next sees the result
+        URH_HIP(hipEventRecord(ctx->ev_center, s));
+        URH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_center, 0));
+    }
+    return URHGPU_OK;
+}
+
+// The !fused shape of urhgpu_iq_to_bits_dev for every modulation: demodulate into out->qad, find the center of the demodulated signal, slice with
+// it.  Nothing here waits for the device or reads anything back; on a pipelined context everything behind the demodulation goes to the tail stream.
+int urhgpu_iq_to_bits_auto_center_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, int64_t max_size, const urhgpu_outputs *out,
+                                      void *d_result, void *h_result, int64_t hist_cap) {
+    if (!ctx) return URHGPU_ERR_ARG;
+    if (!p || !out || n <= 0 || !d_iq || !out->rows || !out->counts || !out->qad || !d_result || hist_cap < 0) return URHGPU_ERR_ARG;
+    const bool want_bits = out->bits && out->msg_off && out->pauses && out->pos_off;
+    if (!want_bits && out->blob) return URHGPU_ERR_ARG;      // the blob mirrors the bit outputs: all of them must be given
+    CenterScope scope;                                       // (host waits below here are counted: urhgpu_test_center_host_syncs)
+    if (dtype_bytes(p->dtype) == 0) return URHGPU_ERR_DTYPE;
+    URH_TRY(check_params(p, out->bits != nullptr));
+    if (p->bits_per_symbol < 1 || p->bits_per_symbol > 7) return URHGPU_ERR_UNSUPPORTED;
+    if (((uintptr_t)d_iq & 15) || ((uintptr_t)out->qad & 7)) return URHGPU_ERR_ARG;
+    URH_HIP(hipSetDevice(ctx->device));
+    const Plan pl = make_plan(ctx, n, p->tolerance);
+    const bool ask = (p->mod == URHGPU_MOD_ASK);
+    const bool piped = ctx->pipelined && ctx->tail_stream;
+    if (piped) URH_TRY(begin_pipelined_pass(ctx)); else URH_TRY(join_tail(ctx));
+    int64_t *d_n_rows = ctx->d_counts + 10;
+    BitsParams tile_bp = bits_params(p);
+    tile_bp.d_rows_needed = ctx->d_counts + 8;
+    TileTailMem tile;
+    tile.mem = nullptr;
+    hipStream_t caller = ctx->stream;
+    // from here on an error ends the pass like a success does: the arenas have rotated (begin_pipelined_pass), so ev_tail / flip must follow
+    auto rest = [&]() -> int {
+        URH_TRY(ctx->arena.reserve(digitize_scratch_bytes(pl, out->cap_rows, ask, true)));
+        ctx->arena.reset();
+        // the demodulation on the caller's stream (PSK: the Costas loop, its scratch from ctx->aux)
+        if (p->mod == URHGPU_MOD_PSK && n > 2) URH_TRY(costas_demod(ctx, d_iq, n, p, out->qad));
+        else URH_TRY(afp_demod_queue(ctx, d_iq, n, p, out->qad));
+        if (piped) {
+            URH_HIP(hipEventRecord(ctx->ev_hot, ctx->stream));
+            URH_HIP(hipStreamWaitEvent(ctx->tail_stream, ctx->ev_hot, 0));
+            ctx->stream = ctx->tail_stream;
+        }
+        CenterChain c;
+        URH_TRY(center_chain_async(ctx, out->qad, n, max_size, ctx->stream, &c));
+        URH_TRY(center_publish(c, p, d_result, h_result, hist_cap, ctx->stream));
+        URH_TRY(digitize(ctx, false, out->qad, n, p, nullptr, out->rows, out->cap_rows, d_n_rows, ctx->d_counts + 8, ctx->d_counts + 9, pl, 0, nullptr,
+                         want_bits ? &tile_bp : nullptr, want_bits ? &tile : nullptr, c.d_thr));
+        if (!want_bits) return URHGPU_OK;                    // pulse table only
+        const int64_t cap = std::max<int64_t>(out->cap_rows, 1);
+        void *scratch = ctx->arena.take(bits_scratch_bytes(cap));
+        if (!scratch) return URHGPU_ERR_ARG;
+        if (tile.mem) {
+            BitsOut bo{out->bits, out->cap_bits, out->msg_off, out->pauses, out->cap_msg, out->pos, out->cap_pos, out->pos_off, out->counts, out->h_counts};
+            ScanState ss;
+            URH_TRY(scan_state(ctx, tile_desc_cap(cap, pl.n_chunks), &ss));
+            URH_TRY(launch_tile_bits(tile, out->rows, d_n_rows, cap, tile_bp, bo, scratch, ss, ctx->stream));
+            URH_HIP(hipGetLastError());
+        } else {
+            URH_TRY(ppseq_to_bits_inner(ctx, out->rows, d_n_rows, cap, p, out, scratch, ctx->d_counts + 8));
+        }
+        if (out->blob) URH_TRY(launch_pack_blob(out, p->write_bit_sample_pos, ctx->stream));
+        return URHGPU_OK;
+    };
+    const int st = rest();
+    ctx->stream = caller;
+    ctx->last_tail = piped ? ctx->tail_stream : ctx->stream;
+    if (piped) URH_TRY(end_pipelined_pass(ctx));
+    return st;
+}
+
+int64_t urhgpu_center_hist_cap(urhgpu_ctx *ctx) { return ctx ? (int64_t)ctx->tune_center_max_bins : 0; }
+
+int64_t urhgpu_test_center_host_syncs(void) { return (int64_t)urh::g_center_host_syncs.load(); }
 
 // The results of a pass that is over (out: the descriptor the pass was given, with out->blob / cap_blob naming a device blob), on the
 // host: pack kernel, the header, then ONE copy of header.total_bytes -- what the boundary objects (Signal.bits(), BitsResult.ppseq() ...)

@@ -3,6 +3,7 @@
 #pragma once
 #include <math.h>
 
+#include <atomic>
 #include <algorithm>
 #include <new>
 #include <vector>
@@ -42,11 +43,20 @@ void table_args(urhgpu_ctx *ctx, const urhgpu_params *p, const Plan &pl, int64_t
                 int64_t cap_rows, int64_t *d_n_acc, int64_t *d_n_rows, int64_t *d_n_rows_needed, bool ask, ResolveArgs *r, EmitArgs *e);
 int tile_tail_mem(urhgpu_ctx *ctx, int64_t n_entries, bool expands_bits, TileTailMem *tm);
 int scan_state(urhgpu_ctx *ctx, int64_t cap_rows, ScanState *out);
+int reserve_rdesc(urhgpu_ctx *ctx, int64_t n_entries);
+int reserve_auto_center_pass(urhgpu_ctx *ctx, int64_t n_max, int tolerance, int64_t cap_rows);
 BitsParams bits_params(const urhgpu_params *p);
 int begin_pipelined_pass(urhgpu_ctx *ctx);
 int end_pipelined_pass(urhgpu_ctx *ctx);
 int digitize(urhgpu_ctx *ctx, bool from_iq, const void *d_in, int64_t n, const urhgpu_params *p, float *d_qad, int64_t *d_rows, int64_t cap_rows,
              int64_t *d_n_rows, int64_t *d_n_rows_needed, int64_t *d_n_acc, const Plan &pl, int seg_mode = 0, hipStream_t s_tail = nullptr,
-             const BitsParams *tile_bp = nullptr, TileTailMem *tile_out = nullptr);
+             const BitsParams *tile_bp = nullptr, TileTailMem *tile_out = nullptr, const float *d_thr = nullptr);
+
+// msg_estimators.hip: the center chain (detect_center of one range, queued, never waited for) behind the automatic center of a pass
+struct CenterChain { void *d_st; unsigned int *d_hist; float *d_thr; };
+size_t center_chain_bytes(int64_t n, int64_t max_bins);
+int reserve_center_chain(urhgpu_ctx *ctx, int64_t n_max);
+int center_chain_async(urhgpu_ctx *ctx, const float *d_x, int64_t n, int64_t max_size, hipStream_t s, CenterChain *out);
+int center_publish(const CenterChain &c, const urhgpu_params *p, void *d_result, void *h_result, int64_t hist_cap, hipStream_t s);
 
 }  // namespace urh

@@ -15,6 +15,7 @@
 #include "common.hpp"
 #include "compact.hpp"
 #include "launchers.hpp"
+#include "pass.hpp"
 
 using namespace urh;
 
@@ -38,7 +39,12 @@ struct urhgpu_stream {
         bool staged = false;               // the pass's blob arrived in the split layout: copied = head bytes, copied_rows / copied_pos = elements
         int64_t copied_rows = 0, copied_pos = 0;
         int state = 0;                     // 0 free, 1 pass launched (tail pending), 2 copy issued, 3 result handed out
+        // automatic center (urhgpu_stream_set_auto_center): the pass's result block (urhgpu_center_result + the counts of a tied histogram) on the
+        // device and in pinned host memory -- two host blocks used alternately, like h_blob2: the one handed out stays while the next pass's lands
+        char *d_center = nullptr, *h_center2[2] = {nullptr, nullptr};
     } slot[3];
+    int auto_center = 0;                   // every pass detects its own center (urhgpu_iq_to_bits_auto_center_dev) and takes the ordinary route
+    int64_t center_max_size = -1, center_hist_cap = 0;
     // The demodulated signal of pass i lives in qad_ring[i % 4]: four buffers for three result slots, so that the result handed out by
     // push i (pass i - 3) still owns its qad while pass i's hot kernel writes another one -- it is overwritten by push i + 1.
     float *qad_ring[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -289,6 +295,10 @@ int urhgpu_stream_destroy(urhgpu_stream *st) {
         if (s.ev_rows) (void)hipEventDestroy(s.ev_rows);
         if (s.ev_shipped) (void)hipEventDestroy(s.ev_shipped);
     }
+    for (auto &s : st->slot) {
+        if (s.d_center) (void)hipFree(s.d_center);
+        for (char *h : s.h_center2) if (h) (void)hipHostFree(h);
+    }
     for (auto &q : st->qad_ring) if (q) (void)hipFree(q);
     if (st->h_probe) (void)hipHostFree(st->h_probe);
     if (st->ev_probe) (void)hipEventDestroy(st->ev_probe);
@@ -298,6 +308,41 @@ int urhgpu_stream_destroy(urhgpu_stream *st) {
 }
 
 static int stream_push(urhgpu_stream *st, const void *h_iq, const void *d_iq, int64_t n, urhgpu_host_result *ready);
+
+int urhgpu_stream_set_auto_center(urhgpu_stream *st, int enable, int64_t max_size) {
+    if (!st || st->seq != 0) return URHGPU_ERR_ARG;          // before the first push: the scratch is reserved here, not under queued passes
+    if (!enable) { st->auto_center = 0; return URHGPU_OK; }
+    if (!st->want_qad) return URHGPU_ERR_ARG;                // the center is detected on the materialised demodulated signal
+    urhgpu_ctx *ctx = st->ctx;
+    URH_HIP(hipSetDevice(ctx->device));
+    urh::CenterScope scope;
+    URH_TRY(urh::reserve_auto_center_pass(ctx, st->n_max, st->p.tolerance, st->cap_rows));
+    st->center_hist_cap = ctx->tune_center_max_bins;
+    const size_t bytes = sizeof(urhgpu_center_result) + (size_t)st->center_hist_cap * 4;
+    for (auto &s : st->slot) {
+        if (s.d_center) continue;
+        URH_HIP(hipMalloc((void **)&s.d_center, bytes));
+        for (char *&h : s.h_center2) { URH_HIP(hipHostMalloc((void **)&h, bytes)); memset(h, 0, bytes); }
+    }
+    st->auto_center = 1; st->center_max_size = max_size < 0 ? -1 : max_size;
+    return URHGPU_OK;
+}
+
+int urhgpu_stream_center(urhgpu_stream *st, int64_t seq, double *center, int64_t *flag, const uint32_t **hist, int64_t *n_bins, double *e0, double *delta) {
+    if (!st || !st->auto_center || seq < 0 || seq >= st->seq) return URHGPU_ERR_ARG;
+    const urhgpu_stream::Slot &s = st->slot[seq % 3];
+    // the slot's latest pass, handed out -- or the one before it, whose result the latest push has just handed out
+    if (!((s.seq == seq && s.state == 3) || (s.seq == seq + 3))) return URHGPU_ERR_ARG;
+    const char *h = s.h_center2[(seq / 3) & 1];
+    const urhgpu_center_result *r = (const urhgpu_center_result *)h;
+    if (center) *center = r->center;
+    if (flag) *flag = r->flag;
+    if (n_bins) *n_bins = r->n_bins;
+    if (e0) *e0 = r->e0;
+    if (delta) *delta = r->delta;
+    if (hist) *hist = (r->flag == 3 && r->n_counts == r->n_bins && r->n_bins > 0) ? (const uint32_t *)(h + sizeof(urhgpu_center_result)) : nullptr;
+    return URHGPU_OK;
+}
 
 int urhgpu_stream_push(urhgpu_stream *st, const void *d_iq, int64_t n, urhgpu_host_result *ready) {
     return stream_push(st, nullptr, d_iq, n, ready);
@@ -342,6 +387,24 @@ static int stream_push(urhgpu_stream *st, const void *h_iq, const void *d_iq, in
     // sections as soon as the row kernel is through (while the bits are expanded), the head (+ positions) behind the pass's last kernel.
     bool streamed = false, staged = false;
     s.staged = false;
+    if (st->auto_center) {
+        // a pass that slices with the center it detects itself: the ordinary route (the segmented and staged tails start beside a hot kernel that
+        // there is none of), one copy in front of it for a capture that is still on the host
+        if (h_iq) {
+            const size_t bps = st->p.dtype == URHGPU_DT_F32 ? 8 : (st->p.dtype == URHGPU_DT_I16 || st->p.dtype == URHGPU_DT_U16) ? 4 : 2;
+            URH_HIP(hipMemcpyAsync(const_cast<void *>(d_iq), h_iq, (size_t)n * bps, hipMemcpyHostToDevice, ctx->stream));
+        }
+        ctx->costas_stats_next = s.h_costas;
+        const int status = urhgpu_iq_to_bits_auto_center_dev(ctx, d_iq, n, &st->p, st->center_max_size, &pass_out, s.d_center, s.h_center2[(i / 3) & 1],
+                                                             st->center_hist_cap);
+        ctx->costas_stats_next = nullptr;
+        URH_TRY(status);
+        URH_HIP(hipEventRecord(s.ev_tail, ctx->last_tail));
+        s.state = 1; s.seq = i; s.n = n;
+        st->seq = i + 1;
+        URH_TRY(queue_copy(st, s));
+        return URHGPU_OK;
+    }
     // 16-bit row lengths (3 bytes per row); a DENSE pulse table -- more than one row per 64 samples in the last result -- ships state and length
     // in one uint16 (2 bytes per row: what a step ships over PCIe bounds such captures)
 #ifdef URH_NO_ROW16

@@ -89,6 +89,41 @@ class BitsResult:
         self._ctx = ctx
         self._pipe, self._outputs = pipe, outputs          # the pipeline and the C descriptor of the pass: host() packs through them
         self._hostbits = None
+        self._auto = None                                    # auto_center passes, until settled: (pinned result block, max_size, slot), see _settle
+        self._center, self._center_flag = None, None
+
+    @property
+    def center(self):
+        """auto_center passes: the center the pass detected and sliced with (a Python float), None where detect_center gives None (the
+        bits are then those of the configured center); read with the counts"""
+        self._settle()
+        return self._center
+
+    @property
+    def center_flag(self):
+        """auto_center passes: urhgpu_center_result's flag as the device reported it (1 decided on the device, 0 None, 2 / 3 settled here)"""
+        self._settle()
+        return self._center_flag
+
+    def _settle(self):
+        """auto_center passes, before the first read: wait for the pass (the counts' read-back), look at the center's flag in the pinned
+        result block, and where the device left the decision to the host -- more bins than its pool holds (2), the second and third peak
+        tie (3: np.argsort's order of equal counts decides) -- settle the center with numpy and slice the demodulated signal again"""
+        if self._auto is None:
+            return
+        (block, max_size, slot), self._auto = self._auto, None
+        self._read_counts()
+        flag, center = settle_center(self._pipe, block.data_ptr(), self.qad, max_size)
+        self._center_flag = flag
+        self._center = center
+        if flag in (2, 3) and center is not None:
+            from dataclasses import replace
+            again = self._pipe.qad_to_bits(self.qad, replace(self.params, center=center), slot=slot)
+            again.check_capacity()
+            for name in ("rows_buf", "bits_buf", "msg_off_buf", "pauses_buf", "pos_buf", "pos_off_buf", "counts", "_host_counts", "_rows_needed", "_ctx",
+                         "_outputs"):
+                setattr(self, name, getattr(again, name))
+            self._hostbits = None
 
     def host(self, pool=None) -> "HostBits":
         """The results ON THE HOST through the compact blob (include/urhgpu.h): one more kernel packs them (5 B per pulse-table row, one bit
@@ -101,6 +136,7 @@ class BitsResult:
         n / (tolerance + 1) rows, hundreds of MB for a 1 GiB capture whose blob is a few MB."""
         if self._pipe is None or self._outputs is None:
             raise ValueError("this result was not made by a DevicePipeline pass")
+        self._settle()
         pipe, o = self._pipe, self._outputs
         keep = pipe._pinned if pool is None else pool
         if self._hostbits is not None and pool is None and keep.get("owner") is self._hostbits:
@@ -136,6 +172,10 @@ class BitsResult:
 
     def host_counts(self):
         """(n_rows, n_msg, n_bits, n_pos): one 32-byte D2H copy (synchronises)."""
+        self._settle()
+        return self._read_counts()
+
+    def _read_counts(self):
         if self._host_counts is None:
             if self._ctx is not None:
                 self._ctx.join()          # pipelined mode: the current stream waits for the tail of the pass
@@ -467,13 +507,40 @@ def positions_from_rows(row_state, row_len, p):
     return pos.astype(np.int64), np.asarray(off, dtype=np.int64)
 
 
+def settle_center(pipe, block_ptr: int, qad, max_size):
+    """(flag, center) of an auto_center pass from its result block in host memory (include/urhgpu.h: urhgpu_center_result, then the counts
+    of a tied histogram): the device's center for flag 1, None for flag 0; flag 3 -- peaks_center on the shipped histogram, with the
+    edges the device binned with --, flag 2 (or a tied histogram that was not shipped) -- the single-range estimator on the demodulated
+    signal `qad` (device tensor)."""
+    from . import estimators
+    r = _lib.CenterResult.from_address(block_ptr)
+    flag = int(r.flag)
+    if flag == 1:
+        return flag, float(r.center)
+    if flag == 0:
+        return flag, None
+    nb = int(r.n_bins)
+    if flag == 3 and int(r.n_counts) == nb and nb > 0:
+        counts = np.frombuffer((C.c_ubyte * (4 * nb)).from_address(block_ptr + C.sizeof(_lib.CenterResult)), dtype=np.uint32, count=nb).astype(np.int64)
+        edges = float(r.e0) + np.arange(nb + 1, dtype=np.float64) * float(r.delta)         # np.arange's fill: first + i * (second - first)
+        c = estimators.peaks_center(counts, edges)
+    else:
+        c = estimators.detect_center_dev(pipe, qad, max_size=max_size, _single=True)
+    return flag, (None if c is None else float(c))
+
+
 class CaptureStream:
     """Capture after capture with the results on the host (urhgpu_stream_*): push() queues a pass and returns at once with the result
     of the pass pushed three calls earlier (or None); flush() waits for the rest.  The hot kernel of pass i, the tail of pass i - 1
     and the D2H copy of pass i - 2's compact blob overlap."""
 
-    def __init__(self, pipe: "DevicePipeline", n_max: int, p: DemodParams, want_qad=True, want_pos=True, dtype=np.float32, cap_rows=0, latency=None):
-        """latency: True -- ONE capture at a time, its results as early as possible (a pass that finds the pipeline idle runs its tail in
+    def __init__(self, pipe: "DevicePipeline", n_max: int, p: DemodParams, want_qad=True, want_pos=True, dtype=np.float32, cap_rows=0, latency=None,
+                 auto_center=False, center_max_size=None):
+        """auto_center: every pass detects the center of its own demodulated signal (detect_center with max_size=center_max_size) and slices
+        with it, queued like any other pass; every HostBits handed out is final and carries .center (None: no center, the bits are those of
+        p.center) and .center_flag.  A pass whose center the device left to numpy (flag 2, 3: uncommon) is sliced again from its d_qad when
+        it is handed out -- that may wait for the passes queued behind it; results stay in push order.
+        latency: True -- ONE capture at a time, its results as early as possible (a pass that finds the pipeline idle runs its tail in
         segments beside the hot kernel); False -- capture after capture, highest throughput (staged passes: rows through a staging blob in HBM and the runtime's copy); None: leave the context's
         setting (urhgpu_ctx_set_tuning "stream_latency") as it is"""
         if latency is not None:
@@ -486,6 +553,12 @@ class CaptureStream:
                                                     1 if want_pos else 0, int(cap_rows), C.byref(h)))
         self._h = h
         self._dtype = np.dtype(dtype)
+        self._auto_center, self._center_max_size = bool(auto_center), center_max_size
+        if auto_center:
+            if not want_qad:
+                self.close()
+                raise ValueError("auto_center needs the demodulated signal (want_qad=True)")
+            _lib.check(_lib.load().urhgpu_stream_set_auto_center(h, 1, -1 if center_max_size is None else int(center_max_size)))
         # the captures of the passes that may still be running (three are in flight at most): a caller's temporary -- a pinned host buffer
         # under the DMA of push_upload in particular, which no allocator knows to be in use -- lives until its pass has been handed out
         self._inflight = []
@@ -504,7 +577,40 @@ class CaptureStream:
         self.pipe.ctx.set_stream(torch.cuda.current_stream(self.pipe.device).cuda_stream)
         _lib.check(_lib.load().urhgpu_stream_push(self._h, C.c_void_p(iq.data_ptr()), int(iq.shape[0]), C.byref(r)))
         self._hold(iq)
-        return HostBits(r, self.params) if r.seq >= 0 else None
+        return self._final(HostBits(r, self.params)) if r.seq >= 0 else None
+
+    def _final(self, h: "HostBits"):
+        """auto_center streams: the pass's center beside its result; flag 2 / 3 settled here (numpy on the shipped histogram, or the
+        single-range estimator on d_qad) and the demodulated signal sliced again with the settled center"""
+        if not self._auto_center:
+            return h
+        lib, pipe = _lib.load(), self.pipe
+        center, flag, hist, nb, e0, delta = C.c_double(0.0), C.c_int64(0), C.c_void_p(), C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+        _lib.check(lib.urhgpu_stream_center(self._h, h.seq, C.byref(center), C.byref(flag), C.byref(hist), C.byref(nb), C.byref(e0), C.byref(delta)))
+        h.center_flag = int(flag.value)
+        h.center = float(center.value) if h.center_flag == 1 else None
+        if h.center_flag not in (2, 3):
+            return h
+        from dataclasses import replace
+        from . import estimators
+        torch = pipe.torch
+        pipe.ctx.set_stream(torch.cuda.current_stream(pipe.device).cuda_stream)
+        qad = torch.empty(h.n_samples, dtype=torch.float32, device=pipe.device)
+        _lib.check(lib.urhgpu_memcpy_dtod(pipe.ctx.handle, C.c_void_p(qad.data_ptr()), C.c_void_p(h.d_qad_ptr), h.n_samples * 4))
+        if h.center_flag == 3 and hist.value:
+            counts = np.frombuffer((C.c_ubyte * (4 * nb.value)).from_address(hist.value), dtype=np.uint32, count=nb.value).astype(np.int64)
+            c = estimators.peaks_center(counts, e0.value + np.arange(nb.value + 1, dtype=np.float64) * delta.value)
+        else:
+            c = estimators.detect_center_dev(pipe, qad, max_size=self._center_max_size, _single=True)
+        if c is None:
+            return h
+        p = replace(self.params, center=float(c), write_bit_sample_pos=h.pos32 is not None)
+        again = pipe.qad_to_bits(qad, p, slot="stream")
+        again.check_capacity()
+        g = again.host(pool={})                               # (a pinned buffer of its own: the result lives as long as the caller keeps it)
+        g.seq, g.n_samples, g.d_qad_ptr, g.params = h.seq, h.n_samples, h.d_qad_ptr, self.params
+        g.center, g.center_flag = float(c), h.center_flag
+        return g
 
     def push_upload(self, host_iq, dev_iq):
         """A capture that is still on the host (urhgpu_stream_push_upload): host_iq -- a torch CPU tensor (pinned: PCIe speed) or a numpy
@@ -525,14 +631,14 @@ class CaptureStream:
         _lib.check(_lib.load().urhgpu_stream_push_upload(self._h, C.c_void_p(host_iq.data_ptr()), C.c_void_p(dev_iq.data_ptr()), int(host_iq.shape[0]),
                                                          C.byref(r)))
         self._hold(host_iq, dev_iq)
-        return HostBits(r, self.params) if r.seq >= 0 else None
+        return self._final(HostBits(r, self.params)) if r.seq >= 0 else None
 
     def flush(self):
         arr = (_lib.HostResult * 3)()
         n = C.c_int(0)
         _lib.check(_lib.load().urhgpu_stream_flush(self._h, arr, C.byref(n)))
         self._inflight = []                                   # (every pass has finished)
-        return [HostBits(arr[k], self.params) for k in range(n.value)]
+        return [self._final(HostBits(arr[k], self.params)) for k in range(n.value)]
 
     def stats(self) -> dict:
         out = (C.c_int64 * 4)()
@@ -573,6 +679,7 @@ class DevicePipeline:
         _lib.host_libm_verdict()                             # (once per process: a host libm the device code does not restate is reported)
         self._bufs = {}
         self._pinned = {}                                   # pinned host buffers of BitsResult.host()
+        self._auto_slots = set()                            # pipelined: slots of the auto_center passes queued since the last join (iq_to_bits)
         self.tail_stream = None
         for key, value in (tuning or {}).items():
             self.ctx.set_tuning(key, value)
@@ -616,14 +723,22 @@ class DevicePipeline:
     def reserve(self, n: int, p: DemodParams):
         self.ctx.reserve(n, p.tolerance)
 
-    def stream(self, n_max: int, p: DemodParams, want_qad=True, want_pos=True, dtype=np.float32, cap_rows=0, latency=None) -> CaptureStream:
+    def stream(self, n_max: int, p: DemodParams, want_qad=True, want_pos=True, dtype=np.float32, cap_rows=0, latency=None, auto_center=False,
+               center_max_size=None) -> CaptureStream:
         """a CaptureStream on this pipeline's context (which it switches to pipelined passes)"""
-        return CaptureStream(self, n_max, p, want_qad, want_pos, dtype, cap_rows, latency)
+        return CaptureStream(self, n_max, p, want_qad, want_pos, dtype, cap_rows, latency, auto_center, center_max_size)
 
-    def iq_to_bits(self, iq, p: DemodParams, want_qad=True, cap_rows=None, slot=0) -> BitsResult:
+    def iq_to_bits(self, iq, p: DemodParams, want_qad=True, cap_rows=None, slot=0, auto_center=False, center_max_size=None) -> BitsResult:
         """iq: torch tensor on this device, shape (N, 2) of int8/uint8/int16/uint16/float32, or complex64 (N,).
-        The result lives in buffers owned by the pipeline and is overwritten by the next pass with the same `slot`."""
+        The result lives in buffers owned by the pipeline and is overwritten by the next pass with the same `slot`.
+        auto_center: the pass detects the center of its own demodulated signal (AutoInterpretation.detect_center with
+        max_size=center_max_size, as ProtocolSniffer does per flush) and slices with it, all of it queued on the device
+        (urhgpu_iq_to_bits_auto_center_dev); BitsResult.center / .center_flag tell what it found.  Where the device leaves the decision
+        to numpy (flag 2, 3) the result is settled on the host before its first read; where there is no center (None) the bits are
+        those of p.center."""
         torch = self.torch
+        if auto_center and not want_qad:
+            raise ValueError("auto_center needs the demodulated signal (want_qad=True)")
         if iq.dtype == torch.complex64:
             iq = torch.view_as_real(iq)
         if iq.dim() != 2 or iq.shape[1] != 2 or not iq.is_contiguous():
@@ -651,6 +766,28 @@ class DevicePipeline:
         o.pos_off = pos_off.data_ptr()
         o.counts = counts.data_ptr()
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        if auto_center:
+            lib = _lib.load()
+            hist_cap = int(lib.urhgpu_center_hist_cap(self.ctx.handle))
+            nbytes = C.sizeof(_lib.CenterResult) + 4 * hist_cap
+            d_res = self._buf(sfx + "center", (nbytes,), torch.uint8)
+            block = self._pinned.get(("center", slot))
+            if block is None or block.numel() < nbytes:
+                block = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+                self._pinned[("center", slot)] = block
+            if self.tail_stream is not None:
+                # the slot's qad is read by its previous pass's tail (center chain, segmentation): a pass that REUSES a slot whose tail may still be
+                # pending makes its demodulation wait for the tail; passes on slots of their own overlap
+                if slot in self._auto_slots:
+                    self.ctx.join()
+                    self._auto_slots.clear()
+                self._auto_slots.add(slot)
+            _lib.check(lib.urhgpu_iq_to_bits_auto_center_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, C.byref(cp),
+                                                             -1 if center_max_size is None else int(center_max_size), C.byref(o),
+                                                             C.c_void_p(d_res.data_ptr()), C.c_void_p(block.data_ptr()), hist_cap))
+            res = BitsResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, self.ctx, pipe=self, outputs=o)
+            res._auto = (block, center_max_size, slot)
+            return res
         _lib.check(_lib.load().urhgpu_iq_to_bits_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, C.byref(cp), C.byref(o)))
         return BitsResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, self.ctx, pipe=self, outputs=o)
 

@@ -18,7 +18,7 @@ Two layers:
                        flush(index, params, automatic_center) -> (center, bits, pauses, bit_sample_pos)
                    GpuSniffEngine is the product: the buffer is device resident, a chunk costs one pass of
                    urhgpu_chunk_power_stats_dev (append + statistics in one read, two launches, one synchronisation), a flush is
-                   DevicePipeline.iq_to_bits on buffer[:index].  There is no CPU engine in this package.
+                   DevicePipeline.iq_to_bits on buffer[:index] (with automatic_center: auto_center=True, the center detected inside the pass).  There is no CPU engine in this package.
 """
 import time
 from dataclasses import dataclass, replace
@@ -125,7 +125,15 @@ class GpuSniffEngine:
         if not (params.noise_threshold < max_magnitude(self.dtype)):           # Signal.quad_demod (:474-484): two zeros instead of a demodulation
             qad = torch.zeros(2, dtype=torch.float32, device=pipe.device)
         elif automatic_center:
-            qad = pipe.afp_demod(iq, params)
+            # ProtocolSniffer.py:246-249: detect_center(qad, max_size=150 * samples_per_symbol) per flush -- ONE queued pass that demodulates,
+            # finds the center on the device and slices with it (the exact row bound: no second pass for a noisy buffer)
+            res = pipe.iq_to_bits(iq, params, want_qad=True, cap_rows=index // (int(params.tolerance) + 1) + 2, auto_center=True,
+                                  center_max_size=150 * sps)
+            center = res.center
+            if center is None:
+                raise ValueError("no center could be detected (the reference fails in grab_pulse_lens with center None)")
+            res.check_capacity()
+            return (center,) + tuple(res.messages())
         else:
             res = pipe.iq_to_bits_checked(iq, params, want_qad=False)
             return (center,) + tuple(res.messages())
