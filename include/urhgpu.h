@@ -863,6 +863,62 @@ int urhgpu_magnitude_chunk_partials_dev(urhgpu_ctx *ctx, const void *d_iq, int d
 int urhgpu_pairwise_partial_f32_dev(urhgpu_ctx *ctx, const float *d_x, int64_t m_local, int64_t g_off, int64_t m_total, int mode, float mean,
                                     float *d_out, int64_t cap, int64_t *n_out);
 
+/* ---- automatic noise threshold inside a pass, decided on the device -------------------------------------------------------------
+ * The reference opens a capture with default_noise_threshold = "automatic" (Signal.py:97-103): noise_threshold =
+ * AutoInterpretation.detect_noise_level(magnitudes), and demodulates with it.  These entry points run detect_noise_level
+ * (AutoInterpretation.py:60-91) as a chain that is queued and never waited for: the per-chunk (sum, max) of the magnitudes
+ * (urhgpu_magnitude_chunk_stats_dev's kernels; chunks of max(1, n / 100) samples counted from the END of the capture, at most 199 of
+ * them) and ONE workgroup that decides (k_noise_decide) in the reference's scalar types: float32 means of fp64 sums, minimum / maximum
+ * as doubles (util.minmax hands Python floats back), the float32 product 1.1f * min for the candidates, the fp64 maximum of the
+ * candidates' maxima, ceil(result * 10000) / 10000 in fp64.  The chain's scratch is a fixed part of the context from its creation: it
+ * never grows.  The kernels that gate by magnitude load noise_sqrd from the result block (a uniform load per workgroup).
+ *   flag 1  noise = detect_noise_level's value (this includes the 0 it returns for n <= 3, for means that lie close together and for an
+ *           all-zero capture)
+ *   flag 2  noise is the value, but it is not below Signal.max_magnitude of the sample type (urhgpu_noise_max_magnitude; a comparison of
+ *           doubles, Signal.py:404-406): the reference then does not demodulate at all (Signal.py:474-484: np.zeros(2))
+ *   flag 0  the reference raises: math.ceil of a NaN (ValueError) or of an infinity (OverflowError); noise holds that NaN / infinity
+ * WITH FLAG 0 OR 2 A QUEUED PASS GATED WITH p->noise_threshold: its outputs are those of the pass without auto_noise. */
+typedef struct urhgpu_noise_result {
+    double noise;                /* flag 1, 2: detect_noise_level's value; flag 0: the NaN / infinity math.ceil would have been given */
+    float noise_f32;             /* the threshold the pass gated with as afp_demod's `float noise_mag` argument: (float)noise for flag 1 (and for
+                                  * every flag of urhgpu_detect_noise_level_dev, which has no pass), p->noise_threshold for flag 0 / 2 */
+    float noise_sqrd;            /* noise_f32 * noise_f32, an fp32 multiply: what the kernels compare |sample|^2 with */
+    int64_t flag;
+    int64_t chunk, n_chunks;     /* the chunk geometry: samples per chunk, chunks (0 for n <= 3) */
+    int64_t n_candidates;        /* chunks with mean <= 1.1f * min */
+    double min_mean, max_mean;   /* of the float32 chunk means, as doubles */
+} urhgpu_noise_result;
+/* Signal.max_magnitude of a sample type (Signal.py:404-406): (2 * max(min^2, max^2)) ** 0.5 with IQArray.min_max_for_dtype's bounds
+ * (-1, 1 for float32).  Host arithmetic; 0 for an unknown dtype. */
+double urhgpu_noise_max_magnitude(int dtype);
+/* The chain alone on d_iq (device, n samples of dtype): d_result (device, sizeof(urhgpu_noise_result), 8-byte aligned) is complete when the
+ * work queued so far on the context's stream is.  Asynchronous: no read-back, no wait. */
+int urhgpu_detect_noise_level_dev(urhgpu_ctx *ctx, const void *d_iq, int dtype, int64_t n, void *d_result);
+/* IQ -> bits with the noise threshold (auto_noise) and / or the center (auto_center) detected inside the pass.
+ *   auto_noise alone   the chain, then the FUSED pass of urhgpu_iq_to_bits_dev with the hot kernel reading the threshold from
+ *                      d_noise_result, then the ordinary tail; out->qad is optional.  PSK: the Costas kernels read it.
+ *   with auto_center   the shape of urhgpu_iq_to_bits_auto_center_dev (out->qad required: URHGPU_ERR_ARG without), k_afp_demod or the
+ *                      Costas loop reading the device threshold; the center chain and the slicing are that entry point's.
+ *   auto_noise = 0     exactly urhgpu_iq_to_bits_auto_center_dev (auto_center != 0) or urhgpu_iq_to_bits_dev (both 0).
+ * d_noise_result (auto_noise: required, device, 8-byte aligned) / d_center_result + hist_cap (auto_center: as urhgpu_iq_to_bits_auto_center_dev).
+ * h_noise_result / h_center_result: optional pinned host mirrors, written by kernels of the pass and valid once the pass is over, as
+ * out->h_counts is.  The pass never waits for the device and reads nothing back (PSK on a context that is not pipelined keeps the
+ * host-driven Costas rounds unless "costas_dev_rounds" says otherwise). */
+int urhgpu_iq_to_bits_auto_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, int auto_noise, int auto_center,
+                               int64_t center_max_size, const urhgpu_outputs *out, void *d_noise_result, void *h_noise_result,
+                               void *d_center_result, void *h_center_result, int64_t hist_cap);
+/* Every pass of the stream detects its own noise threshold (urhgpu_iq_to_bits_auto_dev).  Before the first push (URHGPU_ERR_ARG after).
+ * Such passes take the ordinary route (tail behind the hot kernel, pack + copy behind the tail); urhgpu_stream_push_upload makes ONE copy
+ * in front of the pass: the chunks count from the END of the capture, so nothing can be gated before all of it has landed.  May be
+ * combined with urhgpu_stream_set_auto_center. */
+int urhgpu_stream_set_auto_noise(urhgpu_stream *st, int enable);
+/* The threshold of a pass whose result has been handed out (by a push's `ready` or by urhgpu_stream_flush), valid as long as that result. */
+int urhgpu_stream_noise(urhgpu_stream *st, int64_t seq, double *noise, int64_t *flag);
+/* how often code reached from the automatic-noise entry points (urhgpu_detect_noise_level_dev, urhgpu_iq_to_bits_auto_dev with auto_noise,
+ * and through it the passes of such a stream) made the host wait for the device: the counter of urhgpu_test_center_host_syncs, kept
+ * separately for these entry points. */
+int64_t urhgpu_test_noise_host_syncs(void);
+
 #ifdef __cplusplus
 }
 #endif

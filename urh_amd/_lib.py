@@ -58,6 +58,12 @@ class CenterResult(C.Structure):
                 ("kept", C.c_int64), ("trimmed", C.c_int64), ("n_counts", C.c_int64)]
 
 
+class NoiseResult(C.Structure):
+    """struct urhgpu_noise_result (include/urhgpu.h)"""
+    _fields_ = [("noise", C.c_double), ("noise_f32", C.c_float), ("noise_sqrd", C.c_float), ("flag", C.c_int64), ("chunk", C.c_int64),
+                ("n_chunks", C.c_int64), ("n_candidates", C.c_int64), ("min_mean", C.c_double), ("max_mean", C.c_double)]
+
+
 class HostResult(C.Structure):
     """struct urhgpu_host_result (include/urhgpu.h); pointers are pinned host memory owned by the stream"""
     _fields_ = [
@@ -115,6 +121,12 @@ PROTOTYPES = {
     "urhgpu_stream_center": (_i, [_vp, _i64, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(_vp), C.POINTER(_i64), C.POINTER(C.c_double),
                                   C.POINTER(C.c_double)]),
     "urhgpu_test_center_host_syncs": (_i64, []),
+    "urhgpu_noise_max_magnitude": (C.c_double, [_i]),
+    "urhgpu_detect_noise_level_dev": (_i, [_vp, _vp, _i, _i64, _vp]),
+    "urhgpu_iq_to_bits_auto_dev": (_i, [_vp, _vp, _i64, C.POINTER(Params), _i, _i, _i64, C.POINTER(Outputs), _vp, _vp, _vp, _vp, _i64]),
+    "urhgpu_stream_set_auto_noise": (_i, [_vp, _i]),
+    "urhgpu_stream_noise": (_i, [_vp, _i64, C.POINTER(C.c_double), C.POINTER(_i64)]),
+    "urhgpu_test_noise_host_syncs": (_i64, []),
     "urhgpu_blob_capacity": (_i64, [_i64, _i64, _i64, _i64, _i]),
     "urhgpu_outputs_to_host": (_i, [_vp, C.POINTER(Outputs), _i, _vp, _i64, C.POINTER(_i64)]),
     "urhgpu_host_libm_check": (_i, [C.POINTER(_i64)]),

@@ -73,12 +73,21 @@ inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 // arena that grows (hipFree waits for the device) -- calls center_note_wait() beside its wait.
 extern std::atomic<long long> g_center_host_syncs;
 extern thread_local int g_center_scope;
-inline void center_note_wait() { if (g_center_scope > 0) ++g_center_host_syncs; }
+// (urhgpu_test_noise_host_syncs: the same places, counted for the automatic-noise entry points while a NoiseScope is open)
+extern std::atomic<long long> g_noise_host_syncs;
+extern thread_local int g_noise_scope;
+inline void center_note_wait() {
+    if (g_center_scope > 0) ++g_center_host_syncs;
+    if (g_noise_scope > 0) ++g_noise_host_syncs;
+}
 struct CenterScope { CenterScope() { ++g_center_scope; } ~CenterScope() { --g_center_scope; } };
+struct NoiseScope { bool on; explicit NoiseScope(bool enable = true) : on(enable) { if (on) ++g_noise_scope; } ~NoiseScope() { if (on) --g_noise_scope; } };
 
 }  // namespace urh
 
 constexpr size_t kSmallPinned = size_t(1) << 20;
+constexpr int kNoiseMaxChunks = 199;             // detect_noise_level: n / max(1, n / 100) chunks at most
+constexpr size_t kNoiseWorkBytes = 128 * 1024;   // urhgpu_ctx::d_noise_work: 199 x 32 partial (sum, max) pairs, 2 x 256 doubles
 struct urhgpu_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -163,6 +172,12 @@ struct urhgpu_ctx {
     urh::Arena center_work;
     int tune_center_max_bins = 4096;       // bins the pool holds for the single range (urhgpu_ctx_set_tuning "auto_center_max_bins")
     hipEvent_t ev_center = nullptr;        // urhgpu_detect_center_dev on a pipelined context: hand-over between the caller's stream and the tail stream
+    // automatic noise threshold inside a pass (urhgpu_detect_noise_level_dev, urhgpu_iq_to_bits_auto_dev; pass.hip "noise chain"): the partials of
+    // the chunk statistics and the 2 x 199 doubles k_noise_decide reads.  Allocated with the context (kNoiseWorkBytes): it never grows, so it
+    // never waits.  Every noise chain of a context runs on the caller's stream, in order, and so does whatever the hot kernel's stream hands
+    // back to it (hot_launch), so the one scratch serves passes that overlap further down.
+    void *d_noise_work = nullptr;
+    int wide_int_auto = 0;                 // the next urhgpu_iq_to_bits_auto_dev pass takes the wide-loop instantiation (a capture stream's probe said so)
 };
 constexpr size_t kSegBlockBytes = 4096;      // 16 progress counters on their own 128-byte lines, then the SegState
 

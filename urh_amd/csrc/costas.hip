@@ -49,6 +49,9 @@ struct CostasArgs {
     float noise_sqrd, alpha, beta, scale, shift;
     int loop_order;
     int warm;                // un-gated samples a candidate runs before its chunk (from the loop bandwidth, see launch_costas)
+    // not nullptr: the pass's noise threshold was decided on the device (k_noise_decide) -- every kernel loads noise_sqrd from this device float
+    // at its entry (costas_device_noise) instead of taking the launch argument above
+    const float *d_noise = nullptr;
 };
 struct CostasState { float freq, phase; };
 // One rank's shard of a sharded capture (the SH instantiations below; include/urhgpu.h, "PSK across shards"): local sample i is
@@ -75,6 +78,12 @@ template <> struct CostasLoad<URHGPU_DT_U8> { static __device__ __forceinline__ 
 template <> struct CostasLoad<URHGPU_DT_I16> { static __device__ __forceinline__ float2 at(const void *p, int64_t i) { const short2 v = ((const short2 *)p)[i]; return make_float2((float)v.x, (float)v.y); } };
 template <> struct CostasLoad<URHGPU_DT_U16> { static __device__ __forceinline__ float2 at(const void *p, int64_t i) { const ushort2 v = ((const ushort2 *)p)[i]; return make_float2((float)v.x, (float)v.y); } };
 
+template <class A>
+__device__ __forceinline__ A costas_device_noise(const A &a_in) {
+    A a = a_in;
+    if (a.d_noise) a.noise_sqrd = *a.d_noise;                  // (a uniform load, once per workgroup)
+    return a;
+}
 __device__ __forceinline__ bool costas_gated(float2 sm, const CostasArgs &a) { return sm.x * sm.x + sm.y * sm.y <= a.noise_sqrd; }
 
 // One sample of the loop (:291-328): returns the output, updates the state.  err is only carried for loop orders
@@ -163,7 +172,8 @@ __device__ __forceinline__ float costas_step_bf(float2 sm, CostasState &st, floa
 constexpr int kCostasTile = 1024;
 
 template <int DT>
-__global__ __launch_bounds__(64) void k_costas(const CostasArgs a) {
+__global__ __launch_bounds__(64) void k_costas(const CostasArgs a_in) {
+    const CostasArgs a = costas_device_noise(a_in);
     __shared__ float2 s_x[kCostasTile];
     const int lane = threadIdx.x;
     CostasState st{0.0f, 1.5f};                                // :261
@@ -269,8 +279,9 @@ template <bool SH, class A> __device__ __forceinline__ bool chunk0_exact(const A
 // SH (a shard): the walk back reads into the halo and stops at global sample 1, exactly where the single-GPU walk does.
 // DEV: c_from / use_seed / seed_freq come from the control block (the arguments are ignored), nothing to do once the chain has closed.
 template <int DT, int ORDER, bool SH = false, bool DEV = false>
-__global__ __launch_bounds__(256) void k_costas_spec(const CostasArgsT<SH> a, SpecBuffers b, int64_t n_chunks, int K, int64_t c_from,
+__global__ __launch_bounds__(256) void k_costas_spec(const CostasArgsT<SH> a_in, SpecBuffers b, int64_t n_chunks, int K, int64_t c_from,
                                                       int use_seed, float seed_freq) {
+    const CostasArgsT<SH> a = costas_device_noise(a_in);
     if constexpr (DEV) {
         if (costas_ctl(b)->done) return;
         c_from = costas_ctl(b)->c_from; use_seed = costas_ctl(b)->use_seed; seed_freq = costas_ctl(b)->seed_freq;
@@ -378,7 +389,8 @@ __global__ __launch_bounds__(256) void k_costas_spec(const CostasArgsT<SH> a, Sp
 
 // The chunk itself, one lane per distinct candidate: checkpoints, end state, un-gated sample count.
 template <int DT, int ORDER, bool SH = false>
-__global__ __launch_bounds__(256) void k_costas_run(const CostasArgsT<SH> a, SpecBuffers b, int K) {
+__global__ __launch_bounds__(256) void k_costas_run(const CostasArgsT<SH> a_in, SpecBuffers b, int K) {
+    const CostasArgsT<SH> a = costas_device_noise(a_in);
     const int64_t gid = blockIdx.x * 256ll + threadIdx.x;
     if (gid >= *b.run_count) return;
     const int64_t ck = b.run_list[gid];
@@ -466,8 +478,9 @@ constexpr int kStitchBlock = 1024;              // 16 wavefronts: the fast-forwa
 // DEV: c_from comes from the control block, which the exit rewrites for the round queued behind this one (see CostasCtl); the host
 // passes allow_break = 0 to the last stitch it has queued, so the chain always closes.
 template <int DT, int ORDER, bool SH = false, bool DEV = false>
-__global__ __launch_bounds__(kStitchBlock) void k_costas_stitch(const CostasArgsT<SH> a, SpecBuffers b, int64_t n_chunks, int K, int64_t c_from,
+__global__ __launch_bounds__(kStitchBlock) void k_costas_stitch(const CostasArgsT<SH> a_in, SpecBuffers b, int64_t n_chunks, int K, int64_t c_from,
                                                                  int allow_break) {
+    const CostasArgsT<SH> a = costas_device_noise(a_in);
     if constexpr (DEV) {
         const int done = costas_ctl(b)->done;
         c_from = costas_ctl(b)->c_from > 1 ? costas_ctl(b)->c_from : 1;
@@ -616,7 +629,8 @@ __global__ __launch_bounds__(kStitchBlock) void k_costas_stitch(const CostasArgs
 // sample (gidx >= 0) is evaluated by kNumCkpt lanes, each from the candidate's checkpoint state (bitwise the true state
 // there); any other chunk by one lane from T[c].
 template <int DT, int ORDER, bool SH = false>
-__global__ __launch_bounds__(256) void k_costas_final(const CostasArgsT<SH> a, SpecBuffers b, int64_t n_chunks, int K) {
+__global__ __launch_bounds__(256) void k_costas_final(const CostasArgsT<SH> a_in, SpecBuffers b, int64_t n_chunks, int K) {
+    const CostasArgsT<SH> a = costas_device_noise(a_in);
     const int64_t gid = blockIdx.x * 256ll + threadIdx.x;
     const int64_t c = gid / kNumCkpt;
     const int j = (int)(gid % kNumCkpt);            // segment j = samples [j kCkpt, (j + 1) kCkpt) of the chunk
@@ -836,9 +850,9 @@ static int costas_args(const urhgpu_params *p, CostasArgs &a) {
     return URHGPU_OK;
 }
 
-int launch_costas(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad, void *scratch) {
+int launch_costas(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad, void *scratch, const float *d_noise) {
     CostasArgs a;
-    a.iq = d_iq; a.n = n; a.out = d_qad;
+    a.iq = d_iq; a.n = n; a.out = d_qad; a.d_noise = d_noise;
     URH_TRY(costas_args(p, a));
     switch (p->dtype) {
         case URHGPU_DT_I8: return launch_costas_dt<URHGPU_DT_I8>(a, scratch, ctx);

@@ -10,6 +10,8 @@ namespace urh {
 thread_local char g_hip_err[256] = "";
 std::atomic<long long> g_center_host_syncs{0};
 thread_local int g_center_scope = 0;
+std::atomic<long long> g_noise_host_syncs{0};
+thread_local int g_noise_scope = 0;
 
 int Arena::reserve(size_t bytes) {
     if (bytes <= cap) return URHGPU_OK;
@@ -102,6 +104,7 @@ int urhgpu_ctx_create(int device, urhgpu_ctx **out) {
     URH_HIP(hipMalloc((void **)&ctx->d_counts, 16 * sizeof(int64_t)));
     URH_HIP(hipMalloc((void **)&ctx->d_tickets, 16 * sizeof(int32_t)));     // [0..3] elections, [4..7] ResolveAux, [8..9] tile tail's huge-row counters
     URH_HIP(hipMemset(ctx->d_tickets, 0, 16 * sizeof(int32_t)));
+    URH_HIP(hipMalloc(&ctx->d_noise_work, kNoiseWorkBytes));               // the noise chain's scratch: fixed, part of the context
     {   // d_tickets[4..7] is the ResolveAux block of the resolve kernels: kAuxNone x3, -1
         const int32_t aux0[4] = {kAuxNone, kAuxNone, kAuxNone, -1};
         URH_HIP(hipMemcpy(ctx->d_tickets + 4, aux0, sizeof(aux0), hipMemcpyHostToDevice));
@@ -147,6 +150,7 @@ int urhgpu_ctx_destroy(urhgpu_ctx *ctx) {
     for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
     if (ctx->d_counts) (void)hipFree(ctx->d_counts);
     if (ctx->d_tickets) (void)hipFree(ctx->d_tickets);
+    if (ctx->d_noise_work) (void)hipFree(ctx->d_noise_work);
     if (ctx->d_desc) (void)hipFree(ctx->d_desc);
     if (ctx->d_rdesc) (void)hipFree(ctx->d_rdesc);
     if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);

@@ -413,11 +413,13 @@ __device__ __forceinline__ uint32_t classify(float q, const RunArgs &p, bool che
 }
 
 // Demodulate one sample.  (pc,pd) = previous IQ sample, (c,d) = this one.
-template <int MOD, int DT = URHGPU_DT_F32>
-__device__ __forceinline__ float demod_one(float pc, float pd, float c, float d, const RunArgs &p) {
+// DN (here and in the helpers below): noise_sqrd is the value `nsq` the kernel loaded from device memory (RunArgs::d_noise), not the launch
+// argument p.noise_sqrd -- which the instantiations without DN read exactly where they always did
+template <int MOD, int DT = URHGPU_DT_F32, bool DN = false>
+__device__ __forceinline__ float demod_one(float pc, float pd, float c, float d, const RunArgs &p, float nsq) {
     if (MOD == URHGPU_MOD_ASK && DT != URHGPU_DT_F32 && p.seg_mode) return seg_value_int(c, d, p.thr[0]);
     const float mag = c * c + d * d;
-    if (mag <= p.noise_sqrd) return p.noise_val;
+    if (mag <= (DN ? nsq : p.noise_sqrd)) return p.noise_val;
     if (MOD == URHGPU_MOD_ASK) return __builtin_sqrtf(mag) / p.max_magnitude;   // (double)sqrtf/(double) == fp32 div
     if (MOD == URHGPU_MOD_FSK) {
         float re, im;
@@ -486,11 +488,11 @@ __device__ __forceinline__ void load_rows_v4(const RunArgs &p, int64_t a0, int r
 // noise-gated (the fast path: states follow from the thresholds alone), 1 when q0/q1 are final but some sample is gated,
 // 2 (FSK only) when some lane needs the general code: q0/q1 are then NOT valid and the caller redoes the row with
 // fsk_row_general().
-template <int MOD>
-__device__ __forceinline__ int demod_pair(const RowIn &r, float prev_c, float prev_d, const RunArgs &p, float &q0, float &q1) {
+template <int MOD, bool DN = false>
+__device__ __forceinline__ int demod_pair(const RowIn &r, float prev_c, float prev_d, const RunArgs &p, float nsq, float &q0, float &q1) {
     const float c0 = r.c0, d0 = r.d0, c1 = r.c1, d1 = r.d1;
     const float mag0 = c0 * c0 + d0 * d0, mag1 = c1 * c1 + d1 * d1;
-    const bool n0 = mag0 <= p.noise_sqrd, n1 = mag1 <= p.noise_sqrd;
+    const bool n0 = mag0 <= (DN ? nsq : p.noise_sqrd), n1 = mag1 <= (DN ? nsq : p.noise_sqrd);
     const bool any_noise = __builtin_amdgcn_ballot_w64(n0 | n1) != 0;
     if (any_noise && __builtin_amdgcn_ballot_w64(n0 & n1) == ~0ull) {     // a row inside a pause: all NOISE
         q0 = q1 = p.noise_val;
@@ -554,11 +556,11 @@ __device__ __forceinline__ int demod_pair(const RowIn &r, float prev_c, float pr
 // samples unconditionally and returns true when the lane needs anything else (a noise-gated sample, an FSK
 // quotient outside the fast range).  The caller ballots the flags of a whole batch of rows once and sends only
 // the flagged rows through demod_pair: the hot loop has no per-row branches and the rows' dependent chains interleave.
-template <int MOD, int DT = URHGPU_DT_F32>
-__device__ __forceinline__ bool spec_pair(const RowIn &r, float prev_c, float prev_d, const RunArgs &p, float &q0, float &q1) {
+template <int MOD, int DT = URHGPU_DT_F32, bool DN = false>
+__device__ __forceinline__ bool spec_pair(const RowIn &r, float prev_c, float prev_d, const RunArgs &p, float nsq, float &q0, float &q1) {
     const float c0 = r.c0, d0 = r.d0, c1 = r.c1, d1 = r.d1;
     const float mag0 = c0 * c0 + d0 * d0, mag1 = c1 * c1 + d1 * d1;
-    const bool n0 = mag0 <= p.noise_sqrd, n1 = mag1 <= p.noise_sqrd;
+    const bool n0 = mag0 <= (DN ? nsq : p.noise_sqrd), n1 = mag1 <= (DN ? nsq : p.noise_sqrd);
     if (MOD == URHGPU_MOD_FSK) {
         const float pc = dpp_wave_shr1(c1, prev_c), pd = dpp_wave_shr1(d1, prev_d);
         const float re0 = pc * c0 + pd * d0, im0 = pc * d0 - pd * c0;
@@ -601,10 +603,11 @@ __device__ __forceinline__ bool spec_pair(const RowIn &r, float prev_c, float pr
 // true when the lane needs something else (a gated sample, |re| outside the division's window, |im/re| outside [2^-29, 2^25) --
 // which includes an exactly zero cross product).  For lanes inside spec_pair's range the result is the same bits: there the
 // reduction is "none", u = |t|, and t - poly(t) is odd in t.
-__device__ __forceinline__ bool ext_pair(const RowIn &r, float prev_c, float prev_d, const RunArgs &p, float &q0, float &q1) {
+template <bool DN = false>
+__device__ __forceinline__ bool ext_pair(const RowIn &r, float prev_c, float prev_d, const RunArgs &p, float nsq, float &q0, float &q1) {
     const float c0 = r.c0, d0 = r.d0, c1 = r.c1, d1 = r.d1;
     const float mag0 = c0 * c0 + d0 * d0, mag1 = c1 * c1 + d1 * d1;
-    const bool n0 = mag0 <= p.noise_sqrd, n1 = mag1 <= p.noise_sqrd;
+    const bool n0 = mag0 <= (DN ? nsq : p.noise_sqrd), n1 = mag1 <= (DN ? nsq : p.noise_sqrd);
     const float pc = dpp_wave_shr1(c1, prev_c), pd = dpp_wave_shr1(d1, prev_d);
     const float re0 = pc * c0 + pd * d0, im0 = pc * d0 - pd * c0;
     const float re1 = c0 * c1 + d0 * d1, im1 = c0 * d1 - d0 * c1;
@@ -619,14 +622,15 @@ __device__ __forceinline__ bool ext_pair(const RowIn &r, float prev_c, float pre
 
 // The general FSK row (any operand class, any angle, noise gating).  Deliberately rolled up (one
 // copy of the general atan2f per kernel) so that the hot loop stays small in the instruction cache.
-__device__ __forceinline__ void fsk_row_general(const RowIn &r, float prev_c, float prev_d, const RunArgs &p, float &q0, float &q1) {
+template <bool DN = false>
+__device__ __forceinline__ void fsk_row_general(const RowIn &r, float prev_c, float prev_d, const RunArgs &p, float nsq, float &q0, float &q1) {
     const float pc = dpp_wave_shr1(r.c1, prev_c), pd = dpp_wave_shr1(r.d1, prev_d);
     float out[2];
 #pragma unroll 1
     for (int s = 0; s < 2; ++s) {
         const float a = s ? r.c0 : pc, b = s ? r.d0 : pd, c = s ? r.c1 : r.c0, d = s ? r.d1 : r.d0;
         float re, im, q = p.noise_val;
-        if (!(c * c + d * d <= p.noise_sqrd)) {
+        if (!(c * c + d * d <= (DN ? nsq : p.noise_sqrd))) {
             conj_mul_general(a, b, c, d, re, im);
             q = atan2f_dev(im, re);
         }
@@ -699,8 +703,8 @@ __device__ __forceinline__ void fsk_front(const v4f (&cur)[NB], float &prev_c, f
 }
 // ZEROS_OK (integer captures): an exactly zero cross product -- one sample in 700 at 8 bits -- does not flag the batch (z - 1 wraps to the
 // largest unsigned number for z = 0: it passes the lower bound and z itself the upper one); the caller settles those samples in place.
-template <int NB, bool ZEROS_OK>
-__device__ __forceinline__ bool fsk_divide(const FskFront<NB> &f, const RunArgs &p, v2f (&t)[NB], v2f (&z)[NB]) {
+template <int NB, bool ZEROS_OK, bool DN = false>
+__device__ __forceinline__ bool fsk_divide(const FskFront<NB> &f, const RunArgs &p, float nsq, v2f (&t)[NB], v2f (&z)[NB]) {
     uint32_t re_max = 0u, re_min = 0u, z_max = 0u, z_min = 0u;
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
@@ -715,7 +719,7 @@ __device__ __forceinline__ bool fsk_divide(const FskFront<NB> &f, const RunArgs 
     // (one ballot per compare: the masks are OR-ed on the scalar unit; a ballot of the OR-ed condition costs a v_cndmask + v_cmp)
     const uint64_t any = __builtin_amdgcn_ballot_w64(re_max >= kReLo + kReSpan) | __builtin_amdgcn_ballot_w64(re_min < kReLo) |
                          __builtin_amdgcn_ballot_w64(z_max >= kZHi) | __builtin_amdgcn_ballot_w64(z_min < (ZEROS_OK ? kZLo - 1u : kZLo)) |
-                         __builtin_amdgcn_ballot_w64(f.mag_min <= p.noise_sqrd);
+                         __builtin_amdgcn_ballot_w64(f.mag_min <= (DN ? nsq : p.noise_sqrd));
     return any != 0;
 }
 
@@ -730,8 +734,8 @@ __device__ __forceinline__ bool fsk_divide(const FskFront<NB> &f, const RunArgs 
 // Window (one flag per batch, integer min / max over bit patterns as in fsk_divide): |re| in [2^-40, 2^40), 2^-29 <= ax < 2^25, nothing
 // gated.  Returns 1 when the batch lies outside it (q invalid), else 0, or 2 when it also lies inside the fast loop's window (the caller
 // counts those to find its way back).  ZEROS_OK (integer captures): exact zeros of im pass; the caller settles them.
-template <int NB, bool ZEROS_OK>
-__device__ __forceinline__ int fsk_wide(const FskFront<NB> &f, const RunArgs &p, float (&q0)[NB], float (&q1)[NB]) {
+template <int NB, bool ZEROS_OK, bool DN = false>
+__device__ __forceinline__ int fsk_wide(const FskFront<NB> &f, const RunArgs &p, float nsq, float (&q0)[NB], float (&q1)[NB]) {
     const float pi = 3.1415927410e+00f, pi_lo = -8.7422776573e-08f;
     v2f t[NB];
     uint32_t ax[NB][2];
@@ -749,7 +753,7 @@ __device__ __forceinline__ int fsk_wide(const FskFront<NB> &f, const RunArgs &p,
     }
     const uint64_t out = __builtin_amdgcn_ballot_w64(re_max >= kReLo + kReSpan) | __builtin_amdgcn_ballot_w64(re_min < kReLo) |
                          __builtin_amdgcn_ballot_w64(a_max >= kAtanLo + kAtanExtSpan) | __builtin_amdgcn_ballot_w64(a_min < (ZEROS_OK ? kAtanLo - 1u : kAtanLo)) |
-                         __builtin_amdgcn_ballot_w64(f.mag_min <= p.noise_sqrd);
+                         __builtin_amdgcn_ballot_w64(f.mag_min <= (DN ? nsq : p.noise_sqrd));
     if (out != 0) return 1;
     const uint64_t beyond = __builtin_amdgcn_ballot_w64(a_max >= kAtanLo + kAtanSpan) | __builtin_amdgcn_ballot_w64(raw_max >= 0x80000000u);
     const AtanLutRow *const lut = atan_lut();
@@ -784,8 +788,8 @@ __device__ __forceinline__ int fsk_wide(const FskFront<NB> &f, const RunArgs &p,
 // Demodulate one batch of NB rows (cur[j] = a lane's two samples of row j).  (prev_c, prev_d) is the IQ sample before
 // the batch (wavefront-uniform) and is advanced to the batch's last sample.  Returns the per-row "gated" flags (bit j:
 // some sample of row j may equal the NOISE sentinel, so the classification has to test for it).
-template <int SRC, int DT, int MOD, int NB>
-__device__ __forceinline__ uint32_t demod_batch(const RowIn (&cur)[NB], float &prev_c, float &prev_d, const RunArgs &p,
+template <int SRC, int DT, int MOD, int NB, bool DN = false>
+__device__ __forceinline__ uint32_t demod_batch(const RowIn (&cur)[NB], float &prev_c, float &prev_d, const RunArgs &p, float nsq,
                                                 float (&q0)[NB], float (&q1)[NB], uint32_t &hint) {
     constexpr int kBatch = NB;
     uint32_t general = 0, gated = 0;                        // per-row flags, wavefront-uniform
@@ -814,7 +818,7 @@ __device__ __forceinline__ uint32_t demod_batch(const RowIn (&cur)[NB], float &p
 #pragma unroll
                 for (int j = 0; j < kBatch; ++j) {
                     pcs[j] = prev_c; pds[j] = prev_d;
-                    flag[j] = ext_pair(cur[j], prev_c, prev_d, p, q0[j], q1[j]);
+                    flag[j] = ext_pair<DN>(cur[j], prev_c, prev_d, p, nsq, q0[j], q1[j]);
                     prev_c = lane63(cur[j].c1); prev_d = lane63(cur[j].d1);
                 }
 #pragma unroll
@@ -825,7 +829,7 @@ __device__ __forceinline__ uint32_t demod_batch(const RowIn (&cur)[NB], float &p
 #pragma unroll
             for (int j = 0; j < kBatch; ++j) {
                 pcs[j] = prev_c; pds[j] = prev_d;
-                flag[j] = spec_pair<MOD, DT>(cur[j], prev_c, prev_d, p, q0[j], q1[j]);
+                flag[j] = spec_pair<MOD, DT, DN>(cur[j], prev_c, prev_d, p, nsq, q0[j], q1[j]);
                 if (MOD == URHGPU_MOD_FSK) { prev_c = lane63(cur[j].c1); prev_d = lane63(cur[j].d1); }
             }
 #pragma unroll
@@ -844,7 +848,7 @@ __device__ __forceinline__ uint32_t demod_batch(const RowIn (&cur)[NB], float &p
 #pragma unroll
                 for (int k = 1; k < kBatch; ++k) if (j == k) { r = cur[k]; pc = pcs[k]; pd = pds[k]; }
                 float g0 = 0.f, g1 = 0.f;
-                int kind = demod_pair<MOD>(r, pc, pd, p, g0, g1);
+                int kind = demod_pair<MOD, DN>(r, pc, pd, p, nsq, g0, g1);
                 if (kind == 3) { kind = 0; ++n_ext; }
                 if (kind == 2) general |= 1u << j;
                 else {
@@ -862,7 +866,7 @@ __device__ __forceinline__ uint32_t demod_batch(const RowIn (&cur)[NB], float &p
     for (int j = 0; j < kBatch; ++j) {
         if (SRC == SRC_QAD) { q0[j] = cur[j].c0; q1[j] = cur[j].d0; gated |= 1u << j; continue; }
         pcs[j] = prev_c; pds[j] = prev_d;
-        const int k = demod_pair<MOD>(cur[j], prev_c, prev_d, p, q0[j], q1[j]);
+        const int k = demod_pair<MOD, DN>(cur[j], prev_c, prev_d, p, nsq, q0[j], q1[j]);
         if (k == 2) general |= 1u << j;
         if (k != 0 && k != 3) gated |= 1u << j;
         if (MOD == URHGPU_MOD_FSK) { prev_c = lane63(cur[j].c1); prev_d = lane63(cur[j].d1); }
@@ -876,7 +880,7 @@ __device__ __forceinline__ uint32_t demod_batch(const RowIn (&cur)[NB], float &p
 #pragma unroll
             for (int k = 1; k < kBatch; ++k) if (j == k) { r = cur[k]; pc = pcs[k]; pd = pds[k]; }
             float g0, g1;
-            fsk_row_general(r, pc, pd, p, g0, g1);
+            fsk_row_general<DN>(r, pc, pd, p, nsq, g0, g1);
 #pragma unroll
             for (int k = 0; k < kBatch; ++k) if (j == k) { q0[k] = g0; q1[k] = g1; }
         }
@@ -886,8 +890,8 @@ __device__ __forceinline__ uint32_t demod_batch(const RowIn (&cur)[NB], float &p
 
 // Chunk prologue: the state of sample a0-1 (kStNone when the capture starts at a0) and, for FSK, the IQ sample a0-1
 // itself (the seam operand of the chunk's first sample).  Wavefront-uniform loads.
-template <int SRC, int DT, int MOD, bool ORDER2>
-__device__ __forceinline__ uint32_t chunk_prologue(const RunArgs &p, int64_t a0, bool global_start, float &prev_c, float &prev_d) {
+template <int SRC, int DT, int MOD, bool ORDER2, bool DN = false>
+__device__ __forceinline__ uint32_t chunk_prologue(const RunArgs &p, float nsq, int64_t a0, bool global_start, float &prev_c, float &prev_d) {
     uint32_t st = kStNone;
     if (SRC == SRC_QAD) {
         const float *q = (const float *)p.in;
@@ -909,7 +913,7 @@ __device__ __forceinline__ uint32_t chunk_prologue(const RunArgs &p, int64_t a0,
             have = true;
         }
         if (have) {
-            const float q = is_global0 ? p.noise_val : demod_one<MOD, DT>(pc, pd, prev_c, prev_d, p);
+            const float q = is_global0 ? p.noise_val : demod_one<MOD, DT, DN>(pc, pd, prev_c, prev_d, p, nsq);
             st = classify<ORDER2, SRC == SRC_QAD>(q, p);
         }
     }
@@ -930,7 +934,7 @@ __device__ __forceinline__ uint32_t chunk_init_state(const RunArgs &p, int64_t c
         if (SRC == SRC_IQ && p.seg_mode) {
             float c = 0.f, d = 0.f;
             Iq<DT>::load1(p.in, 0, c, d);
-            init = classify<ORDER2, SRC == SRC_QAD>(demod_one<MOD, DT>(0.f, 0.f, c, d, p), p);
+            init = classify<ORDER2, SRC == SRC_QAD>(demod_one<MOD, DT>(0.f, 0.f, c, d, p, 0.f), p);
         }
     }
     return init;
@@ -962,7 +966,9 @@ __device__ __forceinline__ uint32_t diff_nibble(uint32_t w, uint32_t pw) {
 //   tiles only (the hot launch); the partial tile at the end of a capture is a chunk of its own,
 //   handled by a one-workgroup launch of the bounds-checked instantiation.
 // -----------------------------------------------------------------------------------------------------
-template <int SRC, int DT, int MOD, bool ORDER2, bool WRITE_QAD, bool FULL>
+// DNOISE (IQ input only): the pass's noise threshold was decided on the device (k_noise_decide) -- noise_sqrd is loaded from RunArgs::d_noise,
+// one uniform load per workgroup, instead of being a launch argument
+template <int SRC, int DT, int MOD, bool ORDER2, bool WRITE_QAD, bool FULL, bool DNOISE = false>
 __global__ __launch_bounds__(kBlock, URH_MINWAVES) void k_demod_runs(const RunArgs p) {
     __shared__ __attribute__((aligned(16))) uint8_t s_state[16 + kTile];   // [15] = state of the sample before the tile
     __shared__ uint32_t s_bm[kBlock + 1];
@@ -987,13 +993,14 @@ __global__ __launch_bounds__(kBlock, URH_MINWAVES) void k_demod_runs(const RunAr
     const int64_t a1 = (a0 + p.chunk_len < p.range_end) ? a0 + p.chunk_len : p.range_end;
     uint64_t *slab = p.slab + chunk * p.slab_stride;
     const bool global_start = (p.left_halo == nullptr);
+    const float nsq = DNOISE ? *p.d_noise : 0.f;              // (without DNOISE the helpers read p.noise_sqrd themselves)
     if (SRC == SRC_IQ && MOD == URHGPU_MOD_FSK) { atan_table_init(); __syncthreads(); }
 
     // ---- chunk prologue: the two samples before the chunk (wavefront-uniform loads), the state of
     // sample a0-1, initial carries ------------------------------------------------------------------
     float prev_c = 0.f, prev_d = 0.f;          // IQ sample a0-1: seam operand of the chunk's first sample
     {
-        const uint32_t st = chunk_prologue<SRC, DT, MOD, ORDER2>(p, a0, global_start, prev_c, prev_d);
+        const uint32_t st = chunk_prologue<SRC, DT, MOD, ORDER2, DNOISE>(p, nsq, a0, global_start, prev_c, prev_d);
         if (t == 0) {
             s_prev_state8 = st;
             s_pend_pos = -1; s_pend_state = 0; s_lead = -1; s_carry_last = 0xFFFFu; s_first_state = 0xFFFFu; s_count = 0; s_last_pos = 0;
@@ -1026,7 +1033,7 @@ __global__ __launch_bounds__(kBlock, URH_MINWAVES) void k_demod_runs(const RunAr
                     if (have_cur) load_rows<SRC, DT, FULL>(p, ta + kTile, 0, t, a1, nxt);
                 }
                 float q0[kBatch], q1[kBatch];
-                const uint32_t gated = demod_batch<SRC, DT, MOD, kBatch>(cur, prev_c, prev_d, p, q0, q1, spec_hint);
+                const uint32_t gated = demod_batch<SRC, DT, MOD, kBatch, DNOISE>(cur, prev_c, prev_d, p, nsq, q0, q1, spec_hint);
 #pragma unroll
                 for (int j = 0; j < kBatch; ++j) {
                     const int off = (rb + j) * kRowSamples + 2 * t;
@@ -1281,7 +1288,8 @@ template <int DT, bool WIDEI = false> constexpr int bp_hot_waves() { return (DT 
 template <int SRC, int DT, int MOD, bool RUNS, int NPL> constexpr bool bp_seven() {
     return URH_INT_WAVES7 && SRC == SRC_IQ && MOD == URHGPU_MOD_FSK && RUNS && NPL == 1;
 }
-template <int SRC, int DT, int MOD, bool WRITE_QAD, bool RUNS = true, int NPL = 1, bool STAMPS = false, bool WIDEI = false>
+// DNOISE (IQ input; never with STAMPS): noise_sqrd is loaded from RunArgs::d_noise (see k_demod_runs)
+template <int SRC, int DT, int MOD, bool WRITE_QAD, bool RUNS = true, int NPL = 1, bool STAMPS = false, bool WIDEI = false, bool DNOISE = false>
 __global__ __launch_bounds__((kBlock * bp_waves<SRC, MOD>())) __attribute__((amdgpu_waves_per_eu((STAMPS || bp_seven<SRC, DT, MOD, RUNS, NPL>()) ? bp_hot_waves<DT, WIDEI>() : 1, (STAMPS || bp_seven<SRC, DT, MOD, RUNS, NPL>()) ? bp_hot_waves<DT, WIDEI>() : 8)))
 void k_demod_runs_bp(const RunArgs p) {
     // One workgroup per chunk, URH_WPB wavefronts: wavefront w streams the w-th share of the chunk's rows on its own
@@ -1309,6 +1317,7 @@ void k_demod_runs_bp(const RunArgs p) {
     if (STAMPS && w == 0 && lane == 0) p.chunks[chunk].first_acc = (int32_t)(uint32_t)wall_clock64();
     const bool global_start = (p.left_halo == nullptr);
     const bool first_row = (a0 == 0) && global_start && (w == 0);   // this wavefront holds sample 0 of the capture
+    const float nsq = DNOISE ? *p.d_noise : 0.f;              // (without DNOISE the helpers read p.noise_sqrd themselves)
 
     // the first batch of rows is requested before the prologue's (dependent, wavefront-uniform) loads: their latency overlaps
     constexpr int kBatch = URH_KBATCH;
@@ -1329,7 +1338,7 @@ void k_demod_runs_bp(const RunArgs p) {
 
     float prev_c = 0.f, prev_d = 0.f;                         // IQ sample before my first row (FSK seam operand)
     uint32_t st_before = kStNone;                             // state of sample a0-1: wavefront 0 (it runs phase 2)
-    if (w == 0 && RUNS) st_before = chunk_prologue<SRC, DT, MOD, NPL == 1>(p, a0, global_start, prev_c, prev_d);
+    if (w == 0 && RUNS) st_before = chunk_prologue<SRC, DT, MOD, NPL == 1, DNOISE>(p, nsq, a0, global_start, prev_c, prev_d);
     else if (SRC == SRC_IQ && MOD == URHGPU_MOD_FSK) {
         const int64_t before = a0 + (int64_t)r0 * kRowSamples - 1;
         if (before >= 0) Iq<DT>::load1(p.in, before, prev_c, prev_d);
@@ -1450,7 +1459,7 @@ void k_demod_runs_bp(const RunArgs p) {
                 float nc = prev_c, nd = prev_d;
                 fsk_front<kBatch>(cv, nc, nd, f);
                 v2f t[kBatch], z[kBatch];
-                if (__builtin_expect((fsk_divide<kBatch, kIntCapture>(f, p, t, z)), 0)) break;          // cv still holds batch rb
+                if (__builtin_expect((fsk_divide<kBatch, kIntCapture, DNOISE>(f, p, nsq, t, z)), 0)) break;          // cv still holds batch rb
                 float q0[kBatch], q1[kBatch];
 #pragma unroll
                 for (int j = 0; j < kBatch; ++j) { const v2f q = t[j] - atanf_poly2(t[j], z[j]); q0[j] = q.x; q1[j] = q.y; }
@@ -1485,7 +1494,7 @@ void k_demod_runs_bp(const RunArgs p) {
                     float nc = prev_c, nd = prev_d;
                     fsk_front<kBatch>(cv, nc, nd, f);
                     float q0[kBatch], q1[kBatch];
-                    const int kind = fsk_wide<kBatch, kIntCapture>(f, p, q0, q1);
+                    const int kind = fsk_wide<kBatch, kIntCapture, DNOISE>(f, p, nsq, q0, q1);
                     if (__builtin_expect(kind == 1, 0)) { outside = true; break; }
                     if (kIntCapture) settle_zeros(f, q0, q1, true);
                     prev_c = nc; prev_d = nd;
@@ -1504,7 +1513,7 @@ void k_demod_runs_bp(const RunArgs p) {
 #pragma unroll
             for (int j = 0; j < kBatch; ++j) { cur[j].c0 = cv[j].x; cur[j].d0 = cv[j].y; cur[j].c1 = cv[j].z; cur[j].d1 = cv[j].w; }
             if (!have_nv && rb + kBatch < r_end) load_rows_v4<DT>(p, a0, rb + kBatch, lane, nv);
-            const uint32_t gated = demod_batch<SRC, DT, MOD, kBatch>(cur, prev_c, prev_d, p, q0, q1, spec_hint);
+            const uint32_t gated = demod_batch<SRC, DT, MOD, kBatch, DNOISE>(cur, prev_c, prev_d, p, nsq, q0, q1, spec_hint);
             emit(cur, q0, q1, gated, rb, true);
 #pragma unroll
             for (int j = 0; j < kBatch; ++j) cv[j] = nv[j];
@@ -1516,7 +1525,7 @@ void k_demod_runs_bp(const RunArgs p) {
         for (int rb = r0; rb < r_end; rb += kBatch) {
             float q0[kBatch], q1[kBatch];
             if (rb + kBatch < r_end) load_rows_bp<SRC, DT>(p, a0, rb + kBatch, lane, nxt);
-            const uint32_t gated = demod_batch<SRC, DT, MOD, kBatch>(cur, prev_c, prev_d, p, q0, q1, spec_hint);
+            const uint32_t gated = demod_batch<SRC, DT, MOD, kBatch, DNOISE>(cur, prev_c, prev_d, p, nsq, q0, q1, spec_hint);
             emit(cur, q0, q1, gated, rb, true);
 #pragma unroll
             for (int j = 0; j < kBatch; ++j) cur[j] = nxt[j];
@@ -1718,9 +1727,10 @@ void k_demod_runs_bp(const RunArgs p) {
 constexpr int kAfpBlock = 256;                  // k_afp_demod: 4 wavefronts, 512 samples per workgroup-wide load
 constexpr int kAfpRow = kAfpBlock * 2;
 
-template <int DT, int MOD>
+template <int DT, int MOD, bool DNOISE = false>
 __global__ __launch_bounds__(kAfpBlock) void k_afp_demod(const RunArgs p) {
     const int lane = threadIdx.x & 63;
+    const float nsq = DNOISE ? *p.d_noise : 0.f;                // (DNOISE: the threshold k_noise_decide left in device memory)
     const bool global_start = (p.left_halo == nullptr);
     const int64_t stride = (int64_t)gridDim.x * kAfpRow;
     for (int64_t base = (int64_t)blockIdx.x * kAfpRow; base < p.n; base += stride) {
@@ -1737,10 +1747,10 @@ __global__ __launch_bounds__(kAfpBlock) void k_afp_demod(const RunArgs p) {
         }
         const float pc = dpp_wave_shr1(c1, sc), pd = dpp_wave_shr1(d1, sd);
         if (v0) {
-            float q0 = demod_one<MOD>(pc, pd, c0, d0, p);
+            float q0 = demod_one<MOD, URHGPU_DT_F32, DNOISE>(pc, pd, c0, d0, p, nsq);
             if (i0 == 0 && global_start) q0 = p.noise_val;
             if (v1) {
-                const float q1 = demod_one<MOD>(c0, d0, c1, d1, p);
+                const float q1 = demod_one<MOD, URHGPU_DT_F32, DNOISE>(c0, d0, c1, d1, p, nsq);
                 *(float2 *)(p.qad + i0) = make_float2(q0, q1);
             } else {
                 p.qad[i0] = q0;
@@ -1820,7 +1830,21 @@ static void launch_runs_4(RunArgs a, hipStream_t s, HotEvents *ev) {
         // integer FSK captures with wide phase steps (RunArgs::wide_int): the instantiation with the wide loop
         constexpr bool widei_ok = SRC == SRC_IQ && (DT == URHGPU_DT_I8 || DT == URHGPU_DT_I16) && MOD == URHGPU_MOD_FSK;      // (unsigned samples are not centred: re > 0)
         const unsigned grid = (unsigned)(c_hi - c_lo);
-        if (widei_ok && a.wide_int && planes_ok && (O2 || a.order == 4)) {
+        if (SRC == SRC_IQ && a.d_noise) {
+            // the threshold lives in device memory (RunArgs::d_noise): the DNOISE instantiations -- plain, wide-loop and state-byte; no STAMPS
+            if constexpr (SRC == SRC_IQ) {
+                if (widei_ok && a.wide_int && planes_ok && (O2 || a.order == 4)) {
+                    ++g_wide_int_launches;
+                    if (O2) launch_bp<k_demod_runs_bp<SRC, DT, MOD, WQ, true, 1, false, widei_ok, true>, SRC, MOD>(grid, a, s, ev);
+                    else launch_bp<k_demod_runs_bp<SRC, DT, MOD, WQ, true, 2, false, widei_ok, true>, SRC, MOD>(grid, a, s, nullptr);
+                } else if (planes_ok && O2)
+                    launch_bp<k_demod_runs_bp<SRC, DT, MOD, WQ, true, 1, false, false, true>, SRC, MOD>(grid, a, s, ev);
+                else if (planes_ok && a.order == 4)
+                    launch_bp<k_demod_runs_bp<SRC, DT, MOD, WQ, true, 2, false, false, true>, SRC, MOD>(grid, a, s, nullptr);
+                else
+                    hipLaunchKernelGGL((k_demod_runs<SRC, DT, MOD, O2, WQ, true, true>), dim3(grid), dim3(kBlock), 0, s, a);
+            }
+        } else if (widei_ok && a.wide_int && planes_ok && (O2 || a.order == 4)) {
             ++g_wide_int_launches;
             if (O2) launch_bp<k_demod_runs_bp<SRC, DT, MOD, WQ, true, 1, false, widei_ok>, SRC, MOD>(grid, a, s, ev);
             else launch_bp<k_demod_runs_bp<SRC, DT, MOD, WQ, true, 2, false, widei_ok>, SRC, MOD>(grid, a, s, nullptr);
@@ -1837,7 +1861,11 @@ static void launch_runs_4(RunArgs a, hipStream_t s, HotEvents *ev) {
     if (ranged ? (n_full < a.n && a.launch_lo <= n_main && a.launch_hi > n_main)
                : (n_full < a.n && ((part == 0) || (part == 1 && !tail_is_first) || (part == 2 && tail_is_first)))) {
         a.range_begin = n_full; a.range_end = a.n; a.chunk_base = n_main;
-        hipLaunchKernelGGL((k_demod_runs<SRC, DT, MOD, O2, WQ, false>), dim3(1), dim3(kBlock), 0, s, a);
+        bool launched = false;
+        if constexpr (SRC == SRC_IQ) {
+            if (a.d_noise) { hipLaunchKernelGGL((k_demod_runs<SRC, DT, MOD, O2, WQ, false, true>), dim3(1), dim3(kBlock), 0, s, a); launched = true; }
+        }
+        if (!launched) hipLaunchKernelGGL((k_demod_runs<SRC, DT, MOD, O2, WQ, false>), dim3(1), dim3(kBlock), 0, s, a);
     }
 }
 
@@ -1879,8 +1907,9 @@ int launch_demod_runs_iq(const RunArgs &a, int dtype, int mod, bool write_qad, h
 // above the noise gate; out[0] = per mille of them, out[1] = pairs counted (pinned host memory: the stream reads it at its next push and picks
 // the instantiation, RunArgs::wide_int).  A statistic for a choice of code path only: no result depends on it.
 template <int DT>
-__global__ __launch_bounds__(1024) void k_wide_probe(const void *iq, int64_t n, float noise_sqrd, int32_t *out) {
+__global__ __launch_bounds__(1024) void k_wide_probe(const void *iq, int64_t n, float noise_sqrd, const float *d_noise, int32_t *out) {
     __shared__ int s_w[16], s_v[16];
+    if (d_noise) noise_sqrd = *d_noise;                       // (the gate of a pass whose threshold was decided on the device)
     int wide = 0, valid = 0;
     const int64_t stride = (n - 2) / 4096 > 0 ? (n - 2) / 4096 : 1;
 #pragma unroll
@@ -1907,13 +1936,13 @@ __global__ __launch_bounds__(1024) void k_wide_probe(const void *iq, int64_t n, 
         out[0] = v > 0 ? (int32_t)((int64_t)w * 1000 / v) : 0;
     }
 }
-int launch_wide_probe(const void *d_iq, int dtype, int64_t n, float noise_sqrd, int32_t *h_out, hipStream_t s) {
+int launch_wide_probe(const void *d_iq, int dtype, int64_t n, float noise_sqrd, int32_t *h_out, hipStream_t s, const float *d_noise) {
     if (n < 2 || !d_iq || !h_out) return URHGPU_ERR_ARG;
     switch (dtype) {
-        case URHGPU_DT_I8: hipLaunchKernelGGL(k_wide_probe<URHGPU_DT_I8>, dim3(1), dim3(1024), 0, s, d_iq, n, noise_sqrd, h_out); break;
-        case URHGPU_DT_U8: hipLaunchKernelGGL(k_wide_probe<URHGPU_DT_U8>, dim3(1), dim3(1024), 0, s, d_iq, n, noise_sqrd, h_out); break;
-        case URHGPU_DT_I16: hipLaunchKernelGGL(k_wide_probe<URHGPU_DT_I16>, dim3(1), dim3(1024), 0, s, d_iq, n, noise_sqrd, h_out); break;
-        case URHGPU_DT_U16: hipLaunchKernelGGL(k_wide_probe<URHGPU_DT_U16>, dim3(1), dim3(1024), 0, s, d_iq, n, noise_sqrd, h_out); break;
+        case URHGPU_DT_I8: hipLaunchKernelGGL(k_wide_probe<URHGPU_DT_I8>, dim3(1), dim3(1024), 0, s, d_iq, n, noise_sqrd, d_noise, h_out); break;
+        case URHGPU_DT_U8: hipLaunchKernelGGL(k_wide_probe<URHGPU_DT_U8>, dim3(1), dim3(1024), 0, s, d_iq, n, noise_sqrd, d_noise, h_out); break;
+        case URHGPU_DT_I16: hipLaunchKernelGGL(k_wide_probe<URHGPU_DT_I16>, dim3(1), dim3(1024), 0, s, d_iq, n, noise_sqrd, d_noise, h_out); break;
+        case URHGPU_DT_U16: hipLaunchKernelGGL(k_wide_probe<URHGPU_DT_U16>, dim3(1), dim3(1024), 0, s, d_iq, n, noise_sqrd, d_noise, h_out); break;
         default: return URHGPU_ERR_DTYPE;
     }
     return URHGPU_OK;
@@ -1940,7 +1969,8 @@ static void launch_afp_3(const RunArgs &a0, int grid, hipStream_t s) {
     const int64_t n_main = (a.n / chunk) * chunk;
     if (n_main > 0) {
         a.chunk_len = chunk; a.range_begin = 0; a.range_end = n_main; a.chunk_base = 0;
-        hipLaunchKernelGGL((k_demod_runs_bp<SRC_IQ, DT, MOD, true, false>), dim3((unsigned)(n_main / chunk)), dim3(kBlock * bp_waves<SRC_IQ, MOD>()), 0, s, a);
+        if (a.d_noise) hipLaunchKernelGGL((k_demod_runs_bp<SRC_IQ, DT, MOD, true, false, 1, false, false, true>), dim3((unsigned)(n_main / chunk)), dim3(kBlock * bp_waves<SRC_IQ, MOD>()), 0, s, a);
+        else hipLaunchKernelGGL((k_demod_runs_bp<SRC_IQ, DT, MOD, true, false>), dim3((unsigned)(n_main / chunk)), dim3(kBlock * bp_waves<SRC_IQ, MOD>()), 0, s, a);
     }
     if (n_main < a.n) {
         RunArgs t = a0;
@@ -1951,7 +1981,8 @@ static void launch_afp_3(const RunArgs &a0, int grid, hipStream_t s) {
             t.n = a0.n - n_main;
         }
         const int g = (int)std::min<int64_t>(grid, (t.n + kAfpRow - 1) / kAfpRow);
-        hipLaunchKernelGGL((k_afp_demod<DT, MOD>), dim3(g), dim3(kAfpBlock), 0, s, t);
+        if (t.d_noise) hipLaunchKernelGGL((k_afp_demod<DT, MOD, true>), dim3(g), dim3(kAfpBlock), 0, s, t);
+        else hipLaunchKernelGGL((k_afp_demod<DT, MOD>), dim3(g), dim3(kAfpBlock), 0, s, t);
     }
 }
 

@@ -656,4 +656,83 @@ int launch_mag_chunk_stats(const void *iq, int dtype, int64_t n, int64_t chunk, 
     return launch_mag_any(dtype, iq, n, nullptr, chunk, n_chunks, ps, pm, d_sum, d_max, s);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The decision part of detect_noise_level (AutoInterpretation.py:74-91) on the chunks' (sum, max), chunk 0 = the capture's last chunk, in
+// the reference's own scalar types; one workgroup (there are at most kNoiseMaxChunks chunks), decided by one thread:
+//   mean_k = (float)(sum_k / chunk)                         np.mean of float64 magnitudes, stored by np.fromiter(dtype=float32)
+//   minimum, maximum                                        util.minmax hands Python floats (doubles) back; a NaN mean anywhere ends in 0
+//                                                           (np.min is NaN, no chunk compares, np.max([]) raises ValueError: return 0)
+//   maximum == 0 || minimum / maximum > 0.9  ->  0          a division of doubles against the double 0.9
+//   candidates: mean_k <= 1.1f * min                        numpy's product of a float32 scalar and a Python float is float32
+//   result = max of the candidates' maxima                  fp64; np.max: a NaN maximum wins
+//   ceil(result * 10000) / 10000                            fp64; math.ceil raises for a NaN (ValueError) / an infinity (OverflowError): flag 0
+// The library is built without contraction, so every product above is rounded on its own.  use_cfg (a pass): where the value is not to be
+// used -- flag 0, or flag 2: not below Signal.max_magnitude -- the block's noise_f32 / noise_sqrd are those of the configured threshold.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_noise_decide(const double *sum, const double *mx, int64_t chunk, int n_chunks, double max_mag, float cfg_noise,
+                                                      int use_cfg, urhgpu_noise_result *d_res, urhgpu_noise_result *h_res) {
+    __shared__ float s_mean[256];
+    __shared__ double s_max[256];
+    const int t = threadIdx.x;
+    if (t < n_chunks) { s_mean[t] = (float)(sum[t] / (double)chunk); s_max[t] = mx[t]; }
+    __syncthreads();
+    if (t != 0) return;
+    urhgpu_noise_result r;
+    r.noise = 0.0; r.flag = 1; r.chunk = chunk; r.n_chunks = n_chunks; r.n_candidates = 0; r.min_mean = 0.0; r.max_mean = 0.0;
+    if (n_chunks > 0) {
+        float mn = s_mean[0], mxm = s_mean[0];
+        bool nan = mn != mn;
+        for (int k = 1; k < n_chunks; ++k) {
+            const float e = s_mean[k];
+            nan = nan || (e != e);
+            if (e > mxm) mxm = e;
+            if (e < mn) mn = e;
+        }
+        const double minimum = (double)mn, maximum = (double)mxm;
+        r.min_mean = minimum; r.max_mean = maximum;
+        if (!nan && !(maximum == 0.0 || minimum / maximum > 0.9)) {
+            const float lim = 1.1f * mn;
+            double result = 0.0;
+            bool res_nan = false;
+            int64_t cand = 0;
+            for (int k = 0; k < n_chunks; ++k) {
+                if (!(s_mean[k] <= lim)) continue;
+                const double m = s_max[k];
+                if (m != m) res_nan = true;
+                if (cand == 0 || m > result) result = m;
+                ++cand;
+            }
+            r.n_candidates = cand;
+            if (cand > 0) {
+                if (res_nan) result = __builtin_nan("");
+                if (result != result || result == __builtin_inf() || result == -__builtin_inf()) { r.noise = result; r.flag = 0; }
+                else r.noise = __builtin_ceil(result * 10000.0) / 10000.0;
+            }
+        }
+    }
+    if (r.flag == 1 && !(r.noise < max_mag)) r.flag = 2;
+    r.noise_f32 = (use_cfg && r.flag != 1) ? cfg_noise : (float)r.noise;
+    r.noise_sqrd = r.noise_f32 * r.noise_f32;
+    if (d_res) *d_res = r;
+    if (h_res) *h_res = r;
+}
+
+static_assert(kNoiseWorkBytes >= (size_t)kNoiseMaxChunks * kMagSlices * 16 + 512 + 2 * 256 * 8, "the context's noise scratch holds the partials and the chunk statistics");
+
+// detect_noise_level of a capture as a queued chain: chunk statistics, then the decision.  work: the context's noise scratch
+// (kNoiseWorkBytes).  Nothing here waits for the device.
+int launch_noise_chain(const void *iq, int dtype, int64_t n, double max_mag, float cfg_noise, int use_cfg, void *work, void *d_result, void *h_result,
+                       hipStream_t s) {
+    int64_t chunk = 1, n_chunks = 0;
+    if (n > 3) { chunk = std::max<int64_t>(1, n / 100); n_chunks = n / chunk; }       // :61-72 (int(n * 1 / 100); the front remainder is dropped)
+    if (n_chunks > kNoiseMaxChunks) return URHGPU_ERR_ARG;                            // (cannot happen: n / (n / 100) <= 199)
+    double *d_sum = (double *)work, *d_max = d_sum + 256;
+    void *scratch = d_max + 256;
+    if (n_chunks > 0) URH_TRY(launch_mag_chunk_stats(iq, dtype, n, chunk, n_chunks, d_sum, d_max, scratch, s));
+    hipLaunchKernelGGL(k_noise_decide, dim3(1), dim3(256), 0, s, d_sum, d_max, chunk, (int)n_chunks, max_mag, cfg_noise, use_cfg,
+                       (urhgpu_noise_result *)d_result, (urhgpu_noise_result *)h_result);
+    URH_HIP(hipGetLastError());
+    return URHGPU_OK;
+}
+
 }  // namespace urh

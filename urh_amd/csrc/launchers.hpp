@@ -56,6 +56,10 @@ struct RunArgs {
     // qad-input launches only (launch_runs_qad): not nullptr -- the kernels load their order - 1 thresholds from THIS device array instead of thr[]
     // (a pass that slices with the center it has just detected: k_ac_publish writes them on the same stream, msg_estimators.hip)
     const float *d_thr;
+    // IQ-input launches only: not nullptr -- the kernels load noise_sqrd from THIS device float instead of the argument above (a pass that gates
+    // with the threshold it has just detected: k_noise_decide writes it on the caller's stream, urhgpu_noise_result::noise_sqrd); the DNOISE
+    // instantiations of demod_runs.hip.  Not with seg_mode, progress (streamed segments), stamp_probe or a graded tail.
+    const float *d_noise;
 };
 extern bool g_force_state_bytes;   // test hook: order 2 through the state-byte kernel too
 extern std::atomic<long long> g_wide_int_launches;
@@ -64,7 +68,7 @@ extern int g_tail_skip;            // pulse_table.hip: measurement hook (urhgpu_
 // Start / stop events a caller offers to a hot launch (`ev`): attached to the bit-plane kernel's dispatch itself (hipExtLaunchKernelGGL: the
 // kernel's own begin / end timestamps, what rocprofv3 reports, and its completion signal); `used` says the launcher took them
 struct HotEvents { hipEvent_t start = nullptr, stop = nullptr; bool used = false; };
-int launch_wide_probe(const void *d_iq, int dtype, int64_t n, float noise_sqrd, int32_t *h_out, hipStream_t s);      // demod_runs.hip: k_wide_probe
+int launch_wide_probe(const void *d_iq, int dtype, int64_t n, float noise_sqrd, int32_t *h_out, hipStream_t s, const float *d_noise = nullptr);      // demod_runs.hip: k_wide_probe
 int launch_demod_runs_iq(const RunArgs &a, int dtype, int mod, bool write_qad, hipStream_t s, HotEvents *ev = nullptr);
 int launch_runs_qad(const RunArgs &a, hipStream_t s, HotEvents *ev = nullptr);
 bool runs_streamable(const RunArgs &a);       // RunArgs::progress is honoured for these arguments (bit-plane kernel, whole tiles)
@@ -351,6 +355,10 @@ int launch_magnitudes(const void *iq, int dtype, int64_t n, double *out, hipStre
 size_t mag_chunk_scratch_bytes(int64_t n_chunks);
 int launch_mag_chunk_stats(const void *iq, int dtype, int64_t n, int64_t chunk, int64_t n_chunks, double *d_sum, double *d_max,
                            void *scratch, hipStream_t s);
+// detect_noise_level as a queued chain (chunk statistics + k_noise_decide) into a urhgpu_noise_result on the device and, optionally, in pinned
+// host memory; work: urhgpu_ctx::d_noise_work
+int launch_noise_chain(const void *iq, int dtype, int64_t n, double max_mag, float cfg_noise, int use_cfg, void *work, void *d_result, void *h_result,
+                       hipStream_t s);
 // ---- estimators.hip ----------------------------------------------------------------------------------------
 size_t compact_scratch_bytes(int64_t n);
 int launch_compact_gt(const float *x, int64_t n, const int64_t *d_n, float thr, float *out, int64_t *d_count, void *scratch,
@@ -389,7 +397,7 @@ int launch_pack_blob(const urhgpu_outputs *o, int write_pos, hipStream_t s);
 void launch_copy_shape(const float *in, float *out, int64_t n_samples, int shape, hipStream_t s);
 // ---- costas.hip -----------------------------------------------------------------------------------------------
 size_t costas_scratch_bytes(int64_t n);
-int launch_costas(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad, void *scratch);
+int launch_costas(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad, void *scratch, const float *d_noise = nullptr);
 extern std::atomic<long long> g_costas_host_syncs;        // hipStreamSynchronize calls of the Costas launchers (urhgpu_test_costas_host_syncs)
 void costas_scratch_layout(int64_t n, int K, int64_t out3[3]);     // urhgpu_test_costas_scratch
 // sharded captures: one rank's Costas pass between its two phases (urhgpu_shard_costas_spec_dev / _resolve_dev)

@@ -175,6 +175,10 @@ int reserve_rdesc(urhgpu_ctx *ctx, int64_t n_entries) {
 // the center chain's scratch and the descriptor memory of the tail's scans.  Capture streams call it before their first push.
 int reserve_auto_center_pass(urhgpu_ctx *ctx, int64_t n_max, int tolerance, int64_t cap_rows) {
     URH_TRY(reserve_center_chain(ctx, n_max));
+    return reserve_pass_descriptors(ctx, n_max, tolerance, cap_rows);
+}
+// ... the descriptor memory alone (a stream of automatic-noise passes: the noise chain's scratch is part of the context)
+int reserve_pass_descriptors(urhgpu_ctx *ctx, int64_t n_max, int tolerance, int64_t cap_rows) {
     const Plan pl = make_plan(ctx, n_max, tolerance);
     // chunks of a shorter capture: at most one per tile up to the plan's target, see make_plan
     const int64_t n_chunks = std::max<int64_t>(pl.n_chunks, (int64_t)ctx->prop.multiProcessorCount * 16 + 2);
@@ -201,7 +205,7 @@ void table_args(urhgpu_ctx *ctx, const urhgpu_params *p, const Plan &pl, int64_t
 // scratch must come from ctx->arena (already reserved by the caller).
 int digitize(urhgpu_ctx *ctx, bool from_iq, const void *d_in, int64_t n, const urhgpu_params *p, float *d_qad, int64_t *d_rows, int64_t cap_rows,
              int64_t *d_n_rows, int64_t *d_n_rows_needed, int64_t *d_n_acc, const Plan &pl, int seg_mode, hipStream_t s_tail, const BitsParams *tile_bp,
-             TileTailMem *tile_out, const float *d_thr) {
+             TileTailMem *tile_out, const float *d_thr, const float *d_noise) {
     hipStream_t s = ctx->stream;
     if (s_tail && from_iq) URH_TRY(hot_stream_begin(ctx, &s));
     if (tile_out) tile_out->mem = nullptr;
@@ -209,6 +213,11 @@ int digitize(urhgpu_ctx *ctx, bool from_iq, const void *d_in, int64_t n, const u
     URH_TRY(hot_run_args(ctx, p, pl, n, 0, from_iq, &a));
     a.in = d_in; a.qad = d_qad;
     if (d_thr) { if (from_iq) return URHGPU_ERR_ARG; a.d_thr = d_thr; }      // (thresholds in device memory: the qad-input kernels only)
+    if (d_noise) {                                           // (the noise threshold in device memory: the IQ-input kernels only, never the segmentation)
+        if (!from_iq || seg_mode) return URHGPU_ERR_ARG;
+        a.d_noise = d_noise;
+        if (ctx->wide_int_auto) a.wide_int = 1;              // (what a capture stream's probe saw in the captures before)
+    }
     a.lds_pad = ctx->pipelined ? ctx->hot_lds_pad : 0;
     if (seg_mode) {
         // message segmentation: state = (|sample| > noise threshold) with the 10-sample outlier tolerance.  Reuses the
@@ -345,27 +354,28 @@ int urhgpu_get_center_thresholds(float center, float spacing, int modulation_ord
 // The Costas loop of a PSK pass on the context's stream, its scratch from ctx->aux.  Every Costas kernel of a context runs on that one
 // stream, in order, so the one scratch serves passes that overlap further down (a pipelined pass's tail only reads the demodulated signal).
 // (A capture longer than any before lets the arena grow: hipFree waits for the device first.  Capture streams reserve for n_max up front.)
-static int costas_demod(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad) {
+static int costas_demod(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad, const float *d_noise = nullptr) {
     URH_TRY(ctx->aux.reserve(costas_scratch_bytes(n) + 1024));
     ctx->aux.reset();
     void *scratch = ctx->aux.take(costas_scratch_bytes(n));
-    URH_TRY(launch_costas(ctx, d_iq, n, p, d_qad, scratch));
+    URH_TRY(launch_costas(ctx, d_iq, n, p, d_qad, scratch, d_noise));
     URH_HIP(hipGetLastError());
     return URHGPU_OK;
 }
 
 // ---- device-pointer entry points -------------------------------------------------------------------
 // afp_demod on the context's stream as it is: no wait for an earlier pass's tail (the demodulation takes no scratch from the pass arenas)
-static int afp_demod_queue(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad) {
+// d_noise: not nullptr -- the kernels gate with the noise_sqrd in THIS device float (a pass whose threshold was decided on the device)
+static int afp_demod_queue(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad, const float *d_noise = nullptr) {
     if (n <= 2) {                                   // signal_functions.pyx:335-336
         if (n > 0) URH_HIP(hipMemsetAsync(d_qad, 0, (size_t)n * 4, ctx->stream));
         return URHGPU_OK;
     }
     if (((uintptr_t)d_iq & 15) || ((uintptr_t)d_qad & 7)) return URHGPU_ERR_ARG;
-    if (p->mod == URHGPU_MOD_PSK) return costas_demod(ctx, d_iq, n, p, d_qad);
+    if (p->mod == URHGPU_MOD_PSK) return costas_demod(ctx, d_iq, n, p, d_qad, d_noise);
     RunArgs a;
     memset(&a, 0, sizeof(a));
-    a.in = d_iq; a.qad = d_qad; a.n = n; a.left_halo = nullptr;
+    a.in = d_iq; a.qad = d_qad; a.n = n; a.left_halo = nullptr; a.d_noise = d_noise;
     a.noise_sqrd = p->noise_threshold * p->noise_threshold;
     a.noise_val = noise_for(p);
     URH_TRY(max_magnitude_for(p->dtype, &a.max_magnitude));
@@ -434,13 +444,24 @@ int urhgpu_ppseq_to_bits_dev(urhgpu_ctx *ctx, const int64_t *d_rows, const int64
     return URHGPU_OK;
 }
 
-int urhgpu_iq_to_bits_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p,
-                          const urhgpu_outputs *out) {
+// The automatic noise threshold of a pass (urhgpu_iq_to_bits_auto_dev): where its result block goes.  queue() puts the chain -- chunk
+// statistics, k_noise_decide -- on the caller's stream, in front of whatever gates; the kernels then load block->noise_sqrd.
+struct NoiseAuto {
+    void *d_res, *h_res;
+    const float *d_noise() const { return &((const urhgpu_noise_result *)d_res)->noise_sqrd; }
+    int queue(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p) const {
+        return launch_noise_chain(d_iq, p->dtype, n, urhgpu_noise_max_magnitude(p->dtype), p->noise_threshold, 1, ctx->d_noise_work, d_res, h_res, ctx->stream);
+    }
+};
+
+static int iq_to_bits_impl(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, const urhgpu_outputs *out, const NoiseAuto *na) {
     if (!ctx || !p || !out || n <= 0 || !d_iq || !out->rows || !out->counts) return URHGPU_ERR_ARG;
     if (dtype_bytes(p->dtype) == 0) return URHGPU_ERR_DTYPE;
     URH_TRY(check_params(p, out->bits != nullptr));
     if (((uintptr_t)d_iq & 15) || (out->qad && ((uintptr_t)out->qad & 7))) return URHGPU_ERR_ARG;
     URH_HIP(hipSetDevice(ctx->device));
+    const float *d_noise = na ? na->d_noise() : nullptr;
+    if (na) URH_TRY(na->queue(ctx, d_iq, n, p));             // (its scratch is the context's own: no arena, no wait)
     const Plan pl = make_plan(ctx, n, p->tolerance);
     const bool ask = (p->mod == URHGPU_MOD_ASK);
     const bool fused = !(n <= 2 || p->mod == URHGPU_MOD_PSK);
@@ -463,10 +484,12 @@ int urhgpu_iq_to_bits_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const ur
         if (!qad) { qad = (float *)ctx->arena.take((size_t)n * 4); if (!qad) return URHGPU_ERR_ARG; }      // (piped: the rotating arena's, not a later pass's)
         hipStream_t caller = ctx->stream;
         if (psk_piped) {
-            URH_TRY(costas_demod(ctx, d_iq, n, p, qad));
+            URH_TRY(costas_demod(ctx, d_iq, n, p, qad, d_noise));
             URH_HIP(hipEventRecord(ctx->ev_hot, ctx->stream));
             URH_HIP(hipStreamWaitEvent(ctx->tail_stream, ctx->ev_hot, 0));
             ctx->stream = ctx->tail_stream;
+        } else if (d_noise) {
+            URH_TRY(afp_demod_queue(ctx, d_iq, n, p, qad, d_noise));
         } else {
             URH_TRY(urhgpu_afp_demod_dev(ctx, d_iq, n, p, qad));
         }
@@ -477,7 +500,7 @@ int urhgpu_iq_to_bits_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const ur
     } else {
         URH_TRY(digitize(ctx, true, d_iq, n, p, out->qad, out->rows, out->cap_rows, d_n_rows, ctx->d_counts + 8,
                          ctx->d_counts + 9, pl, 0, piped ? ctx->tail_stream : nullptr, want_bits ? &tile_bp : nullptr,
-                         want_bits ? &tile : nullptr));
+                         want_bits ? &tile : nullptr, nullptr, d_noise));
     }
     int st = URHGPU_OK;
     if (want_bits) {                                                         // else: pulse table only
@@ -503,6 +526,11 @@ int urhgpu_iq_to_bits_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const ur
     ctx->last_tail = piped ? ctx->tail_stream : ctx->stream;
     if (piped) URH_TRY(end_pipelined_pass(ctx));
     return st;
+}
+
+int urhgpu_iq_to_bits_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p,
+                          const urhgpu_outputs *out) {
+    return iq_to_bits_impl(ctx, d_iq, n, p, out, nullptr);
 }
 
 // ---- automatic center inside a pass ------------------------------------------------------------------------------------------
@@ -532,8 +560,8 @@ int urhgpu_detect_center_dev(urhgpu_ctx *ctx, const float *d_qad, int64_t n, int
 
 // The !fused shape of urhgpu_iq_to_bits_dev for every modulation: demodulate into out->qad, find the center of the demodulated signal, slice with
 // it.  Nothing here waits for the device or reads anything back; on a pipelined context everything behind the demodulation goes to the tail stream.
-int urhgpu_iq_to_bits_auto_center_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, int64_t max_size, const urhgpu_outputs *out,
-                                      void *d_result, void *h_result, int64_t hist_cap) {
+static int iq_to_bits_auto_center_impl(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, int64_t max_size, const urhgpu_outputs *out,
+                                       void *d_result, void *h_result, int64_t hist_cap, const NoiseAuto *na) {
     if (!ctx) return URHGPU_ERR_ARG;
     if (!p || !out || n <= 0 || !d_iq || !out->rows || !out->counts || !out->qad || !d_result || hist_cap < 0) return URHGPU_ERR_ARG;
     const bool want_bits = out->bits && out->msg_off && out->pauses && out->pos_off;
@@ -544,6 +572,8 @@ int urhgpu_iq_to_bits_auto_center_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t
     if (p->bits_per_symbol < 1 || p->bits_per_symbol > 7) return URHGPU_ERR_UNSUPPORTED;
     if (((uintptr_t)d_iq & 15) || ((uintptr_t)out->qad & 7)) return URHGPU_ERR_ARG;
     URH_HIP(hipSetDevice(ctx->device));
+    const float *d_noise = na ? na->d_noise() : nullptr;
+    if (na) URH_TRY(na->queue(ctx, d_iq, n, p));             // (the noise chain: on the caller's stream, in front of the demodulation)
     const Plan pl = make_plan(ctx, n, p->tolerance);
     const bool ask = (p->mod == URHGPU_MOD_ASK);
     const bool piped = ctx->pipelined && ctx->tail_stream;
@@ -559,8 +589,8 @@ int urhgpu_iq_to_bits_auto_center_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t
         URH_TRY(ctx->arena.reserve(digitize_scratch_bytes(pl, out->cap_rows, ask, true)));
         ctx->arena.reset();
         // the demodulation on the caller's stream (PSK: the Costas loop, its scratch from ctx->aux)
-        if (p->mod == URHGPU_MOD_PSK && n > 2) URH_TRY(costas_demod(ctx, d_iq, n, p, out->qad));
-        else URH_TRY(afp_demod_queue(ctx, d_iq, n, p, out->qad));
+        if (p->mod == URHGPU_MOD_PSK && n > 2) URH_TRY(costas_demod(ctx, d_iq, n, p, out->qad, d_noise));
+        else URH_TRY(afp_demod_queue(ctx, d_iq, n, p, out->qad, d_noise));
         if (piped) {
             URH_HIP(hipEventRecord(ctx->ev_hot, ctx->stream));
             URH_HIP(hipStreamWaitEvent(ctx->tail_stream, ctx->ev_hot, 0));
@@ -593,6 +623,51 @@ int urhgpu_iq_to_bits_auto_center_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t
     if (piped) URH_TRY(end_pipelined_pass(ctx));
     return st;
 }
+
+int urhgpu_iq_to_bits_auto_center_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, int64_t max_size, const urhgpu_outputs *out,
+                                      void *d_result, void *h_result, int64_t hist_cap) {
+    return iq_to_bits_auto_center_impl(ctx, d_iq, n, p, max_size, out, d_result, h_result, hist_cap, nullptr);
+}
+
+// ---- automatic noise threshold inside a pass ----------------------------------------------------------------------------------
+// Signal.max_magnitude (Signal.py:404-406): (2 * max(min^2, max^2)) ** 0.5 over IQArray.min_max_for_dtype's bounds
+double urhgpu_noise_max_magnitude(int dtype) {
+    switch (dtype) {
+        case URHGPU_DT_I8: return sqrt(2.0 * 128.0 * 128.0);
+        case URHGPU_DT_U8: return sqrt(2.0 * 255.0 * 255.0);
+        case URHGPU_DT_I16: return sqrt(2.0 * 32768.0 * 32768.0);
+        case URHGPU_DT_U16: return sqrt(2.0 * 65535.0 * 65535.0);
+        case URHGPU_DT_F32: return sqrt(2.0);
+        default: return 0.0;
+    }
+}
+
+int urhgpu_detect_noise_level_dev(urhgpu_ctx *ctx, const void *d_iq, int dtype, int64_t n, void *d_result) {
+    if (!ctx || n < 0 || (n > 0 && !d_iq) || !d_result || ((uintptr_t)d_result & 7)) return URHGPU_ERR_ARG;
+    if (dtype_bytes(dtype) == 0) return URHGPU_ERR_DTYPE;
+    if ((uintptr_t)d_iq & (uintptr_t)(dtype_bytes(dtype) - 1)) return URHGPU_ERR_ARG;
+    NoiseScope scope;                                        // (host waits below here are counted: urhgpu_test_noise_host_syncs)
+    URH_HIP(hipSetDevice(ctx->device));
+    return launch_noise_chain(d_iq, dtype, n, urhgpu_noise_max_magnitude(dtype), 0.0f, 0, ctx->d_noise_work, d_result, nullptr, ctx->stream);
+}
+
+int urhgpu_iq_to_bits_auto_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, int auto_noise, int auto_center,
+                               int64_t center_max_size, const urhgpu_outputs *out, void *d_noise_result, void *h_noise_result,
+                               void *d_center_result, void *h_center_result, int64_t hist_cap) {
+    if (!ctx) return URHGPU_ERR_ARG;
+    if (auto_center && (!out || !out->qad)) return URHGPU_ERR_ARG;       // the center is detected on the materialised demodulated signal
+    if (!auto_noise) {
+        if (auto_center) return urhgpu_iq_to_bits_auto_center_dev(ctx, d_iq, n, p, center_max_size, out, d_center_result, h_center_result, hist_cap);
+        return urhgpu_iq_to_bits_dev(ctx, d_iq, n, p, out);
+    }
+    if (!d_noise_result || ((uintptr_t)d_noise_result & 7) || ((uintptr_t)h_noise_result & 7)) return URHGPU_ERR_ARG;
+    NoiseScope scope;                                        // (host waits below here are counted: urhgpu_test_noise_host_syncs)
+    const NoiseAuto na{d_noise_result, h_noise_result};
+    if (auto_center) return iq_to_bits_auto_center_impl(ctx, d_iq, n, p, center_max_size, out, d_center_result, h_center_result, hist_cap, &na);
+    return iq_to_bits_impl(ctx, d_iq, n, p, out, &na);
+}
+
+int64_t urhgpu_test_noise_host_syncs(void) { return (int64_t)urh::g_noise_host_syncs.load(); }
 
 int64_t urhgpu_center_hist_cap(urhgpu_ctx *ctx) { return ctx ? (int64_t)ctx->tune_center_max_bins : 0; }
 

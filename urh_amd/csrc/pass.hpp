@@ -45,12 +45,13 @@ int tile_tail_mem(urhgpu_ctx *ctx, int64_t n_entries, bool expands_bits, TileTai
 int scan_state(urhgpu_ctx *ctx, int64_t cap_rows, ScanState *out);
 int reserve_rdesc(urhgpu_ctx *ctx, int64_t n_entries);
 int reserve_auto_center_pass(urhgpu_ctx *ctx, int64_t n_max, int tolerance, int64_t cap_rows);
+int reserve_pass_descriptors(urhgpu_ctx *ctx, int64_t n_max, int tolerance, int64_t cap_rows);
 BitsParams bits_params(const urhgpu_params *p);
 int begin_pipelined_pass(urhgpu_ctx *ctx);
 int end_pipelined_pass(urhgpu_ctx *ctx);
 int digitize(urhgpu_ctx *ctx, bool from_iq, const void *d_in, int64_t n, const urhgpu_params *p, float *d_qad, int64_t *d_rows, int64_t cap_rows,
              int64_t *d_n_rows, int64_t *d_n_rows_needed, int64_t *d_n_acc, const Plan &pl, int seg_mode = 0, hipStream_t s_tail = nullptr,
-             const BitsParams *tile_bp = nullptr, TileTailMem *tile_out = nullptr, const float *d_thr = nullptr);
+             const BitsParams *tile_bp = nullptr, TileTailMem *tile_out = nullptr, const float *d_thr = nullptr, const float *d_noise = nullptr);
 
 // msg_estimators.hip: the center chain (detect_center of one range, queued, never waited for) behind the automatic center of a pass
 struct CenterChain { void *d_st; unsigned int *d_hist; float *d_thr; };

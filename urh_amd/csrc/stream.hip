@@ -42,7 +42,10 @@ struct urhgpu_stream {
         // automatic center (urhgpu_stream_set_auto_center): the pass's result block (urhgpu_center_result + the counts of a tied histogram) on the
         // device and in pinned host memory -- two host blocks used alternately, like h_blob2: the one handed out stays while the next pass's lands
         char *d_center = nullptr, *h_center2[2] = {nullptr, nullptr};
+        // automatic noise threshold (urhgpu_stream_set_auto_noise): the pass's urhgpu_noise_result, in the same regime
+        char *d_noise = nullptr, *h_noise2[2] = {nullptr, nullptr};
     } slot[3];
+    int auto_noise = 0;                    // every pass detects its own noise threshold (urhgpu_iq_to_bits_auto_dev) and takes the ordinary route
     int auto_center = 0;                   // every pass detects its own center (urhgpu_iq_to_bits_auto_center_dev) and takes the ordinary route
     int64_t center_max_size = -1, center_hist_cap = 0;
     // The demodulated signal of pass i lives in qad_ring[i % 4]: four buffers for three result slots, so that the result handed out by
@@ -298,6 +301,8 @@ int urhgpu_stream_destroy(urhgpu_stream *st) {
     for (auto &s : st->slot) {
         if (s.d_center) (void)hipFree(s.d_center);
         for (char *h : s.h_center2) if (h) (void)hipHostFree(h);
+        if (s.d_noise) (void)hipFree(s.d_noise);
+        for (char *h : s.h_noise2) if (h) (void)hipHostFree(h);
     }
     for (auto &q : st->qad_ring) if (q) (void)hipFree(q);
     if (st->h_probe) (void)hipHostFree(st->h_probe);
@@ -344,6 +349,35 @@ int urhgpu_stream_center(urhgpu_stream *st, int64_t seq, double *center, int64_t
     return URHGPU_OK;
 }
 
+int urhgpu_stream_set_auto_noise(urhgpu_stream *st, int enable) {
+    if (!st || st->seq != 0) return URHGPU_ERR_ARG;          // before the first push: the result blocks are allocated here, not under queued passes
+    if (!enable) { st->auto_noise = 0; return URHGPU_OK; }
+    urhgpu_ctx *ctx = st->ctx;
+    URH_HIP(hipSetDevice(ctx->device));
+    urh::NoiseScope scope;
+    // what an ordinary pass over up to n_max samples would otherwise allocate when it first needs it (each allocation waits for the device): the
+    // descriptor memory of the tail's scans (the noise chain's own scratch is part of the context)
+    URH_TRY(urh::reserve_pass_descriptors(ctx, st->n_max, st->p.tolerance, st->cap_rows));
+    for (auto &s : st->slot) {
+        if (s.d_noise) continue;
+        URH_HIP(hipMalloc((void **)&s.d_noise, sizeof(urhgpu_noise_result)));
+        for (char *&h : s.h_noise2) { URH_HIP(hipHostMalloc((void **)&h, sizeof(urhgpu_noise_result))); memset(h, 0, sizeof(urhgpu_noise_result)); }
+    }
+    st->auto_noise = 1;
+    return URHGPU_OK;
+}
+
+int urhgpu_stream_noise(urhgpu_stream *st, int64_t seq, double *noise, int64_t *flag) {
+    if (!st || !st->auto_noise || seq < 0 || seq >= st->seq) return URHGPU_ERR_ARG;
+    const urhgpu_stream::Slot &s = st->slot[seq % 3];
+    // the slot's latest pass, handed out -- or the one before it, whose result the latest push has just handed out
+    if (!((s.seq == seq && s.state == 3) || (s.seq == seq + 3))) return URHGPU_ERR_ARG;
+    const urhgpu_noise_result *r = (const urhgpu_noise_result *)s.h_noise2[(seq / 3) & 1];
+    if (noise) *noise = r->noise;
+    if (flag) *flag = r->flag;
+    return URHGPU_OK;
+}
+
 int urhgpu_stream_push(urhgpu_stream *st, const void *d_iq, int64_t n, urhgpu_host_result *ready) {
     return stream_push(st, nullptr, d_iq, n, ready);
 }
@@ -387,18 +421,34 @@ static int stream_push(urhgpu_stream *st, const void *h_iq, const void *d_iq, in
     // sections as soon as the row kernel is through (while the bits are expanded), the head (+ positions) behind the pass's last kernel.
     bool streamed = false, staged = false;
     s.staged = false;
-    if (st->auto_center) {
+    if (st->auto_center || st->auto_noise) {
         // a pass that slices with the center it detects itself: the ordinary route (the segmented and staged tails start beside a hot kernel that
-        // there is none of), one copy in front of it for a capture that is still on the host
+        // there is none of), one copy in front of it for a capture that is still on the host.  A pass that gates with the noise threshold it
+        // detects itself: the same -- the chunks of detect_noise_level count from the END of the capture, so nothing can be gated before all of
+        // it has landed, and a hot kernel that starts behind the decision has no segments to run beside.
         if (h_iq) {
             const size_t bps = st->p.dtype == URHGPU_DT_F32 ? 8 : (st->p.dtype == URHGPU_DT_I16 || st->p.dtype == URHGPU_DT_U16) ? 4 : 2;
             URH_HIP(hipMemcpyAsync(const_cast<void *>(d_iq), h_iq, (size_t)n * bps, hipMemcpyHostToDevice, ctx->stream));
         }
         ctx->costas_stats_next = s.h_costas;
-        const int status = urhgpu_iq_to_bits_auto_center_dev(ctx, d_iq, n, &st->p, st->center_max_size, &pass_out, s.d_center, s.h_center2[(i / 3) & 1],
-                                                             st->center_hist_cap);
+        const bool probe = st->auto_noise && !st->auto_center && st->h_probe != nullptr;      // (signed integer FSK through the fused kernel)
+        if (probe) {
+            const int permille = ((volatile int32_t *)st->h_probe)[0], pairs = ((volatile int32_t *)st->h_probe)[1];
+            if (pairs >= 256) st->wide_int = st->wide_int ? (permille > 3) : (permille >= 10);
+            ctx->wide_int_auto = st->wide_int;
+            if (st->wide_int) st->wide_passes += 1;
+        }
+        const int status = urhgpu_iq_to_bits_auto_dev(ctx, d_iq, n, &st->p, st->auto_noise, st->auto_center, st->center_max_size, &pass_out, s.d_noise,
+                                                      st->auto_noise ? s.h_noise2[(i / 3) & 1] : nullptr, s.d_center,
+                                                      st->auto_center ? s.h_center2[(i / 3) & 1] : nullptr, st->center_hist_cap);
         ctx->costas_stats_next = nullptr;
+        ctx->wide_int_auto = 0;
         URH_TRY(status);
+        if (probe) {                                           // behind the pass's tail, gated like the pass: by the threshold in the slot's block
+            URH_TRY(launch_wide_probe(d_iq, st->p.dtype, n, 0.0f, st->h_probe, ctx->last_tail, &((const urhgpu_noise_result *)s.d_noise)->noise_sqrd));
+            URH_HIP(hipEventRecord(st->ev_probe, ctx->last_tail));
+            st->probe_pending = true;
+        }
         URH_HIP(hipEventRecord(s.ev_tail, ctx->last_tail));
         s.state = 1; s.seq = i; s.n = n;
         st->seq = i + 1;

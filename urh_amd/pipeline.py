@@ -91,6 +91,34 @@ class BitsResult:
         self._hostbits = None
         self._auto = None                                    # auto_center passes, until settled: (pinned result block, max_size, slot), see _settle
         self._center, self._center_flag = None, None
+        self._auto_noise = None                              # auto_noise passes, until read: (pinned urhgpu_noise_result, slot), see _read_noise
+        self._noise, self._noise_flag = None, None
+
+    @property
+    def noise_flag(self):
+        """auto_noise passes: urhgpu_noise_result's flag (1 the pass gated with the threshold it detected; 2 the threshold is not below the
+        sample type's max_magnitude: this result is the reference's zeros(2) result; 0 the reference raises); read with the counts, never
+        raises"""
+        self._read_noise()
+        return self._noise_flag
+
+    @property
+    def noise_threshold(self):
+        """auto_noise passes: detect_noise_level's value for the capture (a Python float), read with the counts; where the reference raises
+        (flag 0) so does this"""
+        self._read_noise()
+        if self._noise_flag == 0:
+            raise_noise_error(self._noise)
+        return self._noise
+
+    def _read_noise(self):
+        """auto_noise passes, before the first read: wait for the pass (the counts' read-back) and look at the pinned result block"""
+        if self._auto_noise is None:
+            return
+        block, _ = self._auto_noise
+        self._read_counts()
+        r = _lib.NoiseResult.from_address(block.data_ptr())
+        self._noise, self._noise_flag = float(r.noise), int(r.flag)
 
     @property
     def center(self):
@@ -109,6 +137,22 @@ class BitsResult:
         """auto_center passes, before the first read: wait for the pass (the counts' read-back), look at the center's flag in the pinned
         result block, and where the device left the decision to the host -- more bins than its pool holds (2), the second and third peak
         tie (3: np.argsort's order of equal counts decides) -- settle the center with numpy and slice the demodulated signal again"""
+        if self._auto_noise is not None:
+            # the hand-out of an auto_noise pass: flag 0 -- the reference's exception (math.ceil of a NaN / an infinity); flag 2 -- what the
+            # reference makes of quad_demod's zeros(2) (Signal.py:474-484): the slicing of two zeros
+            self._read_noise()
+            if self._noise_flag == 0:
+                raise_noise_error(self._noise)
+            (_, slot), self._auto_noise = self._auto_noise, None
+            if self._noise_flag == 2:
+                self._auto = None                            # (no demodulated signal: nothing to find a center on)
+                torch = self._pipe.torch
+                again = self._pipe.qad_to_bits(torch.zeros(2, dtype=torch.float32, device=self._pipe.device), self.params, slot=slot)
+                again.check_capacity()
+                for name in ("qad", "rows_buf", "bits_buf", "msg_off_buf", "pauses_buf", "pos_buf", "pos_off_buf", "counts", "_host_counts", "_rows_needed",
+                             "_ctx", "_outputs"):
+                    setattr(self, name, getattr(again, name))
+                self._hostbits = None
         if self._auto is None:
             return
         (block, max_size, slot), self._auto = self._auto, None
@@ -507,6 +551,13 @@ def positions_from_rows(row_state, row_len, p):
     return pos.astype(np.int64), np.asarray(off, dtype=np.int64)
 
 
+def raise_noise_error(value: float):
+    """what AutoInterpretation.detect_noise_level raises where urhgpu_noise_result's flag is 0: math.ceil of a NaN or of an infinity"""
+    import math
+    math.ceil(float(value) * 10000)
+    raise ValueError("cannot convert float NaN to integer")     # (not reached for a NaN / an infinity: math.ceil has raised)
+
+
 def settle_center(pipe, block_ptr: int, qad, max_size):
     """(flag, center) of an auto_center pass from its result block in host memory (include/urhgpu.h: urhgpu_center_result, then the counts
     of a tied histogram): the device's center for flag 1, None for flag 0; flag 3 -- peaks_center on the shipped histogram, with the
@@ -535,8 +586,14 @@ class CaptureStream:
     and the D2H copy of pass i - 2's compact blob overlap."""
 
     def __init__(self, pipe: "DevicePipeline", n_max: int, p: DemodParams, want_qad=True, want_pos=True, dtype=np.float32, cap_rows=0, latency=None,
-                 auto_center=False, center_max_size=None):
-        """auto_center: every pass detects the center of its own demodulated signal (detect_center with max_size=center_max_size) and slices
+                 auto_center=False, center_max_size=None, auto_noise=False):
+        """auto_noise: every pass detects the noise threshold of its own capture (AutoInterpretation.detect_noise_level, the reference's
+        default_noise_threshold = "automatic") on the device and gates with it, queued like any other pass; every HostBits handed out
+        carries .noise_threshold and .noise_flag (include/urhgpu.h: urhgpu_noise_result).  Flag 2 -- the threshold is not below the sample
+        type's max_magnitude -- is settled when the result is handed out: it becomes the reference's zeros(2) result.  Flag 0 -- the
+        reference raises -- raises here, at the hand-out (from flush(): after the other results have been finalised; the exception's
+        .results holds them, None in the failed places).  May be combined with auto_center.
+        auto_center: every pass detects the center of its own demodulated signal (detect_center with max_size=center_max_size) and slices
         with it, queued like any other pass; every HostBits handed out is final and carries .center (None: no center, the bits are those of
         p.center) and .center_flag.  A pass whose center the device left to numpy (flag 2, 3: uncommon) is sliced again from its d_qad when
         it is handed out -- that may wait for the passes queued behind it; results stay in push order.
@@ -554,6 +611,9 @@ class CaptureStream:
         self._h = h
         self._dtype = np.dtype(dtype)
         self._auto_center, self._center_max_size = bool(auto_center), center_max_size
+        self._auto_noise = bool(auto_noise)
+        if auto_noise:
+            _lib.check(_lib.load().urhgpu_stream_set_auto_noise(h, 1))
         if auto_center:
             if not want_qad:
                 self.close()
@@ -582,6 +642,10 @@ class CaptureStream:
     def _final(self, h: "HostBits"):
         """auto_center streams: the pass's center beside its result; flag 2 / 3 settled here (numpy on the shipped histogram, or the
         single-range estimator on d_qad) and the demodulated signal sliced again with the settled center"""
+        if self._auto_noise:
+            h = self._final_noise(h)
+            if h.noise_flag == 2:
+                return h
         if not self._auto_center:
             return h
         lib, pipe = _lib.load(), self.pipe
@@ -610,6 +674,32 @@ class CaptureStream:
         g = again.host(pool={})                               # (a pinned buffer of its own: the result lives as long as the caller keeps it)
         g.seq, g.n_samples, g.d_qad_ptr, g.params = h.seq, h.n_samples, h.d_qad_ptr, self.params
         g.center, g.center_flag = float(c), h.center_flag
+        if self._auto_noise:
+            g.noise_threshold, g.noise_flag = h.noise_threshold, h.noise_flag
+        return g
+
+    def _final_noise(self, h: "HostBits"):
+        """auto_noise streams: the pass's threshold beside its result; flag 0 raises what the reference raises, flag 2 hands out the slicing
+        of two zeros (the reference's quad_demod gives zeros(2) then, Signal.py:474-484)"""
+        lib, pipe = _lib.load(), self.pipe
+        noise, flag = C.c_double(0.0), C.c_int64(0)
+        _lib.check(lib.urhgpu_stream_noise(self._h, h.seq, C.byref(noise), C.byref(flag)))
+        h.noise_threshold, h.noise_flag = float(noise.value), int(flag.value)
+        if h.noise_flag == 0:
+            raise_noise_error(h.noise_threshold)
+        if h.noise_flag != 2:
+            return h
+        from dataclasses import replace
+        torch = pipe.torch
+        pipe.ctx.set_stream(torch.cuda.current_stream(pipe.device).cuda_stream)
+        p = replace(self.params, write_bit_sample_pos=h.pos32 is not None)
+        again = pipe.qad_to_bits(torch.zeros(2, dtype=torch.float32, device=pipe.device), p, slot="stream")
+        again.check_capacity()
+        g = again.host(pool={})                               # (a pinned buffer of its own: the result lives as long as the caller keeps it)
+        g.seq, g.n_samples, g.d_qad_ptr, g.params = h.seq, h.n_samples, h.d_qad_ptr, self.params
+        g.noise_threshold, g.noise_flag = h.noise_threshold, 2
+        if self._auto_center:
+            g.center, g.center_flag = None, 0
         return g
 
     def push_upload(self, host_iq, dev_iq):
@@ -638,7 +728,19 @@ class CaptureStream:
         n = C.c_int(0)
         _lib.check(_lib.load().urhgpu_stream_flush(self._h, arr, C.byref(n)))
         self._inflight = []                                   # (every pass has finished)
-        return [self._final(HostBits(arr[k], self.params)) for k in range(n.value)]
+        out, failed = [], None
+        for k in range(n.value):
+            try:
+                out.append(self._final(HostBits(arr[k], self.params)))
+            except (ValueError, OverflowError) as exc:            # (an auto_noise pass where the reference raises: the others are still handed out)
+                if not self._auto_noise:
+                    raise
+                out.append(None)
+                failed = failed or exc
+        if failed is not None:
+            failed.results = out
+            raise failed
+        return out
 
     def stats(self) -> dict:
         out = (C.c_int64 * 4)()
@@ -724,18 +826,23 @@ class DevicePipeline:
         self.ctx.reserve(n, p.tolerance)
 
     def stream(self, n_max: int, p: DemodParams, want_qad=True, want_pos=True, dtype=np.float32, cap_rows=0, latency=None, auto_center=False,
-               center_max_size=None) -> CaptureStream:
+               center_max_size=None, auto_noise=False) -> CaptureStream:
         """a CaptureStream on this pipeline's context (which it switches to pipelined passes)"""
-        return CaptureStream(self, n_max, p, want_qad, want_pos, dtype, cap_rows, latency, auto_center, center_max_size)
+        return CaptureStream(self, n_max, p, want_qad, want_pos, dtype, cap_rows, latency, auto_center, center_max_size, auto_noise)
 
-    def iq_to_bits(self, iq, p: DemodParams, want_qad=True, cap_rows=None, slot=0, auto_center=False, center_max_size=None) -> BitsResult:
+    def iq_to_bits(self, iq, p: DemodParams, want_qad=True, cap_rows=None, slot=0, auto_center=False, center_max_size=None, auto_noise=False) -> BitsResult:
         """iq: torch tensor on this device, shape (N, 2) of int8/uint8/int16/uint16/float32, or complex64 (N,).
         The result lives in buffers owned by the pipeline and is overwritten by the next pass with the same `slot`.
         auto_center: the pass detects the center of its own demodulated signal (AutoInterpretation.detect_center with
         max_size=center_max_size, as ProtocolSniffer does per flush) and slices with it, all of it queued on the device
         (urhgpu_iq_to_bits_auto_center_dev); BitsResult.center / .center_flag tell what it found.  Where the device leaves the decision
         to numpy (flag 2, 3) the result is settled on the host before its first read; where there is no center (None) the bits are
-        those of p.center."""
+        those of p.center.
+        auto_noise: the pass detects the noise threshold of the capture (AutoInterpretation.detect_noise_level: the reference's
+        default_noise_threshold = "automatic") on the device and gates with it, all of it queued (urhgpu_iq_to_bits_auto_dev);
+        BitsResult.noise_threshold / .noise_flag tell what it found.  Where the threshold is not below the sample type's max_magnitude
+        (flag 2) the result becomes, before its first read, what the reference makes of quad_demod's zeros(2); where the reference
+        raises (flag 0) the first read raises the same.  May be combined with auto_center."""
         torch = self.torch
         if auto_center and not want_qad:
             raise ValueError("auto_center needs the demodulated signal (want_qad=True)")
@@ -766,6 +873,39 @@ class DevicePipeline:
         o.pos_off = pos_off.data_ptr()
         o.counts = counts.data_ptr()
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        if auto_noise:
+            lib = _lib.load()
+            nres = self._buf(sfx + "noise", (C.sizeof(_lib.NoiseResult),), torch.uint8)
+            nblock = self._pinned.get(("noise", slot))
+            if nblock is None:
+                nblock = torch.zeros(C.sizeof(_lib.NoiseResult), dtype=torch.uint8).pin_memory()
+                self._pinned[("noise", slot)] = nblock
+            d_cres, cblock, hist_cap = None, None, 0
+            if auto_center:
+                hist_cap = int(lib.urhgpu_center_hist_cap(self.ctx.handle))
+                nbytes = C.sizeof(_lib.CenterResult) + 4 * hist_cap
+                d_cres = self._buf(sfx + "center", (nbytes,), torch.uint8)
+                cblock = self._pinned.get(("center", slot))
+                if cblock is None or cblock.numel() < nbytes:
+                    cblock = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+                    self._pinned[("center", slot)] = cblock
+            if self.tail_stream is not None and auto_center:
+                # (as below) a pass that REUSES a slot whose tail may still be pending -- the center chain reads the slot's qad -- waits for that
+                # tail; passes on slots of their own overlap
+                if slot in self._auto_slots:
+                    self.ctx.join()
+                    self._auto_slots.clear()
+                self._auto_slots.add(slot)
+            _lib.check(lib.urhgpu_iq_to_bits_auto_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, C.byref(cp), 1, 1 if auto_center else 0,
+                                                      -1 if center_max_size is None else int(center_max_size), C.byref(o),
+                                                      C.c_void_p(nres.data_ptr()), C.c_void_p(nblock.data_ptr()),
+                                                      C.c_void_p(d_cres.data_ptr()) if auto_center else None,
+                                                      C.c_void_p(cblock.data_ptr()) if auto_center else None, hist_cap))
+            res = BitsResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, self.ctx, pipe=self, outputs=o)
+            res._auto_noise = (nblock, slot)
+            if auto_center:
+                res._auto = (cblock, center_max_size, slot)
+            return res
         if auto_center:
             lib = _lib.load()
             hist_cap = int(lib.urhgpu_center_hist_cap(self.ctx.handle))

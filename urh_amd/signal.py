@@ -102,13 +102,17 @@ class Signal:
         self.changed = False
 
     @classmethod
-    def from_file_streamed(cls, filename, pinned=None, **params):
+    def from_file_streamed(cls, filename, pinned=None, default_noise_threshold=None, **params):
         """`Signal(filename)` followed by `get_protocol_from_signal()` (Signal.py:42-112, IQArray.py:206-227, ProtocolAnalyzer.py:227-287)
         for a capture whose parameters are already known (a project file keeps them per signal): the file is read into PINNED host
         memory, and the upload does not wait for anything -- pieces are copied into the device buffer the Signal keeps and demodulated
         as they land (urhgpu_stream_push_upload); when the call returns the Signal holds the capture, its demodulated signal and the
         digitisation for the given parameters (`bits()` / `get_protocol()` cost nothing more).  params: the Signal's parameters
         (modulation_type, samples_per_symbol, center, tolerance, noise_threshold, ...) plus the constructor's keywords.
+        default_noise_threshold="automatic" (the reference's default setting, Signal.py:97-103): the noise threshold is detected INSIDE the
+        streamed pass, on the device (CaptureStream(auto_noise=True)), and the pass gates with it; afterwards `noise_threshold` holds it,
+        exactly as from_file(..., default_noise_threshold="automatic") followed by get_protocol() would leave it.  A number: that many
+        percent of max_magnitude, as from_file.
         Float32 / signed FSK and PSK captures take this route; everything else (unsigned sample types, which the reference converts
         first; ASK) falls back to from_file + the ordinary lazy passes -- same results either way.
         pinned: an optional dict that keeps the pinned read buffer AND the capture stream (three output slots, six pinned blobs: what a
@@ -128,11 +132,21 @@ class Signal:
             setattr(s, k, v)
         dt = np.dtype(next((t for ext, t in signed.items() if filename.endswith(ext)), np.float32))
         lo, hi = _limits(dt)
-        gated = not (s.noise_threshold < (2 * max(lo ** 2, hi ** 2)) ** 0.5)      # quad_demod's zeros(2) case (:474-484)
+        auto_noise = default_noise_threshold == "automatic"
+        if default_noise_threshold is not None and not auto_noise:
+            s.noise_threshold = float(default_noise_threshold) / 100 * (2 * max(lo ** 2, hi ** 2)) ** 0.5
+
+        def resident():
+            """the capture is on the device: what from_file does with the setting (the lazy passes follow)"""
+            if auto_noise:
+                from .estimators import detect_noise_level_dev
+                s.noise_threshold = detect_noise_level_dev(s.pipe, s._iq)
+            return s
+        gated = not auto_noise and not (s.noise_threshold < (2 * max(lo ** 2, hi ** 2)) ** 0.5)      # quad_demod's zeros(2) case (:474-484)
         if filename.endswith(unsigned) or s.modulation_type not in ("FSK", "PSK") or gated:
             from .iq_array import from_file
             s.iq = from_file(filename, device=s.pipe.device)
-            return s
+            return resident()
         torch = s.pipe.torch
         import os
         n_values = os.path.getsize(filename) // dt.itemsize // 2 * 2          # convert_array_to_iq drops the last half sample (:238-239)
@@ -140,7 +154,7 @@ class Signal:
         if n < 3:
             from .iq_array import from_file
             s.iq = from_file(filename, device=s.pipe.device)
-            return s
+            return resident()
         keep = pinned if pinned is not None else {}
         tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.int8): torch.int8, np.dtype(np.int16): torch.int16}[dt]
         buf = keep.get("buf")
@@ -163,20 +177,25 @@ class Signal:
         kept = False                                                              # the stream lives on in `pinned`
         try:
             p = s.params()
-            key = (id(s.pipe), repr(p), dt.str)
+            key = (id(s.pipe), repr(p), dt.str, auto_noise)
             if pinned is not None and keep.get("stream_key") == key and keep.get("stream") is not None and n <= keep.get("stream_n", 0):
                 st, kept = keep["stream"], True                                   # (its results were copied out by the call that made them)
             else:
                 if pinned is not None and keep.get("stream") is not None:
                     keep.pop("stream").close()
                     keep.pop("stream_key", None)
-                st = s.pipe.stream(n, p, want_qad=True, want_pos=True, dtype=dt)      # (an upload: its own piece-wise route whatever the latency setting)
+                st = s.pipe.stream(n, p, want_qad=True, want_pos=True, dtype=dt, auto_noise=auto_noise)      # (an upload: its own piece-wise route whatever the latency setting)
                 if pinned is not None:
                     keep["stream"], keep["stream_key"], keep["stream_n"], kept = st, key, n, True
             pushed_before = st.stats()["pushed"]
             st.push_upload(host, dev)                                             # (host / dev stay referenced by this frame until flush() returns)
             (h,) = st.flush()
             h.check()
+            if auto_noise:
+                if h.noise_flag != 1:                             # not below max_magnitude: the reference demodulates nothing -- the lazy passes' zeros(2)
+                    raise ValueError("the detected noise threshold gates everything")
+                s._par["noise_threshold"] = h.noise_threshold     # (the pass gated with it: the caches installed below belong to it)
+                auto_noise = False
             from .pipeline import LazyDigitized
             qad = torch.empty(n, dtype=torch.float32, device=s.pipe.device)
             import ctypes as C
@@ -199,7 +218,7 @@ class Signal:
         finally:
             if st is not None and not kept:
                 st.close()
-        return s
+        return resident()
 
     @property
     def iq(self):
