@@ -919,6 +919,63 @@ int urhgpu_stream_noise(urhgpu_stream *st, int64_t seq, double *noise, int64_t *
  * separately for these entry points. */
 int64_t urhgpu_test_noise_host_syncs(void);
 
+/* ---- message records inside a pass: RSSI, first position and ASK padding ----------------------------------------------------------
+ * ProtocolAnalyzer.get_protocol_from_signal (ProtocolAnalyzer.py:227-321) ends with a step per message: ASK messages borrow zero bits
+ * from the pause that follows them until their length is a multiple of message_length_divisor (:256-263, :303-321), the RSSI is the mean
+ * of magnitudes_normalized over one symbol at the middle bit (:267-269), the timestamp comes from the first bit's position (:270-272).
+ * These entry points queue that step behind a pass, while the capture is still in device memory: one record per message.
+ *   padding   only for URHGPU_MOD_ASK and message_length_divisor > 1.  L = bits of the message, missing = (divisor - L % divisor) % divisor;
+ *             applied iff missing > 0 and pause >= samples_per_symbol * missing.  The padded message has L + missing bits, the pause
+ *             pause - missing * samples_per_symbol; of its np positions the last one is replaced and missing more follow: entries
+ *             0 .. np - 2 stay, then A + sps, .., A + missing * sps, then A + missing * sps + the new pause, with A the entry np - 2 -- the
+ *             start S of the closing pause (np = L + 2), or the last bit's position of a TRAILING message (np = L + 1), whose pause is
+ *             the capture's last pulse-table row when that is a pause too short to close it: such a message is padded as well.  The
+ *             record holds n_pad = missing; the caller applies it to bits, pauses and positions.
+ *   mid_pos   entry k = int((L + n_pad) / 2) of those positions: the pass's own entry for k <= np - 2, else A + (k - (np - 2)) * sps
+ *   rssi      np.mean over the samples [mid_pos, mid_pos + sps) as Python slices them (clipped at the capture's end): every magnitude as
+ *             util.get_magnitudes gives it for the sample type (float32: fp32 multiply, add, sqrtf, widened; integer types: C int sum with
+ *             its wrap-around, double sqrt, NaN for a negative sum), divided in fp64 by sqrt(min^2 + max^2) of IQArray.min_max_for_dtype,
+ *             summed in the order of numpy's float64 np.add.reduce -- pieces of 8192 terms one after the other, each piece pairwise
+ *             (eight accumulators per leaf of up to 128 terms, halves split at multiples of 8), as for float32; a contiguous float64
+ *             reduction IS cut into buffer-sized pieces --, divided by the count.  NaN for an empty window.  Bit-equal
+ *             with the reference for every window length (samples_per_symbol is a uint32).
+ *   flag      1 valid; 0: the pass's outputs did not hold the positions the record needs (a capacity was exceeded: repeat the pass);
+ *             -1: the summation gave up (its tree went deeper than the kernel's stack: no 64-bit window length does that)
+ * The timestamp (signal.timestamp + first_pos / sample_rate) is the caller's: one float expression on values the pass does not know. */
+typedef struct urhgpu_msg_record {
+    double rssi;
+    int64_t first_pos;           /* bit_sample_pos[m][0] */
+    int64_t mid_pos;             /* bit_sample_pos[m][int(len(bits) / 2)], after the padding */
+    int32_t n_pad;               /* zero bits borrowed from the pause (0: none) */
+    int32_t flag;
+} urhgpu_msg_record;
+/* Queued behind the pass that filled `out` (urhgpu_iq_to_bits_dev, _auto_center_dev, _auto_dev, urhgpu_ppseq_to_bits_dev), on the stream
+ * that pass's tail ran on: the tail stream of a pipelined context while its tail is pending (urhgpu_ctx_join then covers the records
+ * too), the context's stream otherwise.  No host wait, nothing read back: the kernel reads out->counts[1] on the device, its grid is
+ * bounded and workgroups without a message retire.  out->pos is required (the pass ran with write_bit_sample_pos; whether the positions
+ * are SHIPPED is another decision: leave them out of the pack).  d_iq: the capture the pass demodulated; IT IS READ BY THIS KERNEL,
+ * later than by anything else of the pass: it must stay valid and unchanged until the records are complete.
+ * d_rec: device, 16-byte aligned, cap_msg records; record m belongs to message m, for m < min(n_msg, cap_msg, out->cap_msg).
+ * h_rec: optional pinned host mirror (16-byte aligned, cap_msg records), stored by one wavefront in one contiguous sweep behind the
+ * records kernel; valid once the pass is over, as out->h_counts is.  1 <= message_length_divisor <= 2^30. */
+int urhgpu_msg_records_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, const urhgpu_outputs *out,
+                           int64_t message_length_divisor, void *d_rec, int64_t cap_msg, void *h_rec);
+/* Every pass of the stream ends with its records.  Before the first push (URHGPU_ERR_ARG after): the record blocks for n_max -- and, for
+ * a stream created without want_pos, device room for the positions the kernel reads, which are then computed but not shipped -- are
+ * allocated here, so that no push waits.  Such passes take the ordinary route (tail behind the hot kernel, records behind the tail,
+ * pack + copy behind the records); urhgpu_stream_push_upload makes ONE copy into d_iq in front of the pass.  May be combined with
+ * urhgpu_stream_set_auto_center / _auto_noise.
+ * LIFETIME OF d_iq IN SUCH A STREAM: the records kernel reads d_iq behind the pass's tail.  The event the pass's copy waits for is recorded
+ * behind that kernel, so a result is never handed out before its records kernel has finished: d_iq (urhgpu_stream_push and
+ * urhgpu_stream_push_upload alike) must stay valid and unchanged until the pass's result has been handed out -- a later push's `ready`,
+ * or urhgpu_stream_flush -- and may be overwritten from then on. */
+int urhgpu_stream_set_msg_records(urhgpu_stream *st, int enable, int64_t message_length_divisor);
+/* The records of a pass whose result has been handed out, valid as long as that result: *rec = n_msg records in pinned host memory. */
+int urhgpu_stream_msg_records(urhgpu_stream *st, int64_t seq, const urhgpu_msg_record **rec, int64_t *n_msg);
+/* how often code reached from the message-record entry points (urhgpu_msg_records_dev, the pushes of a stream with records) made the
+ * host wait for the device: the counter of urhgpu_test_center_host_syncs, kept separately for these entry points. */
+int64_t urhgpu_test_records_host_syncs(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,11 @@ class NoiseResult(C.Structure):
                 ("n_chunks", C.c_int64), ("n_candidates", C.c_int64), ("min_mean", C.c_double), ("max_mean", C.c_double)]
 
 
+class MsgRecord(C.Structure):
+    """struct urhgpu_msg_record (include/urhgpu.h)"""
+    _fields_ = [("rssi", C.c_double), ("first_pos", C.c_int64), ("mid_pos", C.c_int64), ("n_pad", C.c_int32), ("flag", C.c_int32)]
+
+
 class HostResult(C.Structure):
     """struct urhgpu_host_result (include/urhgpu.h); pointers are pinned host memory owned by the stream"""
     _fields_ = [
@@ -127,6 +132,10 @@ PROTOTYPES = {
     "urhgpu_stream_set_auto_noise": (_i, [_vp, _i]),
     "urhgpu_stream_noise": (_i, [_vp, _i64, C.POINTER(C.c_double), C.POINTER(_i64)]),
     "urhgpu_test_noise_host_syncs": (_i64, []),
+    "urhgpu_msg_records_dev": (_i, [_vp, _vp, _i64, C.POINTER(Params), C.POINTER(Outputs), _i64, _vp, _i64, _vp]),
+    "urhgpu_stream_set_msg_records": (_i, [_vp, _i, _i64]),
+    "urhgpu_stream_msg_records": (_i, [_vp, _i64, C.POINTER(_vp), C.POINTER(_i64)]),
+    "urhgpu_test_records_host_syncs": (_i64, []),
     "urhgpu_blob_capacity": (_i64, [_i64, _i64, _i64, _i64, _i]),
     "urhgpu_outputs_to_host": (_i, [_vp, C.POINTER(Outputs), _i, _vp, _i64, C.POINTER(_i64)]),
     "urhgpu_host_libm_check": (_i, [C.POINTER(_i64)]),

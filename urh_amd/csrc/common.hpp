@@ -76,12 +76,17 @@ extern thread_local int g_center_scope;
 // (urhgpu_test_noise_host_syncs: the same places, counted for the automatic-noise entry points while a NoiseScope is open)
 extern std::atomic<long long> g_noise_host_syncs;
 extern thread_local int g_noise_scope;
+// (urhgpu_test_records_host_syncs: the same places, counted for the message-record entry points while a RecordsScope is open)
+extern std::atomic<long long> g_records_host_syncs;
+extern thread_local int g_records_scope;
 inline void center_note_wait() {
     if (g_center_scope > 0) ++g_center_host_syncs;
     if (g_noise_scope > 0) ++g_noise_host_syncs;
+    if (g_records_scope > 0) ++g_records_host_syncs;
 }
 struct CenterScope { CenterScope() { ++g_center_scope; } ~CenterScope() { --g_center_scope; } };
 struct NoiseScope { bool on; explicit NoiseScope(bool enable = true) : on(enable) { if (on) ++g_noise_scope; } ~NoiseScope() { if (on) --g_noise_scope; } };
+struct RecordsScope { bool on; explicit RecordsScope(bool enable = true) : on(enable) { if (on) ++g_records_scope; } ~RecordsScope() { if (on) --g_records_scope; } };
 
 }  // namespace urh
 

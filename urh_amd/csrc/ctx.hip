@@ -12,6 +12,8 @@ std::atomic<long long> g_center_host_syncs{0};
 thread_local int g_center_scope = 0;
 std::atomic<long long> g_noise_host_syncs{0};
 thread_local int g_noise_scope = 0;
+std::atomic<long long> g_records_host_syncs{0};
+thread_local int g_records_scope = 0;
 
 int Arena::reserve(size_t bytes) {
     if (bytes <= cap) return URHGPU_OK;

@@ -395,6 +395,11 @@ void seg_ctl_read(const void *host_copy, int64_t *n_seg, int64_t *n_msgs, int *a
 // ---- compact.hip --------------------------------------------------------------------------------------------------
 int launch_pack_blob(const urhgpu_outputs *o, int write_pos, hipStream_t s);
 void launch_copy_shape(const float *in, float *out, int64_t n_samples, int shape, hipStream_t s);
+// ---- msg_records.hip ----------------------------------------------------------------------------------------------
+// one urhgpu_msg_record per message of the pass that filled `out` (out->pos required), from the capture d_iq; cap_rec records at d_rec (device) and,
+// optionally, mirrored at h_rec (pinned host memory) by one wavefront
+int launch_msg_records(const void *d_iq, int64_t n, const urhgpu_params *p, const urhgpu_outputs *out, int64_t divisor, void *d_rec, int64_t cap_rec,
+                       void *h_rec, hipStream_t s);
 // ---- costas.hip -----------------------------------------------------------------------------------------------
 size_t costas_scratch_bytes(int64_t n);
 int launch_costas(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, float *d_qad, void *scratch, const float *d_noise = nullptr);

@@ -44,7 +44,13 @@ struct urhgpu_stream {
         char *d_center = nullptr, *h_center2[2] = {nullptr, nullptr};
         // automatic noise threshold (urhgpu_stream_set_auto_noise): the pass's urhgpu_noise_result, in the same regime
         char *d_noise = nullptr, *h_noise2[2] = {nullptr, nullptr};
+        // message records (urhgpu_stream_set_msg_records): the pass's urhgpu_msg_record block, in the same regime; d_rec_pos: the positions of a
+        // stream without want_pos, which the records kernel reads and nobody ships
+        char *d_rec = nullptr, *h_rec2[2] = {nullptr, nullptr};
+        int64_t *d_rec_pos = nullptr;
     } slot[3];
+    int msg_records = 0;                   // every pass ends with its records (launch_msg_records behind the tail) and takes the ordinary route
+    int64_t rec_divisor = 1, cap_rec = 0;
     int auto_noise = 0;                    // every pass detects its own noise threshold (urhgpu_iq_to_bits_auto_dev) and takes the ordinary route
     int auto_center = 0;                   // every pass detects its own center (urhgpu_iq_to_bits_auto_center_dev) and takes the ordinary route
     int64_t center_max_size = -1, center_hist_cap = 0;
@@ -303,6 +309,9 @@ int urhgpu_stream_destroy(urhgpu_stream *st) {
         for (char *h : s.h_center2) if (h) (void)hipHostFree(h);
         if (s.d_noise) (void)hipFree(s.d_noise);
         for (char *h : s.h_noise2) if (h) (void)hipHostFree(h);
+        if (s.d_rec) (void)hipFree(s.d_rec);
+        if (s.d_rec_pos) (void)hipFree(s.d_rec_pos);
+        for (char *h : s.h_rec2) if (h) (void)hipHostFree(h);
     }
     for (auto &q : st->qad_ring) if (q) (void)hipFree(q);
     if (st->h_probe) (void)hipHostFree(st->h_probe);
@@ -378,6 +387,43 @@ int urhgpu_stream_noise(urhgpu_stream *st, int64_t seq, double *noise, int64_t *
     return URHGPU_OK;
 }
 
+int urhgpu_stream_set_msg_records(urhgpu_stream *st, int enable, int64_t message_length_divisor) {
+    if (!st || st->seq != 0) return URHGPU_ERR_ARG;          // before the first push: everything is allocated here, not under queued passes
+    if (!enable) { st->msg_records = 0; return URHGPU_OK; }
+    if (message_length_divisor < 1 || message_length_divisor > (int64_t(1) << 30)) return URHGPU_ERR_ARG;
+    urhgpu_ctx *ctx = st->ctx;
+    URH_HIP(hipSetDevice(ctx->device));
+    urh::RecordsScope scope;
+    // (as urhgpu_stream_set_auto_noise: the descriptor memory an ordinary pass over n_max samples would otherwise allocate when it first needs it)
+    URH_TRY(urh::reserve_pass_descriptors(ctx, st->n_max, st->p.tolerance, st->cap_rows));
+    // A message is closed by a pause of more than pause_threshold symbols -- more than pause_threshold * samples_per_symbol samples, each closing
+    // one message -- and one more may trail: the records a capture of n_max samples can need (no long pause at all with pause_threshold 0)
+    const int64_t closing = st->p.pause_threshold > 0 ? st->n_max / (st->p.pause_threshold * (int64_t)st->p.samples_per_symbol) : 0;
+    st->cap_rec = std::min<int64_t>(st->cap_msg, closing + 2);
+    const size_t bytes = (size_t)st->cap_rec * sizeof(urhgpu_msg_record);
+    for (auto &s : st->slot) {
+        if (s.d_rec) continue;
+        URH_HIP(hipMalloc((void **)&s.d_rec, bytes));
+        for (char *&h : s.h_rec2) { URH_HIP(hipHostMalloc((void **)&h, bytes)); memset(h, 0, bytes); }
+        if (!st->want_pos) URH_HIP(hipMalloc((void **)&s.d_rec_pos, (size_t)st->cap_pos * 8));
+    }
+    st->msg_records = 1; st->rec_divisor = message_length_divisor;
+    return URHGPU_OK;
+}
+
+int urhgpu_stream_msg_records(urhgpu_stream *st, int64_t seq, const urhgpu_msg_record **rec, int64_t *n_msg) {
+    if (!st || !st->msg_records || !rec || !n_msg || seq < 0 || seq >= st->seq) return URHGPU_ERR_ARG;
+    const urhgpu_stream::Slot &s = st->slot[seq % 3];
+    // the slot's latest pass, handed out -- or the one before it, whose result the latest push has just handed out
+    if (!((s.seq == seq && s.state == 3) || (s.seq == seq + 3))) return URHGPU_ERR_ARG;
+    const int k = (int)((seq / 3) & 1);
+    const int64_t have = ((const int64_t *)s.h_blob2[k])[2];                 // the result's header: n_msg
+    if (have > st->cap_rec) return URHGPU_ERR_CAPACITY;                      // (more messages than the bound above admits: none so far)
+    *rec = (const urhgpu_msg_record *)s.h_rec2[k];
+    *n_msg = have < 0 ? 0 : have;
+    return URHGPU_OK;
+}
+
 int urhgpu_stream_push(urhgpu_stream *st, const void *d_iq, int64_t n, urhgpu_host_result *ready) {
     return stream_push(st, nullptr, d_iq, n, ready);
 }
@@ -389,6 +435,7 @@ int urhgpu_stream_push_upload(urhgpu_stream *st, const void *h_iq, void *d_iq, i
 
 static int stream_push(urhgpu_stream *st, const void *h_iq, const void *d_iq, int64_t n, urhgpu_host_result *ready) {
     if (!st || !d_iq || n <= 2 || n > st->n_max) return URHGPU_ERR_ARG;
+    urh::RecordsScope records_scope(st->msg_records != 0);   // (host waits below here are counted: urhgpu_test_records_host_syncs)
     urhgpu_ctx *ctx = st->ctx;
     URH_HIP(hipSetDevice(ctx->device));
     const int64_t i = st->seq;
@@ -421,7 +468,9 @@ static int stream_push(urhgpu_stream *st, const void *h_iq, const void *d_iq, in
     // sections as soon as the row kernel is through (while the bits are expanded), the head (+ positions) behind the pass's last kernel.
     bool streamed = false, staged = false;
     s.staged = false;
-    if (st->auto_center || st->auto_noise) {
+    if (st->auto_center || st->auto_noise || st->msg_records) {
+        // a pass that ends with its message records: the ordinary route as well -- the records kernel reads the positions the tail leaves in device
+        // memory (the staged and segmented tails store theirs as uint32 into the blob, or compute none) and runs behind the tail, on its stream.
         // a pass that slices with the center it detects itself: the ordinary route (the segmented and staged tails start beside a hot kernel that
         // there is none of), one copy in front of it for a capture that is still on the host.  A pass that gates with the noise threshold it
         // detects itself: the same -- the chunks of detect_noise_level count from the END of the capture, so nothing can be gated before all of
@@ -438,7 +487,12 @@ static int stream_push(urhgpu_stream *st, const void *h_iq, const void *d_iq, in
             ctx->wide_int_auto = st->wide_int;
             if (st->wide_int) st->wide_passes += 1;
         }
-        const int status = urhgpu_iq_to_bits_auto_dev(ctx, d_iq, n, &st->p, st->auto_noise, st->auto_center, st->center_max_size, &pass_out, s.d_noise,
+        urhgpu_params pass_p = st->p;
+        if (st->msg_records) {                                 // the positions are computed whether or not they are shipped (queue_copy packs by want_pos)
+            pass_p.write_bit_sample_pos = 1;
+            if (!st->want_pos) { pass_out.pos = s.d_rec_pos; pass_out.cap_pos = st->cap_pos; }
+        }
+        const int status = urhgpu_iq_to_bits_auto_dev(ctx, d_iq, n, &pass_p, st->auto_noise, st->auto_center, st->center_max_size, &pass_out, s.d_noise,
                                                       st->auto_noise ? s.h_noise2[(i / 3) & 1] : nullptr, s.d_center,
                                                       st->auto_center ? s.h_center2[(i / 3) & 1] : nullptr, st->center_hist_cap);
         ctx->costas_stats_next = nullptr;
@@ -449,6 +503,9 @@ static int stream_push(urhgpu_stream *st, const void *h_iq, const void *d_iq, in
             URH_HIP(hipEventRecord(st->ev_probe, ctx->last_tail));
             st->probe_pending = true;
         }
+        // the records: behind the tail, in front of the event the pass's copy -- and with it the hand-out -- waits for: d_iq is read until then
+        if (st->msg_records)
+            URH_TRY(urh::launch_msg_records(d_iq, n, &pass_p, &pass_out, st->rec_divisor, s.d_rec, st->cap_rec, s.h_rec2[(i / 3) & 1], ctx->last_tail));
         URH_HIP(hipEventRecord(s.ev_tail, ctx->last_tail));
         s.state = 1; s.seq = i; s.n = n;
         st->seq = i + 1;

@@ -88,11 +88,48 @@ class BitsResult:
         self._host_counts = None
         self._ctx = ctx
         self._pipe, self._outputs = pipe, outputs          # the pipeline and the C descriptor of the pass: host() packs through them
+        self._outputs_pos, self._pos_dev = outputs, pos    # msg_records passes that ship no positions: the descriptor WITH the positions the pass computed
         self._hostbits = None
         self._auto = None                                    # auto_center passes, until settled: (pinned result block, max_size, slot), see _settle
         self._center, self._center_flag = None, None
         self._auto_noise = None                              # auto_noise passes, until read: (pinned urhgpu_noise_result, slot), see _read_noise
         self._noise, self._noise_flag = None, None
+        self._rec = None                                     # msg_records passes: (pinned record block, its capacity, capture, divisor, slot)
+
+    @property
+    def records(self):
+        """msg_records passes: one urhgpu_msg_record per message (include/urhgpu.h) as a structured numpy view (protocol.RECORD_DTYPE) of
+        the pinned block the pass mirrored them into -- valid until the next pass with records on the same slot; read with the counts"""
+        if self._rec is None:
+            raise ValueError("this pass was not asked for message records (msg_records=True)")
+        from .protocol import RECORD_DTYPE
+        self._settle()
+        n_msg = self._read_counts()[1]
+        block, cap = self._rec[0], self._rec[1]
+        if n_msg > cap or n_msg > self.pauses_buf.shape[0]:
+            raise _lib.UrhGpuError(_lib.ERR_CAPACITY, f"output capacity too small: {n_msg} messages")
+        rec = block.numpy().view(RECORD_DTYPE)[:n_msg]
+        if not (rec["flag"] == 1).all():
+            bad = np.nonzero(rec["flag"] != 1)[0]
+            raise _lib.UrhGpuError(_lib.ERR_CAPACITY, f"output capacity too small: the positions of {len(bad)} of {n_msg} messages did not fit "
+                                                      f"(first: message {int(bad[0])}, record {rec[bad[0]]}, counts {self._host_counts})")
+        return rec
+
+    def message_data(self, sample_rate=1e6, timestamp=0.0):
+        """msg_records passes: the list of protocol.MessageData ProtocolAnalyzer.get_protocol_from_signal builds its Message objects from
+        (bits, pause, positions -- padded where the record says so --, RSSI, timestamp)"""
+        from .protocol import messages_from_records
+        rec = self.records
+        self.check_capacity()
+        flat = self._flat(True)
+        return messages_from_records(flat, rec, self.params, sample_rate, timestamp)
+
+    def _requeue_records(self, again):
+        """a pass that was sliced again on the host's decision (auto_center flag 2 / 3, auto_noise flag 2): its records again, for the new slicing"""
+        if self._rec is None:
+            return
+        _, _, iq, divisor, slot = self._rec
+        self._rec = self._pipe._queue_records(iq, self.params, again._outputs_pos, divisor, slot) + (iq, divisor, slot)
 
     @property
     def noise_flag(self):
@@ -147,10 +184,12 @@ class BitsResult:
             if self._noise_flag == 2:
                 self._auto = None                            # (no demodulated signal: nothing to find a center on)
                 torch = self._pipe.torch
-                again = self._pipe.qad_to_bits(torch.zeros(2, dtype=torch.float32, device=self._pipe.device), self.params, slot=slot)
+                again = self._pipe.qad_to_bits(torch.zeros(2, dtype=torch.float32, device=self._pipe.device), self.params, slot=slot,
+                                               compute_pos=self._rec is not None)
+                self._requeue_records(again)
                 again.check_capacity()
                 for name in ("qad", "rows_buf", "bits_buf", "msg_off_buf", "pauses_buf", "pos_buf", "pos_off_buf", "counts", "_host_counts", "_rows_needed",
-                             "_ctx", "_outputs"):
+                             "_ctx", "_outputs", "_outputs_pos", "_pos_dev"):
                     setattr(self, name, getattr(again, name))
                 self._hostbits = None
         if self._auto is None:
@@ -162,10 +201,11 @@ class BitsResult:
         self._center = center
         if flag in (2, 3) and center is not None:
             from dataclasses import replace
-            again = self._pipe.qad_to_bits(self.qad, replace(self.params, center=center), slot=slot)
+            again = self._pipe.qad_to_bits(self.qad, replace(self.params, center=center), slot=slot, compute_pos=self._rec is not None)
+            self._requeue_records(again)
             again.check_capacity()
             for name in ("rows_buf", "bits_buf", "msg_off_buf", "pauses_buf", "pos_buf", "pos_off_buf", "counts", "_host_counts", "_rows_needed", "_ctx",
-                         "_outputs"):
+                         "_outputs", "_outputs_pos", "_pos_dev"):
                 setattr(self, name, getattr(again, name))
             self._hostbits = None
 
@@ -252,8 +292,14 @@ class BitsResult:
 
     def flat(self):
         """(bits u8, msg_off i64, pauses i64, pos i64, pos_off i64) on the host (fresh arrays: they outlive the pipeline's buffers)."""
+        return self._flat(False)
+
+    def _flat(self, derive_pos):
+        """flat(); derive_pos: a pass that shipped no positions has them derived from the pulse table (HostBits.bit_sample_pos)"""
         if self._through_blob():
             h = self.host().check()
+            if self.pos_buf is None and derive_pos:
+                return h.flat()
             if self.pos_buf is None:
                 return h.bits(), h.msg_off.copy(), h.pauses.copy(), np.zeros(0, np.int64), h.pos_off.copy()
             return h.flat()
@@ -263,7 +309,8 @@ class BitsResult:
         msg_off = self.msg_off_buf[:n_msg + 1].cpu().numpy()
         pauses = self.pauses_buf[:n_msg].cpu().numpy()
         pos_off = self.pos_off_buf[:n_msg + 1].cpu().numpy()
-        pos = self.pos_buf[:n_pos].cpu().numpy() if self.pos_buf is not None else np.zeros(0, np.int64)
+        src = self.pos_buf if self.pos_buf is not None else (self._pos_dev if derive_pos else None)
+        pos = src[:n_pos].cpu().numpy() if src is not None else np.zeros(0, np.int64)
         return bits, msg_off, pauses, pos, pos_off
 
     def to_host_pinned(self, pool: dict):
@@ -497,6 +544,19 @@ class HostBits:
         """(bits u8, msg_off i64, pauses i64, pos i64, pos_off i64): what BitsResult.flat() gives"""
         return self.bits(), self.msg_off.copy(), self.pauses.copy(), self.bit_sample_pos(), self.pos_offsets()
 
+    def message_data(self, sample_rate=1e6, timestamp=0.0):
+        """results of a stream with msg_records: the list of protocol.MessageData ProtocolAnalyzer.get_protocol_from_signal builds its Message
+        objects from -- bits, pause and positions padded where the pass's record says so, RSSI and timestamp from the record.  Without
+        shipped positions (want_pos=False) bit_sample_pos is derived here from the pulse table."""
+        from .protocol import messages_from_records
+        rec = self.__dict__.get("records")
+        if rec is None:
+            raise ValueError("this result carries no message records (CaptureStream(msg_records=True))")
+        self.check()
+        if len(rec) != self.n_msg or not (rec["flag"] == 1).all():
+            raise _lib.UrhGpuError(_lib.ERR_CAPACITY, "output capacity too small: a message's record is missing")
+        return messages_from_records(self.flat(), rec, self.params, sample_rate, timestamp)
+
 
 def positions_from_rows(row_state, row_len, p):
     """bit_sample_pos of every message from the pulse table, as ProtocolAnalyzer._ppseq_to_bits builds them (:346-411), on whole arrays:
@@ -586,8 +646,13 @@ class CaptureStream:
     and the D2H copy of pass i - 2's compact blob overlap."""
 
     def __init__(self, pipe: "DevicePipeline", n_max: int, p: DemodParams, want_qad=True, want_pos=True, dtype=np.float32, cap_rows=0, latency=None,
-                 auto_center=False, center_max_size=None, auto_noise=False):
-        """auto_noise: every pass detects the noise threshold of its own capture (AutoInterpretation.detect_noise_level, the reference's
+                 auto_center=False, center_max_size=None, auto_noise=False, msg_records=False, message_length_divisor=1):
+        """msg_records: every pass ends with one record per message (urhgpu_stream_set_msg_records: ASK padding to message_length_divisor,
+        first and middle position, RSSI), computed behind its tail while the capture is in device memory; every HostBits handed out carries
+        .records and .message_data(sample_rate, timestamp) -- also with want_pos=False, where the positions are derived on demand as
+        HostBits.bit_sample_pos() does.  A pushed capture must stay unchanged until its result has been handed out, and may be overwritten
+        from then on.  Such passes take the ordinary route.  May be combined with auto_center / auto_noise.
+        auto_noise: every pass detects the noise threshold of its own capture (AutoInterpretation.detect_noise_level, the reference's
         default_noise_threshold = "automatic") on the device and gates with it, queued like any other pass; every HostBits handed out
         carries .noise_threshold and .noise_flag (include/urhgpu.h: urhgpu_noise_result).  Flag 2 -- the threshold is not below the sample
         type's max_magnitude -- is settled when the result is handed out: it becomes the reference's zeros(2) result.  Flag 0 -- the
@@ -612,6 +677,14 @@ class CaptureStream:
         self._dtype = np.dtype(dtype)
         self._auto_center, self._center_max_size = bool(auto_center), center_max_size
         self._auto_noise = bool(auto_noise)
+        self._msg_records, self._divisor = bool(msg_records), int(message_length_divisor)
+        self._captures = {}                                   # msg_records: push index -> device capture (a pass sliced again at hand-out needs it)
+        self._pushed = 0
+        if msg_records:
+            if self._divisor < 1:
+                self.close()
+                raise ValueError("message_length_divisor must be at least 1")
+            _lib.check(_lib.load().urhgpu_stream_set_msg_records(h, 1, self._divisor))
         if auto_noise:
             _lib.check(_lib.load().urhgpu_stream_set_auto_noise(h, 1))
         if auto_center:
@@ -626,6 +699,29 @@ class CaptureStream:
     def _hold(self, *tensors):
         self._inflight.append(tensors)
         del self._inflight[:-4]
+        if self._msg_records:
+            self._captures[self._pushed] = tensors[-1]
+            self._captures.pop(self._pushed - 4, None)
+        self._pushed += 1
+
+    def _records(self, h: "HostBits"):
+        """msg_records streams: the pass's records beside its result (a view of the stream's pinned block, valid as long as the result)"""
+        from .protocol import RECORD_DTYPE
+        rec, n = C.c_void_p(), C.c_int64(0)
+        _lib.check(_lib.load().urhgpu_stream_msg_records(self._h, h.seq, C.byref(rec), C.byref(n)))
+        nbytes = int(n.value) * RECORD_DTYPE.itemsize
+        h.records = np.frombuffer((C.c_ubyte * nbytes).from_address(rec.value), dtype=RECORD_DTYPE, count=int(n.value)) if nbytes else np.zeros(0, RECORD_DTYPE)
+        return h
+
+    def _records_again(self, g: "HostBits", again: "BitsResult", p):
+        """a pass sliced again at its hand-out (auto_center flag 2 / 3, auto_noise flag 2): its records for the new slicing, from the capture
+        the caller still holds unchanged (the result is only now being handed out)"""
+        pipe = self.pipe
+        block, cap = pipe._queue_records(self._captures[g.seq], p, again._outputs_pos, self._divisor, "stream")
+        pipe.ctx.sync()
+        from .protocol import RECORD_DTYPE
+        g.records = block.numpy().view(RECORD_DTYPE)[:min(g.n_msg, cap)].copy()
+        return g
 
     def push(self, iq):
         torch = self.pipe.torch
@@ -642,6 +738,8 @@ class CaptureStream:
     def _final(self, h: "HostBits"):
         """auto_center streams: the pass's center beside its result; flag 2 / 3 settled here (numpy on the shipped histogram, or the
         single-range estimator on d_qad) and the demodulated signal sliced again with the settled center"""
+        if self._msg_records:
+            h = self._records(h)
         if self._auto_noise:
             h = self._final_noise(h)
             if h.noise_flag == 2:
@@ -669,10 +767,12 @@ class CaptureStream:
         if c is None:
             return h
         p = replace(self.params, center=float(c), write_bit_sample_pos=h.pos32 is not None)
-        again = pipe.qad_to_bits(qad, p, slot="stream")
+        again = pipe.qad_to_bits(qad, p, slot="stream", compute_pos=self._msg_records)
         again.check_capacity()
         g = again.host(pool={})                               # (a pinned buffer of its own: the result lives as long as the caller keeps it)
         g.seq, g.n_samples, g.d_qad_ptr, g.params = h.seq, h.n_samples, h.d_qad_ptr, self.params
+        if self._msg_records:
+            g = self._records_again(g, again, p)
         g.center, g.center_flag = float(c), h.center_flag
         if self._auto_noise:
             g.noise_threshold, g.noise_flag = h.noise_threshold, h.noise_flag
@@ -693,10 +793,12 @@ class CaptureStream:
         torch = pipe.torch
         pipe.ctx.set_stream(torch.cuda.current_stream(pipe.device).cuda_stream)
         p = replace(self.params, write_bit_sample_pos=h.pos32 is not None)
-        again = pipe.qad_to_bits(torch.zeros(2, dtype=torch.float32, device=pipe.device), p, slot="stream")
+        again = pipe.qad_to_bits(torch.zeros(2, dtype=torch.float32, device=pipe.device), p, slot="stream", compute_pos=self._msg_records)
         again.check_capacity()
         g = again.host(pool={})                               # (a pinned buffer of its own: the result lives as long as the caller keeps it)
         g.seq, g.n_samples, g.d_qad_ptr, g.params = h.seq, h.n_samples, h.d_qad_ptr, self.params
+        if self._msg_records:
+            g = self._records_again(g, again, p)
         g.noise_threshold, g.noise_flag = h.noise_threshold, 2
         if self._auto_center:
             g.center, g.center_flag = None, 0
@@ -705,7 +807,8 @@ class CaptureStream:
     def push_upload(self, host_iq, dev_iq):
         """A capture that is still on the host (urhgpu_stream_push_upload): host_iq -- a torch CPU tensor (pinned: PCIe speed) or a numpy
         array, (N, 2) of the stream's dtype or complex64 -- is copied into dev_iq (device tensor of the same shape: the capture stays
-        resident there, e.g. as a Signal's data) piece by piece, and every piece is demodulated as it lands.  Returns like push()."""
+        resident there, e.g. as a Signal's data) piece by piece, and every piece is demodulated as it lands.  A stream with msg_records,
+        auto_noise or auto_center uploads in ONE copy in front of an ordinary pass instead.  Returns like push()."""
         torch = self.pipe.torch
         if isinstance(host_iq, np.ndarray):
             host_iq = torch.from_numpy(host_iq)
@@ -757,6 +860,7 @@ class CaptureStream:
             _lib.load().urhgpu_stream_destroy(self._h)
             self._h = None
             self._inflight = []
+            self._captures = {}
 
     def __del__(self):
         try:
@@ -826,11 +930,32 @@ class DevicePipeline:
         self.ctx.reserve(n, p.tolerance)
 
     def stream(self, n_max: int, p: DemodParams, want_qad=True, want_pos=True, dtype=np.float32, cap_rows=0, latency=None, auto_center=False,
-               center_max_size=None, auto_noise=False) -> CaptureStream:
+               center_max_size=None, auto_noise=False, msg_records=False, message_length_divisor=1) -> CaptureStream:
         """a CaptureStream on this pipeline's context (which it switches to pipelined passes)"""
-        return CaptureStream(self, n_max, p, want_qad, want_pos, dtype, cap_rows, latency, auto_center, center_max_size, auto_noise)
+        return CaptureStream(self, n_max, p, want_qad, want_pos, dtype, cap_rows, latency, auto_center, center_max_size, auto_noise, msg_records,
+                             message_length_divisor)
 
-    def iq_to_bits(self, iq, p: DemodParams, want_qad=True, cap_rows=None, slot=0, auto_center=False, center_max_size=None, auto_noise=False) -> BitsResult:
+    def _queue_records(self, iq, p: DemodParams, o, divisor, slot):
+        """urhgpu_msg_records_dev behind the pass that filled the descriptor o (with positions): one record per message into a device block
+        and its pinned mirror, nothing waited for.  Returns (pinned block, its capacity in records)."""
+        torch = self.torch
+        n = int(iq.shape[0])
+        cp = p.to_c(_torch_dtype(iq))
+        pt, sps = int(p.pause_threshold), int(p.samples_per_symbol)
+        # every message but a trailing one is closed by a pause of more than pause_threshold symbols (none at all with pause_threshold 0)
+        cap = int(o.cap_msg) if pt < 0 else min(int(o.cap_msg), (n // (pt * sps) if pt > 0 else 0) + 2)
+        nbytes = max(cap, 1) * C.sizeof(_lib.MsgRecord)
+        d_rec = self._buf(f"s{slot}:records", (nbytes,), torch.uint8)
+        block = self._pinned.get(("records", slot))
+        if block is None or block.numel() < nbytes:
+            block = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+            self._pinned[("records", slot)] = block
+        _lib.check(_lib.load().urhgpu_msg_records_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, C.byref(cp), C.byref(o), int(divisor),
+                                                      C.c_void_p(d_rec.data_ptr()), cap, C.c_void_p(block.data_ptr())))
+        return block, cap
+
+    def iq_to_bits(self, iq, p: DemodParams, want_qad=True, cap_rows=None, slot=0, auto_center=False, center_max_size=None, auto_noise=False,
+                   msg_records=False, message_length_divisor=1) -> BitsResult:
         """iq: torch tensor on this device, shape (N, 2) of int8/uint8/int16/uint16/float32, or complex64 (N,).
         The result lives in buffers owned by the pipeline and is overwritten by the next pass with the same `slot`.
         auto_center: the pass detects the center of its own demodulated signal (AutoInterpretation.detect_center with
@@ -842,7 +967,21 @@ class DevicePipeline:
         default_noise_threshold = "automatic") on the device and gates with it, all of it queued (urhgpu_iq_to_bits_auto_dev);
         BitsResult.noise_threshold / .noise_flag tell what it found.  Where the threshold is not below the sample type's max_magnitude
         (flag 2) the result becomes, before its first read, what the reference makes of quad_demod's zeros(2); where the reference
-        raises (flag 0) the first read raises the same.  May be combined with auto_center."""
+        raises (flag 0) the first read raises the same.  May be combined with auto_center.
+        msg_records: the pass ends with one record per message (urhgpu_msg_records_dev: ASK padding to message_length_divisor, first and
+        middle position, RSSI), queued behind its tail while the capture is in device memory; BitsResult.records / .message_data() hand
+        them out.  The positions are then computed whether or not p.write_bit_sample_pos ships them.  iq must stay unchanged until the
+        result has been read."""
+        res = self._iq_to_bits(iq, p, want_qad, cap_rows, slot, auto_center, center_max_size, auto_noise, bool(msg_records))
+        if msg_records:
+            if int(message_length_divisor) < 1:
+                raise ValueError("message_length_divisor must be at least 1")
+            if iq.dtype == self.torch.complex64:
+                iq = self.torch.view_as_real(iq)
+            res._rec = self._queue_records(iq, p, res._outputs_pos, message_length_divisor, slot) + (iq, int(message_length_divisor), slot)
+        return res
+
+    def _iq_to_bits(self, iq, p, want_qad, cap_rows, slot, auto_center, center_max_size, auto_noise, compute_pos) -> BitsResult:
         torch = self.torch
         if auto_center and not want_qad:
             raise ValueError("auto_center needs the demodulated signal (want_qad=True)")
@@ -853,6 +992,9 @@ class DevicePipeline:
         npdt = _torch_dtype(iq)
         n = iq.shape[0]
         cp = p.to_c(npdt)
+        ship_pos = bool(p.write_bit_sample_pos)
+        if compute_pos:
+            cp.write_bit_sample_pos = 1
         cap_rows, cap_bits, cap_msg, cap_pos = self.capacities(n, p, cap_rows)
         sfx = f"s{slot}:" if slot else ""
         qad = self._buf(sfx + "qad", (n,), torch.float32) if want_qad else None
@@ -861,8 +1003,19 @@ class DevicePipeline:
         msg_off = self._buf(sfx + "msg_off", (cap_msg + 1,), torch.int64)
         pauses = self._buf(sfx + "pauses", (cap_msg,), torch.int64)
         pos_off = self._buf(sfx + "pos_off", (cap_msg + 1,), torch.int64)
-        pos = self._buf(sfx + "pos", (cap_pos,), torch.int64) if p.write_bit_sample_pos else None
+        pos = self._buf(sfx + "pos", (cap_pos,), torch.int64) if (ship_pos or compute_pos) else None
         counts = self._buf(sfx + "counts", (5,), torch.int64)
+
+        def result():
+            """the pass's BitsResult; a pass that computes positions only for its records hands out a descriptor without them (nothing ships them)"""
+            if ship_pos or pos is None:
+                return BitsResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, self.ctx, pipe=self, outputs=o)
+            o_ship = _lib.Outputs()
+            C.memmove(C.byref(o_ship), C.byref(o), C.sizeof(_lib.Outputs))
+            o_ship.pos, o_ship.cap_pos = None, 0
+            r = BitsResult(qad, rows, bits, msg_off, pauses, None, pos_off, counts, p, self.ctx, pipe=self, outputs=o_ship)
+            r._outputs_pos, r._pos_dev = o, pos
+            return r
         o = _lib.Outputs()
         o.qad = qad.data_ptr() if qad is not None else None
         o.rows = rows.data_ptr(); o.cap_rows = cap_rows
@@ -901,7 +1054,7 @@ class DevicePipeline:
                                                       C.c_void_p(nres.data_ptr()), C.c_void_p(nblock.data_ptr()),
                                                       C.c_void_p(d_cres.data_ptr()) if auto_center else None,
                                                       C.c_void_p(cblock.data_ptr()) if auto_center else None, hist_cap))
-            res = BitsResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, self.ctx, pipe=self, outputs=o)
+            res = result()
             res._auto_noise = (nblock, slot)
             if auto_center:
                 res._auto = (cblock, center_max_size, slot)
@@ -925,28 +1078,29 @@ class DevicePipeline:
             _lib.check(lib.urhgpu_iq_to_bits_auto_center_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, C.byref(cp),
                                                              -1 if center_max_size is None else int(center_max_size), C.byref(o),
                                                              C.c_void_p(d_res.data_ptr()), C.c_void_p(block.data_ptr()), hist_cap))
-            res = BitsResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, self.ctx, pipe=self, outputs=o)
+            res = result()
             res._auto = (block, center_max_size, slot)
             return res
         _lib.check(_lib.load().urhgpu_iq_to_bits_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, C.byref(cp), C.byref(o)))
-        return BitsResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, self.ctx, pipe=self, outputs=o)
+        return result()
 
-    def iq_to_bits_checked(self, iq, p: DemodParams, want_qad=True) -> BitsResult:
+    def iq_to_bits_checked(self, iq, p: DemodParams, want_qad=True, msg_records=False, message_length_divisor=1) -> BitsResult:
         """iq_to_bits with the output capacities verified (one 40-byte read-back) and, if the default capacities were
         too small -- a capture that is mostly noise produces far more pulse-table rows than 4 per symbol --, one more
         pass with what the first one reported."""
-        res = self.iq_to_bits(iq, p, want_qad)
+        res = self.iq_to_bits(iq, p, want_qad, msg_records=msg_records, message_length_divisor=message_length_divisor)
         n_rows, n_msg, n_bits, n_pos = res.host_counts()
         need = res._rows_needed
         if need > res.rows_buf.shape[0] or n_msg > res.pauses_buf.shape[0] or n_bits > res.bits_buf.shape[0] \
                 or (res.pos_buf is not None and n_pos > res.pos_buf.shape[0]):
             n = iq.shape[0]
             worst = n // (p.tolerance + 1) + 2
-            res = self.iq_to_bits(iq, p, want_qad, cap_rows=min(worst, max(2 * need, 4096)))
+            res = self.iq_to_bits(iq, p, want_qad, cap_rows=min(worst, max(2 * need, 4096)), msg_records=msg_records,
+                                  message_length_divisor=message_length_divisor)
             res.check_capacity()
         return res
 
-    def qad_to_bits(self, qad, p: DemodParams, cap_rows=None, slot=0) -> BitsResult:
+    def qad_to_bits(self, qad, p: DemodParams, cap_rows=None, slot=0, compute_pos=False) -> BitsResult:
         """grab_pulse_lens + _ppseq_to_bits on an already demodulated signal (float32 (N,) on this device) -- what the reference does
         whenever only slicing parameters changed, and after AutoInterpretation.estimate has demodulated the capture (Signal.qad is
         cached, Signal.py:421-431): 4 B per sample read instead of the IQ stream again.  Outputs as iq_to_bits (qad = the input)."""
@@ -955,6 +1109,9 @@ class DevicePipeline:
             raise ValueError("Buffer dtype mismatch, expected 'float' (grab_pulse_lens takes float[::1])")
         n = int(qad.shape[0])
         cp = p.to_c(np.float32)
+        ship_pos = bool(p.write_bit_sample_pos)
+        if compute_pos:                                      # (positions for a pass's records, whether or not they are shipped)
+            cp.write_bit_sample_pos = 1
         if cap_rows is None:
             cap_rows = n // (p.tolerance + 1) + 2            # exact bound: one pass, no retry (the table is sliced from a resident signal)
         cap_rows, cap_bits, cap_msg, cap_pos = self.capacities(n, p, cap_rows)
@@ -965,7 +1122,7 @@ class DevicePipeline:
         msg_off = self._buf(sfx + "msg_off", (cap_msg + 1,), torch.int64)
         pauses = self._buf(sfx + "pauses", (cap_msg,), torch.int64)
         pos_off = self._buf(sfx + "pos_off", (cap_msg + 1,), torch.int64)
-        pos = self._buf(sfx + "pos", (cap_pos,), torch.int64) if p.write_bit_sample_pos else None
+        pos = self._buf(sfx + "pos", (cap_pos,), torch.int64) if (ship_pos or compute_pos) else None
         counts = self._buf(sfx + "counts", (5,), torch.int64)
         lib = _lib.load()
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
@@ -986,7 +1143,14 @@ class DevicePipeline:
         o.pos_off = pos_off.data_ptr(); o.counts = counts.data_ptr()
         _lib.check(lib.urhgpu_ppseq_to_bits_dev(self.ctx.handle, C.c_void_p(rows.data_ptr()), C.c_void_p(n_rows.data_ptr()), cap_rows, C.byref(cp),
                                                 C.byref(o)))
-        return BitsResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, None, pipe=self, outputs=o)
+        if ship_pos or pos is None:
+            return BitsResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, None, pipe=self, outputs=o)
+        o_ship = _lib.Outputs()
+        C.memmove(C.byref(o_ship), C.byref(o), C.sizeof(_lib.Outputs))
+        o_ship.pos, o_ship.cap_pos = None, 0
+        r = BitsResult(qad, rows, bits, msg_off, pauses, None, pos_off, counts, p, None, pipe=self, outputs=o_ship)
+        r._outputs_pos, r._pos_dev = o, pos
+        return r
 
     def afp_demod(self, iq, p: DemodParams):
         torch = self.torch

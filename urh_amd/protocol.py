@@ -1,13 +1,18 @@
 """Device-resident counterpart of ProtocolAnalyzer.get_protocol_from_signal
 (/root/reference/src/urh/signalprocessing/ProtocolAnalyzer.py:227-321): the O(N) work (demodulation, pulse table, bit
 expansion) is one urhgpu_iq_to_bits_dev pass; what remains per message -- padding ASK messages to a multiple of
-message_length_divisor (:289-321), the RSSI over one symbol at the middle bit (:267-269), the timestamp (:270-272) -- is
-host arithmetic on a few values, with the RSSI samples fetched from the GPU in one gather.
+message_length_divisor (:289-321), the RSSI over one symbol at the middle bit (:267-269), the first bit's position for the
+timestamp (:270-272) -- is queued behind the pass as one record per message (include/urhgpu.h: urhgpu_msg_record), while the
+capture is still in device memory, and applied here with whole-array operations.  messages_from_bits keeps the host route for
+bits that are already on the host.
 """
 import array
 from dataclasses import dataclass
 
 import numpy as np
+
+# struct urhgpu_msg_record (include/urhgpu.h)
+RECORD_DTYPE = np.dtype([("rssi", "<f8"), ("first_pos", "<i8"), ("mid_pos", "<i8"), ("n_pad", "<i4"), ("flag", "<i4")])
 
 
 @dataclass
@@ -34,31 +39,94 @@ def _min_max_for_dtype(dtype):
     return np.iinfo(dtype).min, np.iinfo(dtype).max
 
 
+def padding_counts(n_bits, pauses, samples_per_symbol, divisor):
+    """Zero bits every message borrows from the pause that follows it so that its length becomes a multiple of `divisor`
+    (ProtocolAnalyzer.py:303-307): the bits missing to the next multiple, where the pause holds that many symbols, else 0.
+    n_bits, pauses: one entry per message."""
+    n_bits = np.asarray(n_bits, dtype=np.int64)
+    pauses = np.asarray(pauses, dtype=np.int64)
+    divisor = int(divisor)
+    if divisor <= 1:
+        return np.zeros(len(n_bits), np.int64)
+    missing = (divisor - n_bits % divisor) % divisor
+    return np.where((missing > 0) & (pauses >= int(samples_per_symbol) * missing), missing, 0)
+
+
+def apply_padding(bits, msg_off, pauses, pos, pos_off, n_pad, samples_per_symbol):
+    """The flat outputs of a pass (bits, msg_off, pauses, pos, pos_off as BitsResult.flat() gives them) with message m extended by
+    n_pad[m] zero bits: the bits are appended, the pause shrinks by n_pad * samples_per_symbol, and of the message's positions the last
+    one is replaced and n_pad more follow: .., A, E become .., A, A + sps, .., A + n_pad * sps, A + n_pad * sps + the new pause (A: the
+    start of the closing pause -- or, for a trailing message whose short pause is borrowed from, its last bit's position).
+    Whole-array operations; returns new arrays."""
+    sps = int(samples_per_symbol)
+    n_pad = np.asarray(n_pad, dtype=np.int64)
+    msg_off, pos_off = np.asarray(msg_off, dtype=np.int64), np.asarray(pos_off, dtype=np.int64)
+    pauses, pos, bits = np.asarray(pauses, dtype=np.int64), np.asarray(pos, dtype=np.int64), np.asarray(bits, dtype=np.uint8)
+    if not n_pad.any():
+        return bits, msg_off, pauses, pos, pos_off
+    length, n_entries = np.diff(msg_off), np.diff(pos_off)
+    pos_pad = np.where(n_entries >= 2, n_pad, 0)                         # (a message without two positions has none extended)
+    shift, pos_shift = np.concatenate([[0], np.cumsum(n_pad)]), np.concatenate([[0], np.cumsum(pos_pad)])      # entries inserted in front of each message
+    new_off, new_pos_off = msg_off + shift, pos_off + pos_shift
+    new_bits = np.zeros(int(new_off[-1]), np.uint8)
+    new_bits[np.arange(len(bits)) + np.repeat(shift[:-1], length)] = bits
+    new_pauses = pauses - n_pad * sps
+    new_pos = np.zeros(int(new_pos_off[-1]), np.int64)
+    new_pos[np.arange(len(pos)) + np.repeat(pos_shift[:-1], n_entries)] = pos    # (a padded message's last entry lands on A + sps's place: overwritten below)
+    m = np.nonzero(pos_pad)[0]
+    count = pos_pad[m]
+    start = pos[pos_off[m] + n_entries[m] - 2]                               # A
+    first = new_pos_off[m] + n_entries[m] - 1                                # where A + sps goes
+    step = np.arange(int(count.sum())) - np.repeat(np.cumsum(count) - count, count)
+    new_pos[np.repeat(first, count) + step] = np.repeat(start, count) + (step + 1) * sps
+    new_pos[first + count] = start + count * sps + new_pauses[m]
+    return new_bits, new_off, new_pauses, new_pos, new_pos_off
+
+
 def ensure_message_length_multiple(bit_data, samples_per_symbol, pauses, bit_sample_pos, divisor):
-    """ProtocolAnalyzer.__ensure_message_length_multiple (:289-321): ASK messages borrow zero bits from the pause
-    that follows them so that their length becomes a multiple of `divisor`."""
-    for i in range(len(bit_data)):
-        missing_bits = (divisor - (len(bit_data[i]) % divisor)) % divisor
-        if missing_bits > 0 and pauses[i] >= samples_per_symbol * missing_bits:
-            bit_data[i].extend([0] * missing_bits)
-            pauses[i] = pauses[i] - missing_bits * samples_per_symbol
-            try:
-                bit_sample_pos[i][-1] = bit_sample_pos[i][-2] + samples_per_symbol
-            except IndexError:
-                continue
-            bit_sample_pos[i].extend([bit_sample_pos[i][-1] + (k + 1) * samples_per_symbol for k in range(missing_bits - 1)])
-            bit_sample_pos[i].append(bit_sample_pos[i][-1] + pauses[i])
+    """ASK messages borrow zero bits from the pause that follows them so that their length becomes a multiple of `divisor`
+    (what ProtocolAnalyzer.__ensure_message_length_multiple does, :289-321), in place on the reference-shaped lists:
+    padding_counts decides, apply_padding extends."""
+    n_msg = len(bit_data)
+    n_pad = padding_counts([len(b) for b in bit_data], list(pauses), samples_per_symbol, divisor)
+    if n_msg == 0 or not n_pad.any() or len(bit_sample_pos) != n_msg:
+        for i in np.nonzero(n_pad)[0].tolist():                                 # (no positions to extend: bits and pauses alone)
+            bit_data[i].extend([0] * int(n_pad[i]))
+            pauses[i] = pauses[i] - int(n_pad[i]) * int(samples_per_symbol)
+        return
+    msg_off = np.concatenate([[0], np.cumsum([len(b) for b in bit_data])])
+    pos_off = np.concatenate([[0], np.cumsum([len(q) for q in bit_sample_pos])])
+    flat_pos = np.concatenate([np.asarray(q, dtype=np.int64) for q in bit_sample_pos])
+    _, _, new_pauses, new_pos, new_pos_off = apply_padding(np.zeros(int(msg_off[-1]), np.uint8), msg_off, pauses, flat_pos, pos_off, n_pad,
+                                                           samples_per_symbol)
+    for i in np.nonzero(n_pad)[0].tolist():
+        bit_data[i].extend([0] * int(n_pad[i]))
+        pauses[i] = int(new_pauses[i])
+        bit_sample_pos[i] = array.array("L", new_pos[new_pos_off[i]:new_pos_off[i + 1]].tolist())
+
+
+def messages_from_records(flat, records, p, sample_rate=1e6, timestamp=0.0):
+    """The list of MessageData from a pass's flat outputs (bits, msg_off, pauses, pos, pos_off) and its records
+    (RECORD_DTYPE, one per message): padding applied on whole arrays, RSSI and first position taken from the records."""
+    sps, bps = int(p.samples_per_symbol), int(p.bits_per_symbol)
+    bits, off, pauses, pos, poff = apply_padding(*flat, records["n_pad"], sps)
+    out = []
+    for i in range(len(pauses)):
+        out.append(MessageData(array.array("B", bits[off[i]:off[i + 1]].tobytes()), int(pauses[i]),
+                               array.array("L", pos[poff[i]:poff[i + 1]].tolist()), float(records["rssi"][i]),
+                               timestamp + int(records["first_pos"][i]) / sample_rate, sps, bps))
+    return out
 
 
 def get_protocol_from_signal_dev(pipe, iq, p, message_length_divisor=1, sample_rate=1e6, timestamp=0.0):
     """iq: capture on the GPU ((N, 2) tensor of a supported dtype or complex64 (N,)); p: pipeline.DemodParams.
-    Returns the list of MessageData the reference would build its Message objects from."""
+    Returns the list of MessageData the reference would build its Message objects from: one pass with its records queued
+    behind it, one hand-out."""
     torch = pipe.torch
     if iq.dtype == torch.complex64:
         iq = torch.view_as_real(iq)
-    res = pipe.iq_to_bits_checked(iq, p, want_qad=True)
-    bit_data, pauses, bit_sample_pos = res.messages()
-    return messages_from_bits(pipe, iq, p, bit_data, pauses, bit_sample_pos, message_length_divisor, sample_rate, timestamp)
+    res = pipe.iq_to_bits_checked(iq, p, want_qad=True, msg_records=True, message_length_divisor=message_length_divisor)
+    return res.message_data(sample_rate, timestamp)
 
 
 def messages_from_bits(pipe, iq, p, bit_data, pauses, bit_sample_pos, message_length_divisor=1, sample_rate=1e6, timestamp=0.0):

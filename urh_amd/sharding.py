@@ -706,7 +706,8 @@ class ShardedPipeline:
             total[b0:b1] = c.all_gather(local[b0:b1]).cpu().numpy().reshape(self.world, -1).sum(axis=0)
         return peaks_center(total, edges)
 
-    def iq_to_bits(self, iq_local, p, want_qad=True, pos_base=None, n_total=None, halo_given=False, left_halo=None, left_raw=None, auto_center=False):
+    def iq_to_bits(self, iq_local, p, want_qad=True, pos_base=None, n_total=None, halo_given=False, left_halo=None, left_raw=None, auto_center=False,
+                   msg_records=False):
         """iq_local: this rank's shard.  pos_base / n_total default to equal shards of len(iq_local).
         halo_given (the same on every rank): whoever distributed the capture handed every rank but the first the two samples that
         precede its shard (left_halo: (2, 2) in the shard's dtype, or complex64 (2,)) -- 16 bytes more per rank to read from the
@@ -718,8 +719,12 @@ class ShardedPipeline:
         Costas exchange has written it and builds its pulse table with the detected center (p.center where detection gives None);
         `last_center` is the value used.  ASK / FSK raise ValueError: their fused hot kernel needs the center before the demodulated
         signal exists.  The recipe there is two passes: one with want_qad=True, `detect_center(result.qad)`, then a second pass with
-        that center."""
+        that center.
+        msg_records: refused (ValueError) -- a message's middle window may lie in another rank's shard; the records belong to single-GPU passes
+        (DevicePipeline.iq_to_bits, CaptureStream)."""
         e, c = self.engine, self.comm
+        if msg_records:
+            raise ValueError("message records are not available for sharded passes: run DevicePipeline.iq_to_bits(msg_records=True) on one GPU")
         if auto_center and p.modulation_type != "PSK":
             raise ValueError("auto_center needs a PSK pass: for ASK / FSK run a pass with want_qad=True, detect_center(result.qad), "
                              "then a second pass with that center")

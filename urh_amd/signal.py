@@ -298,6 +298,8 @@ class Signal:
         self._qad = None
         self._bits = None
         self._bits_key = None
+        self._records = None
+        self._records_key = None
         # the digitisations' views of the pinned host buffers go with the cache (a digitisation somebody still holds is widened first); the
         # buffers themselves stay -- a noise threshold dragged through its range in the GUI lands here on every change, and pinning memory
         # again each time is a hipHostMalloc per change -- and are released with the samples (eliminate)
@@ -522,10 +524,24 @@ class Signal:
 
     def get_protocol(self):
         """ProtocolAnalyzer.get_protocol_from_signal (:227-287): MessageData per message (bits, pause, RSSI, timestamp, positions)."""
-        from .protocol import messages_from_bits
-        data, pauses, bsp = self.bits()
-        return messages_from_bits(self.pipe, self._iq, self.params(), data, pauses, bsp, int(self.message_length_divisor),
-                                  self.sample_rate, self.timestamp)
+        from .protocol import messages_from_bits, messages_from_records
+        divisor = max(1, int(self.message_length_divisor))
+        p = self.params()
+        q = self.qad
+        if int(q.shape[0]) == 0 or q.dtype != self.pipe.torch.float32:        # (nothing to slice / the reference's own error: the host route)
+            data, pauses, bsp = self.bits()
+            return messages_from_bits(self.pipe, self._iq, p, data, pauses, bsp, divisor, self.sample_rate, self.timestamp)
+        key = (self._slice_key(), divisor)
+        if self.__dict__.get("_records") is None or self._records_key != key:
+            # one slicing pass over the cached demodulated signal with the records queued behind it (the capture is resident), one hand-out;
+            # kept until a parameter or the samples change: a repeated call does no device work
+            res = self.pipe.qad_to_bits(q, p, slot=7)
+            res._rec = self.pipe._queue_records(self._iq, p, res._outputs_pos, divisor, 7) + (self._iq, divisor, 7)
+            rec = res.records.copy()
+            res.check_capacity()
+            self._records, self._records_key = (res._flat(True), rec), key
+        flat, rec = self._records
+        return messages_from_records(flat, rec, p, self.sample_rate, self.timestamp)
 
     # ---- parameter estimation -----------------------------------------------------------------------------------------------
     def auto_detect(self, detect_modulation=True, detect_noise=False) -> bool:
@@ -559,6 +575,8 @@ class Signal:
     def _after_edit(self):
         self._bits = None
         self._bits_key = None
+        self._records = None
+        self._records_key = None
         self.changed = True
 
     def insert_data(self, index: int, data):
