@@ -976,6 +976,28 @@ int urhgpu_stream_msg_records(urhgpu_stream *st, int64_t seq, const urhgpu_msg_r
  * host wait for the device: the counter of urhgpu_test_center_host_syncs, kept separately for these entry points. */
 int64_t urhgpu_test_records_host_syncs(void);
 
+/* ---- DC correction: out = x - mean(x, axis 0), the reference's Filter type dc_correction and its receive path's per-chunk correction ----
+ * (Filter.py:31-35, Device.py:822-823).  Bit-equal with numpy's expression for every input:
+ *   float32   the mean of a column is numpy's strictly sequential float32 sum from +0.0 (s = fl32(s + x[i]), i = 0 .. n-1), divided in
+ *             float64 by n and rounded to float32; the subtraction is float32.  The sum is evaluated in chunks of 4096 samples that are
+ *             speculated from a float64 guess and stitched exactly (translated where the proof allows it, re-evaluated serially where not);
+ *             captures of at most 8192 samples are summed directly by one wavefront.
+ *   integers  the mean is double(exact int64 sum) / double(n); out = (T)(int32) trunc(double(x) - mean): truncated toward zero, low bits kept.
+ * Asynchronous on the context's stream, no host wait (but the first call, and a call with a larger n than any before, allocates scratch).
+ * d_in, d_out: device, aligned to one sample (2 x the component size); d_out == d_in is allowed, any other overlap is not.  The mean is
+ * complete before the subtraction starts.  d_mean: optional, device, 8-byte aligned: the two means, float32 pair for URHGPU_DT_F32, float64
+ * pair otherwise.  n == 0: nothing is done.  The calls of one context share one scratch area: they are ordered among themselves. */
+int urhgpu_dc_correct_dev(urhgpu_ctx *ctx, const void *d_in, int64_t n, int dtype, void *d_out, void *d_mean);
+/* The same on host buffers (h_mean: optional, two float32 or two float64 as above); returns when h_out is complete. */
+int urhgpu_dc_correct(urhgpu_ctx *ctx, const void *h_in, int64_t n, int dtype, void *h_out, void *h_mean);
+/* how often urhgpu_dc_correct_dev made the host wait for the device (a scratch area that had to grow: freeing the old one waits) */
+int64_t urhgpu_test_dc_host_syncs(void);
+/* The last float32 call of the context, read back after waiting for the context's stream.  stats[0]: chunks per column (0: the capture
+ * was summed directly); stats[1]: chunks (both columns) whose exit followed from the speculated one -- entered exactly as guessed, or
+ * translated by the difference of the entries, or entered with a NaN sum --; stats[2]: chunks re-evaluated serially from their true entry;
+ * stats[3]: the part of stats[1] that was entered exactly as guessed. */
+int urhgpu_test_dc_stats(urhgpu_ctx *ctx, int64_t *stats);
+
 #ifdef __cplusplus
 }
 #endif

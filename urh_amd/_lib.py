@@ -215,6 +215,10 @@ PROTOTYPES = {
     "urhgpu_chunk_stats_launches": (_i, [_vp, C.POINTER(_i64)]),
     "urhgpu_magnitude_chunk_partials_dev": (_i, [_vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
     "urhgpu_pairwise_partial_f32_dev": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _f, _vp, _i64, C.POINTER(_i64)]),
+    "urhgpu_dc_correct_dev": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    "urhgpu_dc_correct": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    "urhgpu_test_dc_host_syncs": (_i64, []),
+    "urhgpu_test_dc_stats": (_i, [_vp, C.POINTER(_i64)]),
 }
 
 _lib = None

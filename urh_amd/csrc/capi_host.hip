@@ -293,4 +293,23 @@ int urhgpu_median_filter(urhgpu_ctx *ctx, const double *data, int64_t n, unsigne
     return URHGPU_OK;
 }
 
+int urhgpu_dc_correct(urhgpu_ctx *ctx, const void *h_in, int64_t n, int dtype, void *h_out, void *h_mean) {
+    if (!ctx || n < 0 || (n > 0 && (!h_in || !h_out))) return URHGPU_ERR_ARG;
+    const int sb = dtype_bytes(dtype);
+    if (sb == 0) return URHGPU_ERR_DTYPE;
+    if (n == 0) return URHGPU_OK;
+    URH_HIP(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n * sb, mean_bytes = dtype == URHGPU_DT_F32 ? 8 : 16;
+    URH_TRY(ctx->staging.reserve(2 * align256(bytes) + 1024));
+    ctx->staging.reset();
+    void *d_in = nullptr;
+    URH_TRY(stage_in(ctx, h_in, bytes, &d_in));
+    void *d_out = ctx->staging.take(bytes), *d_mean = ctx->staging.take(16);
+    if (!d_out || !d_mean) return URHGPU_ERR_ARG;
+    URH_TRY(urhgpu_dc_correct_dev(ctx, d_in, n, dtype, d_out, d_mean));
+    if (h_mean) URH_HIP(hipMemcpyAsync(h_mean, d_mean, mean_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    URH_TRY(fetch_out(ctx, h_out, d_out, bytes));
+    return URHGPU_OK;
+}
+
 }  // extern "C"

@@ -183,6 +183,12 @@ struct urhgpu_ctx {
     // back to it (hot_launch), so the one scratch serves passes that overlap further down.
     void *d_noise_work = nullptr;
     int wide_int_auto = 0;                 // the next urhgpu_iq_to_bits_auto_dev pass takes the wide-loop instantiation (a capture stream's probe said so)
+    // urhgpu_dc_correct_dev (dc_correct.hip): means, partial sums, and a float32 capture's chunk sums, guesses and speculation records.  Its
+    // own, so that a correction queued beside a pipelined pass's tail touches none of the rotating arenas; calls on another stream than the
+    // last one's wait for that one first (ev_dc), as the FIR's do.
+    urh::Arena dc_work;
+    hipEvent_t ev_dc = nullptr;
+    hipStream_t dc_stream = nullptr;
 };
 constexpr size_t kSegBlockBytes = 4096;      // 16 progress counters on their own 128-byte lines, then the SegState
 

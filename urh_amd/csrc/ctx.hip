@@ -128,6 +128,8 @@ int urhgpu_ctx_destroy(urhgpu_ctx *ctx) {
     ctx->fir_work.release();
     ctx->chunk_work.release();
     ctx->center_work.release();
+    ctx->dc_work.release();
+    if (ctx->ev_dc) (void)hipEventDestroy(ctx->ev_dc);
     if (ctx->ev_center) (void)hipEventDestroy(ctx->ev_center);
     if (ctx->h_chunk) (void)hipHostFree(ctx->h_chunk);
     if (ctx->ev_fir) (void)hipEventDestroy(ctx->ev_fir);

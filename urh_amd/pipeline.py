@@ -646,8 +646,12 @@ class CaptureStream:
     and the D2H copy of pass i - 2's compact blob overlap."""
 
     def __init__(self, pipe: "DevicePipeline", n_max: int, p: DemodParams, want_qad=True, want_pos=True, dtype=np.float32, cap_rows=0, latency=None,
-                 auto_center=False, center_max_size=None, auto_noise=False, msg_records=False, message_length_divisor=1):
-        """msg_records: every pass ends with one record per message (urhgpu_stream_set_msg_records: ASK padding to message_length_divisor,
+                 auto_center=False, center_max_size=None, auto_noise=False, msg_records=False, message_length_divisor=1, dc_correction=False):
+        """dc_correction: every pushed capture minus its own mean (filter.dc_correct_dev: the reference's Filter type dc_correction, bit-equal
+        with numpy's expression), queued in front of its pass into one of four buffers of n_max samples the stream owns and rotates -- a
+        pass is handed out three pushes later, so its buffer is rewritten only behind its hand-out.  The pass, its records included, reads the
+        corrected capture; the caller's tensor is not modified and no push waits for the device.  Not for push_upload.
+        msg_records: every pass ends with one record per message (urhgpu_stream_set_msg_records: ASK padding to message_length_divisor,
         first and middle position, RSSI), computed behind its tail while the capture is in device memory; every HostBits handed out carries
         .records and .message_data(sample_rate, timestamp) -- also with want_pos=False, where the positions are derived on demand as
         HostBits.bit_sample_pos() does.  A pushed capture must stay unchanged until its result has been handed out, and may be overwritten
@@ -695,6 +699,13 @@ class CaptureStream:
         # the captures of the passes that may still be running (three are in flight at most): a caller's temporary -- a pinned host buffer
         # under the DMA of push_upload in particular, which no allocator knows to be in use -- lives until its pass has been handed out
         self._inflight = []
+        self._dc_bufs = None
+        if dc_correction:
+            from .filter import dc_correct_dev
+            torch = pipe.torch
+            tdt = getattr(torch, self._dtype.name)                # (the five sample types carry numpy's names)
+            self._dc_bufs = [torch.zeros((int(n_max), 2), dtype=tdt, device=pipe.device) for _ in range(4)]
+            dc_correct_dev(pipe, self._dc_bufs[0], out=self._dc_bufs[1])      # the correction's scratch for n_max samples is allocated here, not in a push
 
     def _hold(self, *tensors):
         self._inflight.append(tensors)
@@ -729,6 +740,11 @@ class CaptureStream:
             iq = torch.view_as_real(iq)
         if _torch_dtype(iq) != self._dtype or not iq.is_contiguous():
             raise ValueError("the stream was created for contiguous (N, 2) captures of " + str(self._dtype))
+        if self._dc_bufs is not None:
+            from .filter import dc_correct_dev
+            if iq.shape[0] > self._dc_bufs[0].shape[0]:
+                raise ValueError("the capture is longer than the stream's n_max")
+            iq = dc_correct_dev(self.pipe, iq, out=self._dc_bufs[self._pushed % 4][:iq.shape[0]])
         r = _lib.HostResult()
         self.pipe.ctx.set_stream(torch.cuda.current_stream(self.pipe.device).cuda_stream)
         _lib.check(_lib.load().urhgpu_stream_push(self._h, C.c_void_p(iq.data_ptr()), int(iq.shape[0]), C.byref(r)))
@@ -810,6 +826,8 @@ class CaptureStream:
         resident there, e.g. as a Signal's data) piece by piece, and every piece is demodulated as it lands.  A stream with msg_records,
         auto_noise or auto_center uploads in ONE copy in front of an ordinary pass instead.  Returns like push()."""
         torch = self.pipe.torch
+        if self._dc_bufs is not None:
+            raise ValueError("push_upload demodulates the pieces as they land: a stream with dc_correction takes push() of a device capture")
         if isinstance(host_iq, np.ndarray):
             host_iq = torch.from_numpy(host_iq)
         if host_iq.dtype == torch.complex64:
@@ -861,6 +879,7 @@ class CaptureStream:
             self._h = None
             self._inflight = []
             self._captures = {}
+            self._dc_bufs = None
 
     def __del__(self):
         try:
@@ -930,10 +949,10 @@ class DevicePipeline:
         self.ctx.reserve(n, p.tolerance)
 
     def stream(self, n_max: int, p: DemodParams, want_qad=True, want_pos=True, dtype=np.float32, cap_rows=0, latency=None, auto_center=False,
-               center_max_size=None, auto_noise=False, msg_records=False, message_length_divisor=1) -> CaptureStream:
+               center_max_size=None, auto_noise=False, msg_records=False, message_length_divisor=1, dc_correction=False) -> CaptureStream:
         """a CaptureStream on this pipeline's context (which it switches to pipelined passes)"""
         return CaptureStream(self, n_max, p, want_qad, want_pos, dtype, cap_rows, latency, auto_center, center_max_size, auto_noise, msg_records,
-                             message_length_divisor)
+                             message_length_divisor, dc_correction)
 
     def _queue_records(self, iq, p: DemodParams, o, divisor, slot):
         """urhgpu_msg_records_dev behind the pass that filled the descriptor o (with positions): one record per message into a device block
@@ -955,9 +974,12 @@ class DevicePipeline:
         return block, cap
 
     def iq_to_bits(self, iq, p: DemodParams, want_qad=True, cap_rows=None, slot=0, auto_center=False, center_max_size=None, auto_noise=False,
-                   msg_records=False, message_length_divisor=1) -> BitsResult:
+                   msg_records=False, message_length_divisor=1, dc_correction=False) -> BitsResult:
         """iq: torch tensor on this device, shape (N, 2) of int8/uint8/int16/uint16/float32, or complex64 (N,).
         The result lives in buffers owned by the pipeline and is overwritten by the next pass with the same `slot`.
+        dc_correction: the pass runs over the capture minus its own mean (filter.dc_correct_dev), queued into a buffer of the pipeline's
+        (one per slot, rewritten by the next such pass of the slot, behind the tail of the last pass); iq itself is not modified, there is
+        no host wait, and everything below -- auto_noise, auto_center, the records -- reads the corrected capture.
         auto_center: the pass detects the center of its own demodulated signal (AutoInterpretation.detect_center with
         max_size=center_max_size, as ProtocolSniffer does per flush) and slices with it, all of it queued on the device
         (urhgpu_iq_to_bits_auto_center_dev); BitsResult.center / .center_flag tell what it found.  Where the device leaves the decision
@@ -972,6 +994,12 @@ class DevicePipeline:
         middle position, RSSI), queued behind its tail while the capture is in device memory; BitsResult.records / .message_data() hand
         them out.  The positions are then computed whether or not p.write_bit_sample_pos ships them.  iq must stay unchanged until the
         result has been read."""
+        if dc_correction:
+            from .filter import dc_correct_dev
+            if iq.dtype == self.torch.complex64:
+                iq = self.torch.view_as_real(iq)
+            self.ctx.join()                                   # (the buffer may still be read by the tail of the slot's last pass: the stream waits, not the host)
+            iq = dc_correct_dev(self, iq, out=self._buf(("dc", slot), tuple(iq.shape), iq.dtype))
         res = self._iq_to_bits(iq, p, want_qad, cap_rows, slot, auto_center, center_max_size, auto_noise, bool(msg_records))
         if msg_records:
             if int(message_length_divisor) < 1:

@@ -707,7 +707,7 @@ class ShardedPipeline:
         return peaks_center(total, edges)
 
     def iq_to_bits(self, iq_local, p, want_qad=True, pos_base=None, n_total=None, halo_given=False, left_halo=None, left_raw=None, auto_center=False,
-                   msg_records=False):
+                   msg_records=False, dc_correction=False):
         """iq_local: this rank's shard.  pos_base / n_total default to equal shards of len(iq_local).
         halo_given (the same on every rank): whoever distributed the capture handed every rank but the first the two samples that
         precede its shard (left_halo: (2, 2) in the shard's dtype, or complex64 (2,)) -- 16 bytes more per rank to read from the
@@ -721,8 +721,12 @@ class ShardedPipeline:
         signal exists.  The recipe there is two passes: one with want_qad=True, `detect_center(result.qad)`, then a second pass with
         that center.
         msg_records: refused (ValueError) -- a message's middle window may lie in another rank's shard; the records belong to single-GPU passes
-        (DevicePipeline.iq_to_bits, CaptureStream)."""
+        (DevicePipeline.iq_to_bits, CaptureStream).
+        dc_correction: refused (ValueError) -- the mean is the sequential float32 sum of the WHOLE capture; correct it on one GPU
+        (filter.dc_correct_dev) before it is distributed."""
         e, c = self.engine, self.comm
+        if dc_correction:
+            raise ValueError("DC correction is not available for sharded passes: correct the capture on one GPU (filter.dc_correct_dev) first")
         if msg_records:
             raise ValueError("message records are not available for sharded passes: run DevicePipeline.iq_to_bits(msg_records=True) on one GPU")
         if auto_center and p.modulation_type != "PSK":

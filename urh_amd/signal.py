@@ -609,16 +609,25 @@ class Signal:
         self._after_edit()
 
     def filter_range(self, start: int, end: int, taps):
-        """Signal.filter_range (:645-655) with Filter.work's FIR branch (Filter.py:31-46): the range is filtered on its own (zero
-        history), written back in the capture's sample type, and qad[start:end] becomes afp_demod of the filtered range ALONE
-        (so its first sample is the NOISE value, as in the reference)."""
+        """Signal.filter_range (:645-655) with Filter.work (Filter.py:31-46): the range is filtered on its own (zero history),
+        written back in the capture's sample type, and qad[start:end] becomes afp_demod of the filtered range ALONE
+        (so its first sample is the NOISE value, as in the reference).  taps: bare FIR taps or a filter.Filter; its DC-correction
+        type subtracts the mean of the range alone (urhgpu_dc_correct_dev, in the capture's sample type)."""
         import ctypes as C
+        from .filter import Filter, FilterType, dc_correct_dev
         torch = self.pipe.torch
         _ = self.qad                                  # the reference indexes self._qad: it must exist
         seg = self._iq[start:end]
         n = int(seg.shape[0])
         if n == 0:
             return
+        if isinstance(taps, Filter):
+            if taps.filter_type == FilterType.dc_correction:
+                dc_correct_dev(self.pipe, seg, out=seg)               # in place: a range starts on a sample, which is all the kernels ask
+                return self._redemodulate_range(start, end)
+            if taps.filter_type not in (FilterType.moving_average, FilterType.custom):
+                raise ValueError("Unsupported FilterType")
+            taps = taps.taps
         # the RAW sample values as float32 (Filter.apply_fir_filter, Filter.py:37-41: no IQArray scaling), filtered, and written
         # back with numpy's truncating cast (IQArray.__setitem__, IQArray.py:31-33)
         from .iq_array import astype
@@ -632,6 +641,9 @@ class Signal:
         if seg.dtype != torch.float32:
             y = astype(y, self.dtype, self.pipe.ctx)
         self._iq[start:end] = y
+        self._redemodulate_range(start, end)
+
+    def _redemodulate_range(self, start: int, end: int):
         if self._qad.shape[0] == self.num_samples:        # (a zeros(2) cache cannot take the range: the reference raises there too)
             self.demod_passes += 1
             self._qad[start:end] = self.pipe.afp_demod(self._iq[start:end].clone(), self.params())

@@ -64,8 +64,9 @@ class SniffedMessage:
 class GpuSniffEngine:
     """Device-resident accumulation buffer + the per-chunk pass + the flush, on a DevicePipeline."""
 
-    def __init__(self, pipe, dtype=np.float32, buffer_samples=DEFAULT_BUFFER_SAMPLES):
+    def __init__(self, pipe, dtype=np.float32, buffer_samples=DEFAULT_BUFFER_SAMPLES, apply_dc_correction=False):
         import torch
+        self.apply_dc_correction = bool(apply_dc_correction)   # every chunk minus its own mean before anything else sees it (Device.py:822-823)
         self.torch = torch
         self.pipe = pipe
         self.dtype = np.dtype(dtype)
@@ -83,6 +84,8 @@ class GpuSniffEngine:
         n = int(chunk.shape[0])
         store = max(trimmed_rows(n, index, self.buffer_len), 0)
         dst = self.buffer[index:index + store]
+        if self.apply_dc_correction:
+            chunk = self._dc_corrected(chunk)                  # a device tensor of the engine's: the caller's chunk is left as it is
         if isinstance(chunk, np.ndarray):
             if chunk.dtype != self.dtype or chunk.ndim != 2 or chunk.shape[1] != 2:
                 raise ValueError(f"chunk must be an (n, 2) array of {self.dtype}")
@@ -109,6 +112,23 @@ class GpuSniffEngine:
         if self.dtype == np.float32:
             return np.float32(self._sum.value), np.float32(self._max.value)     # float32 values, widened exactly by the library
         return np.float64(self._sum.value), np.float64(self._max.value)
+
+    def _dc_corrected(self, chunk):
+        """the chunk minus its mean (urhgpu_dc_correct_dev, queued in front of the statistics pass), in the engine's spill rows"""
+        from .filter import dc_correct_dev
+        torch = self.torch
+        n = int(chunk.shape[0])
+        if self._spill is None or self._spill.shape[0] < n:
+            self._spill = torch.empty((n, 2), dtype=self.tdtype, device=self.pipe.device)
+        rows = self._spill[:n]
+        if isinstance(chunk, np.ndarray):
+            if chunk.dtype != self.dtype or chunk.ndim != 2 or chunk.shape[1] != 2:
+                raise ValueError(f"chunk must be an (n, 2) array of {self.dtype}")
+            rows.copy_(torch.from_numpy(np.ascontiguousarray(chunk)), non_blocking=True)
+            return dc_correct_dev(self.pipe, rows, out=rows)
+        if chunk.dtype != self.tdtype or chunk.dim() != 2 or chunk.shape[1] != 2 or not chunk.is_contiguous() or chunk.device != self.buffer.device:
+            raise ValueError(f"chunk must be a contiguous (n, 2) tensor of {self.tdtype} on {self.buffer.device}")
+        return dc_correct_dev(self.pipe, chunk, out=rows)
 
     def launches(self) -> int:
         """kernel launches the per-chunk pass has issued so far (two per chunk, whatever its length)"""
@@ -150,14 +170,18 @@ class LiveSniffer:
     """feed(chunk) is ProtocolSniffer.__demodulate_data(data): it returns the messages that chunk completed (usually none)."""
 
     def __init__(self, pipe, params, dtype=np.float32, sample_rate=1e6, adaptive_noise=False, automatic_center=False,
-                 buffer_samples=DEFAULT_BUFFER_SAMPLES, clock=time.time, engine=None, trace=False):
+                 buffer_samples=DEFAULT_BUFFER_SAMPLES, clock=time.time, engine=None, trace=False, apply_dc_correction=False):
+        """apply_dc_correction: every fed chunk minus its own mean, on the device, before it is appended and its gate statistics are taken
+        -- the reference's receive path in front of the sniffer (Device.py:822-823, on by default there).  Off: the chunks as they are fed."""
         self.params = params
         self.dtype = np.dtype(dtype)
         self.sample_rate = sample_rate
         self.adaptive_noise = adaptive_noise
         self.automatic_center = automatic_center
         self.clock = clock
-        self.engine = engine if engine is not None else GpuSniffEngine(pipe, self.dtype, buffer_samples)
+        if engine is not None and apply_dc_correction and not getattr(engine, "apply_dc_correction", False):
+            raise ValueError("apply_dc_correction with an engine of the caller's: the engine must correct its chunks itself")
+        self.engine = engine if engine is not None else GpuSniffEngine(pipe, self.dtype, buffer_samples, apply_dc_correction)
         self.buffer_len = int(buffer_samples)
         self.noise_threshold = params.noise_threshold       # a Python float until the first adaptive update (see feed)
         self.center = params.center
