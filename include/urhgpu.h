@@ -998,6 +998,37 @@ int64_t urhgpu_test_dc_host_syncs(void);
  * stats[3]: the part of stats[1] that was entered exactly as guessed. */
 int urhgpu_test_dc_stats(urhgpu_ctx *ctx, int64_t *stats);
 
+/* ---- DC correction of a sharded capture (urh_amd/sharding.py, "DC correction") ----
+ * Rank r holds n samples of one capture; the mean is the whole capture's.  All four calls are asynchronous on the context's stream, share the
+ * scratch area of urhgpu_dc_correct_dev (the calls of one context are ordered among themselves) and take a shard aligned to one sample, n >= 0
+ * (d_in may be NULL where n == 0).
+ *
+ * sums: d_words (device, 3 x 8 bytes) = {n, sum of column I, sum of column Q}: exact int64 sums for the integer types; for URHGPU_DT_F32 the bits
+ * of two float64 sums (the sums of the shard's 4096-sample chunks, added in order) -- guesses of what the shard adds to the float32 recurrence. */
+int urhgpu_shard_dc_sums_dev(urhgpu_ctx *ctx, const void *d_in, int64_t n, int dtype, void *d_words);
+/* float32 only.  Speculates the shard's chunks from fl32(base[col] + the float64 sum of the chunks in front) and from that value's neighbour
+ * one ulp further from zero, as urhgpu_dc_correct_dev does, and stitches the shard from two entries per column: fl32(base[col]) and its
+ * neighbour.  base: host, two doubles (the float64 sums of the ranks in front).  d_records (device, 16-byte aligned, URHGPU_DC_RECORD_BYTES):
+ * [column][path] x four uint32 {entry bits, exit bits, room, flags}: the shard entered with `entry` leaves with `exit`; entered D ulps from it,
+ * D even, same sign, |D| <= room, it leaves D ulps from `exit`.  room is the minimum over the chunks of m - 1 - |d| (a chunk derived from a
+ * record whose path stays m ulps inside its binade, entered d ulps from that record's entry), 0 where a chunk was re-evaluated serially, was
+ * taken by exact hit from a record that cannot be translated, or was entered with a NaN sum.  flags bit 0: n == 0, the exit is the entry.  The
+ * chunk records stay in the scratch area for urhgpu_shard_dc_resolve_dev. */
+#define URHGPU_DC_RECORD_BYTES 64
+int urhgpu_shard_dc_spec_dev(urhgpu_ctx *ctx, const void *d_in, int64_t n, const double *base, void *d_records);
+/* float32 only.  The shard last given to urhgpu_shard_dc_spec_dev on this context (the same d_in and n; anything else, or another DC call that
+ * used the chunk area in between, is URHGPU_ERR_ARG) stitched from its true entry: entry (host) = the bits of the two column sums in front of
+ * the shard; d_exit (device, 2 x uint32) = the bits of the two sums behind it.  One wavefront over the chunk records; chunks they do not give
+ * are re-evaluated serially. */
+int urhgpu_shard_dc_resolve_dev(urhgpu_ctx *ctx, const void *d_in, int64_t n, const uint32_t *entry, void *d_exit);
+/* d_out = d_in - mean in the sample type, the subtraction of urhgpu_dc_correct_dev with a mean given by the caller: mean (host) = two float32 for
+ * URHGPU_DT_F32, two float64 otherwise.  d_out == d_in is allowed, any other overlap is not. */
+int urhgpu_shard_dc_apply_dev(urhgpu_ctx *ctx, const void *d_in, int64_t n, int dtype, const void *mean, void *d_out);
+/* The last urhgpu_shard_dc_spec_dev of the context and the urhgpu_shard_dc_resolve_dev that followed it (zeros: none), read back after waiting for
+ * the context's stream.  stats[0..3]: chunks per column, chunks derived from their records and chunks re-evaluated serially over all stitched
+ * paths, paths per column; stats[4..7]: the same for the resolve. */
+int urhgpu_shard_dc_stats(urhgpu_ctx *ctx, int64_t *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,11 @@ PROTOTYPES = {
     "urhgpu_dc_correct": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "urhgpu_test_dc_host_syncs": (_i64, []),
     "urhgpu_test_dc_stats": (_i, [_vp, C.POINTER(_i64)]),
+    "urhgpu_shard_dc_sums_dev": (_i, [_vp, _vp, _i64, _i, _vp]),
+    "urhgpu_shard_dc_spec_dev": (_i, [_vp, _vp, _i64, C.POINTER(C.c_double), _vp]),
+    "urhgpu_shard_dc_resolve_dev": (_i, [_vp, _vp, _i64, C.POINTER(C.c_uint32), _vp]),
+    "urhgpu_shard_dc_apply_dev": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    "urhgpu_shard_dc_stats": (_i, [_vp, C.POINTER(_i64)]),
 }
 
 _lib = None

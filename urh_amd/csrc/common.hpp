@@ -189,6 +189,8 @@ struct urhgpu_ctx {
     urh::Arena dc_work;
     hipEvent_t ev_dc = nullptr;
     hipStream_t dc_stream = nullptr;
+    const void *dc_shard_in = nullptr;     // the shard whose chunk records urhgpu_shard_dc_spec_dev left in dc_work (urhgpu_shard_dc_resolve_dev takes no other)
+    int64_t dc_shard_n = -1;
 };
 constexpr size_t kSegBlockBytes = 4096;      // 16 progress counters on their own 128-byte lines, then the SegState
 

@@ -380,6 +380,95 @@ class GpuShardEngine(DevicePipeline):
         counts._urh_keep = (x, d_edges)
         return counts
 
+    # ---- DC correction across the shards (sharding.py: dc_correct; csrc/dc_correct.hip, "sharded captures") ----
+    def _dc_rows(self, t, what):
+        """(n, 2) view of a tensor of a sample type or complex64 (n,), and its dtype code"""
+        from .filter import _TORCH_CODES
+        torch = self.torch
+        x = torch.view_as_real(t) if t.dtype == torch.complex64 else t
+        code = _TORCH_CODES.get(str(x.dtype))
+        if code is None:
+            raise ValueError(f"{what}: Unsupported dtype {x.dtype}")
+        if x.dim() != 2 or x.shape[1] != 2:
+            raise ValueError(f"{what}: an (n, 2) tensor of a sample type or complex64 (n,)")
+        return x, code
+
+    def dc_own(self, iq_local, also, out):
+        """everything a rank can get wrong about the arguments of dc_correct on its own -> is the capture float32"""
+        x, code = self._dc_rows(iq_local, "dc_correct")
+        self._own(x, "dc_correct")
+        if out is not None and out is not iq_local:
+            raise ValueError("dc_correct: out is None or the shard itself")
+        for t in also:
+            a, a_code = self._dc_rows(t, "dc_correct: also")
+            if a_code != code:
+                raise ValueError("dc_correct: `also` holds tensors of the shard's sample type")
+            self._own(a, "dc_correct: also")
+        return code == _lib.DT_F32
+
+    def dc_whole(self, iq_local, out):
+        """one rank: the single-GPU function -> (the corrected capture, its mean on the host)"""
+        from .filter import dc_correct_dev
+        res, mean = dc_correct_dev(self, iq_local, out=out, want_mean=True)
+        self._dc_single = self._dc_rows(iq_local, "dc_correct")[1] == _lib.DT_F32
+        return res, mean.cpu().numpy()
+
+    def dc_sums(self, iq_local):
+        """int64 (3,): n_local and the two column sums (float32 captures: the bits of two float64 sums)"""
+        x, code = self._dc_rows(iq_local, "dc_correct")
+        self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
+        words = self.torch.empty(3, dtype=self.torch.int64, device=self.device)
+        _lib.check(_lib.load().urhgpu_shard_dc_sums_dev(self.ctx.handle, C.c_void_p(x.data_ptr()) if x.shape[0] else None, int(x.shape[0]), code,
+                                                        C.c_void_p(words.data_ptr())))
+        words._urh_keep = x
+        self._dc_single = None
+        return words
+
+    def dc_spec(self, iq_local, base):
+        """int32 (2, 2, 4): the shard's records [column][path] {entry, exit, room, flags}, speculated from the float64 sums in front"""
+        x, _ = self._dc_rows(iq_local, "dc_correct")
+        self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
+        recs = self.torch.empty((2, 2, 4), dtype=self.torch.int32, device=self.device)
+        _lib.check(_lib.load().urhgpu_shard_dc_spec_dev(self.ctx.handle, C.c_void_p(x.data_ptr()) if x.shape[0] else None, int(x.shape[0]),
+                                                        (C.c_double * 2)(float(base[0]), float(base[1])), C.c_void_p(recs.data_ptr())))
+        recs._urh_keep = x
+        return recs
+
+    def dc_resolve(self, iq_local, entry):
+        """int32 (2,): the bits of the shard's exits when entered with `entry` (bits I, bits Q); entry None: zeros, for the ranks that only
+        take part in the hand-over"""
+        out = self.torch.zeros(2, dtype=self.torch.int32, device=self.device)
+        if entry is not None:
+            x, _ = self._dc_rows(iq_local, "dc_correct")
+            self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(_lib.load().urhgpu_shard_dc_resolve_dev(self.ctx.handle, C.c_void_p(x.data_ptr()) if x.shape[0] else None, int(x.shape[0]),
+                                                               (C.c_uint32 * 2)(int(entry[0]), int(entry[1])), C.c_void_p(out.data_ptr())))
+            out._urh_keep = x
+        return out
+
+    def dc_apply(self, t, mean, out=None):
+        """t minus the mean (host: two float32 for float32 samples, two float64 otherwise), into a new tensor or t itself"""
+        x, code = self._dc_rows(t, "dc_correct")
+        res = self.torch.empty_like(t) if out is None else out
+        y = self.torch.view_as_real(res) if res.dtype == self.torch.complex64 else res
+        m = np.ascontiguousarray(mean, dtype=np.float32 if code == _lib.DT_F32 else np.float64)
+        self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(_lib.load().urhgpu_shard_dc_apply_dev(self.ctx.handle, C.c_void_p(x.data_ptr()) if x.shape[0] else None, int(x.shape[0]), code,
+                                                         C.c_void_p(m.ctypes.data), C.c_void_p(y.data_ptr()) if x.shape[0] else None))
+        res._urh_keep = x
+        return res
+
+    def dc_stats(self):
+        """this rank's stitches of the last dc_correct: chunks per column, chunks derived from their records, chunks re-evaluated serially"""
+        lib, st = _lib.load(), (C.c_int64 * 8)()
+        single = getattr(self, "_dc_single", None)
+        if single is not None:
+            if single:
+                _lib.check(lib.urhgpu_test_dc_stats(self.ctx.handle, st))
+            return {"chunks": int(st[0]), "derived": int(st[1]), "reevaluated": int(st[2])}
+        _lib.check(lib.urhgpu_shard_dc_stats(self.ctx.handle, st))
+        return {"chunks": int(st[0]), "derived": int(st[1] + st[5]), "reevaluated": int(st[2] + st[6])}
+
     def rows(self, summaries):
         torch = self.torch
         self._keep += (summaries,)

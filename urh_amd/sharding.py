@@ -37,6 +37,21 @@ all-gathers (one for the noise level; four for the center: kept counts, two reco
 rank's global offset, histogram counts), every result a pure function of gathered data (`pairwise_combine`, `center_parts`).  A PSK
 pass detects its own center with `auto_center=True`.
 
+DC correction: `dc_correct` subtracts the mean of the WHOLE capture from every shard, bit-equal with numpy's `x - np.mean(x, axis=0)`.
+Integers: one all-gather of the ranks' exact int64 column sums.  float32: the mean is the strictly sequential float32 sum of the capture,
+carried across the ranks like the Costas state:
+
+    A. sums        three 8-byte words per rank: n_local and the two column sums (float64 for float32 captures: the guesses)
+    B. records     every rank speculates its shard from fl32(the float64 sum of the ranks before it) and from that guess's neighbour and
+                   gathers, per column and path, {entry, exit, room}: the exit holds for every entry an even number of ulps, at most `room`,
+                   from the path's (64 bytes per rank)
+    C. compose     `dc_compose` (a pure function of the gathered bytes) walks the ranks with the true entry; where a record does not
+                   reach, that rank re-stitches from its true entry and hands its exit over in one more all-gather of 8 bytes per rank
+    D. finish      mean = fl32(double(sum) / double(n_total)); every rank subtracts it from its shard and from the raw samples handed
+                   over with it (`also`)
+
+Two all-gathers when every record holds, world + 1 at most; how many depends on gathered bytes only.
+
 The orchestration below is engine-agnostic: `engine` is the GPU engine (urh_amd.shard_engine.GpuShardEngine,
 HIP kernels behind the C ABI) in production; the CPU test-suite drives the same orchestration with the executable
 model of the kernels (tests/model_shard.py) over a world_size-2 gloo group.
@@ -383,6 +398,59 @@ def costas_exchange(comm, summary, resolve, end_state):
         rounds += 1
 
 
+# ---- the sequential float32 sum of a capture across ranks (csrc/dc_correct.hip writes the records) -------------------------------------
+# a rank's records: [column][path] x {entry bits, exit bits, room, flags} as uint32 (URHGPU_DC_RECORD_BYTES = 64)
+DC_IDENTITY = 1                             # flags: the shard holds no sample, its exit is its entry
+
+
+def dc_compose(records, handoff=None):
+    """Carry numpy's sequential float32 column sums across the shards: a pure function of the gathered shard records ((world, 2, 2, 4)
+    uint32: per column and speculated path {entry bits, exit bits, room, flags}, rank order) and of the exits handed over so far
+    (handoff: {rank: (bits I, bits Q)}), so every rank that evaluates it takes the same branch.  Rank 0 enters with +0.0.  A shard's
+    exit follows from its records where the true entry equals a path's entry (the recorded exit), where it lies D ulps from the path an
+    even number of ulps away, on the same side of zero, with |D| <= room (the recorded exit moved by D: every chunk on the path stays
+    inside its binade, and paths an even distance apart round every tie alike), where the shard is empty, and where the sum is already
+    NaN (it stays).  Returns (entries, pending, total): entries[r] = the true entry of shard r as (bits I, bits Q), None where not known
+    yet; pending = the first rank one of whose columns the records cannot carry (its entry is known: it re-stitches both columns from
+    it and hands its exits over), None when every entry is known; total = the sum's bits (I, Q) when pending is None."""
+    rec = np.ascontiguousarray(np.asarray(records)).view(np.uint32).reshape(-1, 2, 2, 4)
+    handoff = handoff or {}
+    entries = [None] * len(rec)
+    t = (0, 0)                                            # +0.0: numpy's accumulator starts there
+    for r in range(len(rec)):
+        entries[r] = t
+        if r in handoff:
+            t = (int(handoff[r][0]), int(handoff[r][1]))
+            continue
+        nxt = []
+        for col in range(2):
+            e = _dc_exit(rec[r, col], t[col])
+            if e is None:
+                return entries, r, None
+            nxt.append(e)
+        t = tuple(nxt)
+    return entries, None, t
+
+
+def _dc_exit(paths, t):
+    """the exit of one column of a shard entered with the bits t, from its two path records; None where they do not give it"""
+    if int(paths[0, 3]) & DC_IDENTITY:
+        return t
+    for p in paths:
+        if t == int(p[0]):
+            return int(p[1])
+    if (t & 0x7FFFFFFF) > 0x7F800000:
+        return t                                          # a NaN sum absorbs whatever follows
+    p = paths[(t ^ int(paths[0, 0])) & 1]                 # the path an even number of ulps away
+    entry, leave, room = int(p[0]), int(p[1]), int(p[2])
+    if (t ^ entry) >> 31:
+        return None
+    d = (t & 0x7FFFFFFF) - (entry & 0x7FFFFFFF)
+    if abs(d) > room:
+        return None
+    return (leave & 0x80000000) | ((leave & 0x7FFFFFFF) + d)
+
+
 # ---- numpy's float32 summation tree across ranks (csrc/pairwise.hpp has the order; csrc/shard_estimators.hip writes the records) ----
 PW_PIECE, PW_LEAF = 8192, 128               # kPwChunk, kPwLeaf
 PW_REC_HEAD, PW_REC_FIRST, PW_REC_LAST, PW_REC_TAIL, PW_REC_PIECES = 8, 136, 264, 392, 520      # URHGPU_PW_REC_* (include/urhgpu.h)
@@ -576,6 +644,7 @@ class ShardedPipeline:
         self.rank, self.world = comm.rank, comm.world
         self.last_costas = None                  # PSK: the last pass's Costas exchange (rounds, this rank's chunks by map / checkpoint / serial)
         self.last_center = None                  # the center the last pass's pulse table was built with (auto_center: the detected one)
+        self.last_dc = None                      # the last dc_correct: mean, all-gathers, this rank's stitch statistics
 
     # bench.py / DevicePipeline compatible surface ------------------------------------------------
     @property
@@ -706,6 +775,70 @@ class ShardedPipeline:
             total[b0:b1] = c.all_gather(local[b0:b1]).cpu().numpy().reshape(self.world, -1).sum(axis=0)
         return peaks_center(total, edges)
 
+    def dc_correct(self, iq_local, pos_base=None, n_total=None, also=(), out=None):
+        """The shard minus the mean of the WHOLE capture: rows [pos_base, pos_base + n_local) of numpy's x - np.mean(x, axis=0) stored into the
+        capture's sample type, bit for bit -- the sharded counterpart of filter.dc_correct_dev (module docstring, "DC correction").
+        iq_local: (n_local, 2) in one of the five sample types, or complex64 (n_local,); a rank may hold no sample.  pos_base / n_total
+        default as in iq_to_bits; the ranks' n_local must add up to n_total (checked from gathered data: every rank raises ValueError).
+        also: small tensors of the same sample type corrected with the same mean and returned with the shard -- the raw samples a
+        distributor hands over with it (left_halo, the PSK left_raw, the FIR left_raw), without which a corrected shard could not be
+        used with halo_given=True, a PSK pass or fir_filter(raw_halo=True).  out: None (a new tensor) or iq_local (in place).
+        Returns the corrected shard, or (shard, [corrected also tensors]) when `also` is given.  `last_dc` records the mean (two float64
+        for integers, two float32 for float32), the number of all-gathers and this rank's stitch statistics.
+        world == 1 is the single-GPU function; n_total == 0 returns the empty shard; neither enters a collective.  The recipe for a
+        corrected pass: dc_correct, then iq_to_bits on the result."""
+        e = self._estimator_engine("dc_own", "dc_whole", "dc_sums", "dc_spec", "dc_resolve", "dc_apply", "dc_stats")
+        c = self.comm
+        also = tuple(also)
+        is_f32 = e.dc_own(iq_local, also, out)            # everything a rank can get wrong on its own, before anything is exchanged
+        n_local = int(iq_local.shape[0])
+        pos_base = self.rank * n_local if pos_base is None else int(pos_base)
+        n_total = self.world * n_local if n_total is None else int(n_total)
+        if pos_base < 0 or pos_base + n_local > n_total:
+            raise ValueError("dc_correct: the shard does not lie inside the capture")
+        stats = {"chunks": 0, "derived": 0, "reevaluated": 0}
+        gathers = 0
+        if self.world == 1 and n_local != n_total:
+            raise ValueError(f"dc_correct: the ranks hold {n_local} samples, the capture has {n_total}")
+        if n_total == 0:
+            self.last_dc = {"mean": None, "all_gathers": 0, **stats}
+            return (iq_local, list(also)) if also else iq_local
+        if self.world == 1:
+            res, mean = e.dc_whole(iq_local, out)
+            stats = e.dc_stats()
+        else:
+            words = np.ascontiguousarray(c.all_gather(e.dc_sums(iq_local)).cpu().numpy()).view(np.int64).reshape(self.world, 3)
+            gathers = 1
+            held = sum(int(v) for v in words[:, 0])
+            if held != n_total:                           # decided from gathered data: every rank raises, none is left in a collective
+                raise ValueError(f"dc_correct: the ranks hold {held} samples, the capture has {n_total}")
+            if not is_f32:
+                mean = np.array([float(sum(int(v) for v in words[:, k])) / float(n_total) for k in (1, 2)], np.float64)
+            else:
+                with np.errstate(all="ignore"):
+                    guesses = np.ascontiguousarray(words[:, 1:]).view(np.float64)
+                    base = [0.0, 0.0]
+                    for r in range(self.rank):
+                        base = [base[0] + float(guesses[r, 0]), base[1] + float(guesses[r, 1])]
+                    recs = c.all_gather(e.dc_spec(iq_local, base)).cpu().numpy()
+                    gathers = 2
+                    handoff = {}
+                    while True:
+                        entries, pending, total = dc_compose(recs, handoff)
+                        if pending is None:
+                            break
+                        ends = c.all_gather(e.dc_resolve(iq_local, entries[pending] if pending == self.rank else None)).cpu().numpy()
+                        ends = np.ascontiguousarray(ends).view(np.uint32).reshape(self.world, 2)
+                        handoff[pending] = (int(ends[pending, 0]), int(ends[pending, 1]))
+                        gathers += 1
+                    s = np.array(total, np.uint32).view(np.float32)
+                    mean = (s.astype(np.float64) / np.float64(n_total)).astype(np.float32)      # numpy: the float32 sum divided in float64, rounded once
+                stats = e.dc_stats()
+            res = e.dc_apply(iq_local, mean, out)
+        fixed = [e.dc_apply(t, mean, None) for t in also]
+        self.last_dc = {"mean": mean, "all_gathers": gathers, **stats}
+        return (res, fixed) if also else res
+
     def iq_to_bits(self, iq_local, p, want_qad=True, pos_base=None, n_total=None, halo_given=False, left_halo=None, left_raw=None, auto_center=False,
                    msg_records=False, dc_correction=False):
         """iq_local: this rank's shard.  pos_base / n_total default to equal shards of len(iq_local).
@@ -722,11 +855,11 @@ class ShardedPipeline:
         that center.
         msg_records: refused (ValueError) -- a message's middle window may lie in another rank's shard; the records belong to single-GPU passes
         (DevicePipeline.iq_to_bits, CaptureStream).
-        dc_correction: refused (ValueError) -- the mean is the sequential float32 sum of the WHOLE capture; correct it on one GPU
-        (filter.dc_correct_dev) before it is distributed."""
+        dc_correction: refused (ValueError) as an option of the pass; the recipe is `dc_correct` (the mean of the WHOLE capture, carried
+        across the ranks), then iq_to_bits on the result -- with left_halo / left_raw corrected through its `also`."""
         e, c = self.engine, self.comm
         if dc_correction:
-            raise ValueError("DC correction is not available for sharded passes: correct the capture on one GPU (filter.dc_correct_dev) first")
+            raise ValueError("DC correction is not an option of a sharded pass: call dc_correct on the shard first, then iq_to_bits on the result")
         if msg_records:
             raise ValueError("message records are not available for sharded passes: run DevicePipeline.iq_to_bits(msg_records=True) on one GPU")
         if auto_center and p.modulation_type != "PSK":
