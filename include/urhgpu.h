@@ -1029,6 +1029,47 @@ int urhgpu_shard_dc_apply_dev(urhgpu_ctx *ctx, const void *d_in, int64_t n, int 
  * paths, paths per column; stats[4..7]: the same for the resolve. */
 int urhgpu_shard_dc_stats(urhgpu_ctx *ctx, int64_t *stats);
 
+/* ---- message records of a sharded capture (urh_amd/sharding.py, "message records") ----
+ * One urhgpu_msg_record per message that CLOSES on this rank, behind the sharded pass that filled `out` (urhgpu_shard_bits_finish_dev; out->pos
+ * required): concatenated in rank order they are the records urhgpu_msg_records_dev gives for the whole capture, bit for bit.  A rank's second and
+ * later messages start behind a pause row that ends in its shard and are closed by a pause of more than pause_threshold symbols that ends in it
+ * too: their bits, positions and middle window lie in the shard.  The FIRST message a rank closes may have begun on earlier ranks, and its
+ * window [mid_pos, min(mid_pos + samples_per_symbol, n_total)) may lie anywhere up to the end of the closing pause.  What it needs crosses the
+ * ranks in two all-gathers, and a third where a first window is not wholly inside its closing rank's shard (the caller gathers; every
+ * decision is a pure function of gathered words).  All three calls are asynchronous, on the stream urhgpu_msg_records_dev would take.
+ *
+ * 1. summary: d_words (device, 8-byte aligned) = URHGPU_SHARD_REC_SUMMARY_WORDS int64, from the pass's device counts and offsets:
+ *      [0] pos_base   [1] n_local   [2] messages closed here
+ *      [3] bits before the first close (all the rank's bits when none closes)   [4] position entries before the first close (likewise)
+ *      [5] bits behind the last close (0 when none closes)                      [6] position entries behind the last close (likewise)
+ *      [7] the pause of the first message closed here (0: none)
+ *      [8] 1: the pass's outputs stayed inside their capacities on this rank (rows, messages, bits, positions), 0: not
+ *      [9] the rank's position entries
+ *    From the gathered words every rank derives, for the first message of every closing rank: L and np (summed over the ranks since the
+ *    previous close), n_pad, the middle index k, and which rank holds, at which local index, position entry 0 and entry rel (np - 2 where
+ *    the middle lies in the padded part, k otherwise).
+ * 2. look-up: d_index (device, n int64): the LOCAL index into out->pos of every entry asked of this rank, -1 where another rank holds it;
+ *    d_values (device, n int64) = out->pos[d_index[i]], 0 for -1 or an index the rank does not hold.  Gathered, the values give first_pos and
+ *    mid_pos of every first message, and so its window.
+ * 3. windows (only where a first window leaves its closing rank's shard): the ranks contribute the raw samples of those windows that their
+ *    shards hold; the closing rank assembles its window contiguously (d_window, window_len samples of the capture's sample type).
+ * finish: urhgpu_shard_msg_records_dev.  d_iq: the shard the pass demodulated, samples [pos_base, pos_base + n_local) of the n_total; it is read
+ *    here, later than by anything else of the pass.  first (HOST, URHGPU_SHARD_REC_FIRST_WORDS int64): the first message closed here, from the
+ *    gathered data: {1: this rank closes a message, L, np, n_pad, first_pos, mid_pos, 1: every rank that contributes to it held its capacities
+ *    and its entries exist, 1: its window is d_window[0 .. w)} (0: its window lies in the shard).  Every other message is computed as
+ *    urhgpu_msg_records_dev computes it, from out's own msg_off / pos_off / pos / pauses, with its samples read at mid_pos - pos_base.
+ *    flag: 1 valid; 0: a capacity was exceeded on a rank that contributes to the message (on this rank: every record it writes); -1 as for
+ *    urhgpu_msg_records_dev; -2: the window is not inside the shard and no assembled window was given -- nothing outside the shard is read,
+ *    rssi is NaN.  For a message that is not the first one closed here this does not occur (DESIGN.md 5 has the argument).
+ *    d_rec / cap_msg / h_rec, the bounded grid, n_msg read on the device and the mirror sweep: as urhgpu_msg_records_dev. */
+#define URHGPU_SHARD_REC_SUMMARY_WORDS 10
+#define URHGPU_SHARD_REC_FIRST_WORDS 8
+int urhgpu_shard_records_summary_dev(urhgpu_ctx *ctx, int64_t n_local, int64_t pos_base, const urhgpu_outputs *out, void *d_words);
+int urhgpu_shard_records_lookup_dev(urhgpu_ctx *ctx, const urhgpu_outputs *out, const void *d_index, int64_t n, void *d_values);
+int urhgpu_shard_msg_records_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int64_t pos_base, int64_t n_total, const urhgpu_params *p,
+                                 const urhgpu_outputs *out, int64_t message_length_divisor, const int64_t *first, const void *d_window,
+                                 int64_t window_len, void *d_rec, int64_t cap_msg, void *h_rec);
+
 #ifdef __cplusplus
 }
 #endif

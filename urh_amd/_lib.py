@@ -136,6 +136,10 @@ PROTOTYPES = {
     "urhgpu_stream_set_msg_records": (_i, [_vp, _i, _i64]),
     "urhgpu_stream_msg_records": (_i, [_vp, _i64, C.POINTER(_vp), C.POINTER(_i64)]),
     "urhgpu_test_records_host_syncs": (_i64, []),
+    "urhgpu_shard_records_summary_dev": (_i, [_vp, _i64, _i64, C.POINTER(Outputs), _vp]),
+    "urhgpu_shard_records_lookup_dev": (_i, [_vp, C.POINTER(Outputs), _vp, _i64, _vp]),
+    "urhgpu_shard_msg_records_dev": (_i, [_vp, _vp, _i64, _i64, _i64, C.POINTER(Params), C.POINTER(Outputs), _i64, C.POINTER(_i64), _vp, _i64, _vp, _i64,
+                                          _vp]),
     "urhgpu_blob_capacity": (_i64, [_i64, _i64, _i64, _i64, _i]),
     "urhgpu_outputs_to_host": (_i, [_vp, C.POINTER(Outputs), _i, _vp, _i64, C.POINTER(_i64)]),
     "urhgpu_host_libm_check": (_i, [C.POINTER(_i64)]),

@@ -15,6 +15,10 @@
 // leaves), a longer one more rounds and pieces of the same code: exact for every length, no second form.  The terms are formed from global memory when they are added (each is used once; the
 // eight lanes of a leaf read eight neighbouring samples), not staged.
 // k_msg_records_mirror: one wavefront stores the n_msg records into the pinned host mirror, 16 bytes per lane, contiguously.
+// The summation is the device function rec_window_sum, shared with the records of a sharded capture (include/urhgpu.h "message records of a
+// sharded capture"): k_shard_msg_records is k_msg_records on one rank's outputs -- global positions, samples read at mid - pos_base -- with the
+// first message closed on the rank taken from a descriptor built from gathered data and its window from the shard or from a buffer assembled
+// from the ranks' samples; k_shard_rec_summary / k_shard_rec_lookup (one wavefront each) write the words the ranks exchange.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,6 +47,18 @@ struct RecArgs {
 
 struct RecFrame { int64_t off, len; int stage; };
 
+// what one workgroup's summation keeps in LDS (one instance per kernel)
+struct RecShared {
+    RecFrame frames[kRecStack];
+    double values[kRecStack];
+    double acc[kRecThreads];
+    double leaf_sum[kRecLeaves];
+    int64_t leaf_off[kRecLeaves];
+    int leaf_len[kRecLeaves];
+    unsigned char ops[kRecOps];
+    int sp, vsp, n_leaves, n_ops, bad;
+};
+
 // Python's a[start:stop] on n elements: where the slice begins and how many elements it has
 __device__ __forceinline__ void py_slice(int64_t start, int64_t stop, int64_t n, int64_t *lo, int64_t *count) {
     const int64_t a = start < 0 ? (start + n < 0 ? 0 : start + n) : (start > n ? n : start);
@@ -51,18 +67,114 @@ __device__ __forceinline__ void py_slice(int64_t start, int64_t stop, int64_t n,
     *count = b > a ? b - a : 0;
 }
 
+// The float64 np.add.reduce of the w terms mag(iq[lo + i]) / norm (the file's head has the order): the ONE copy of the summation, called by
+// every thread of the workgroup of both records kernels.  Returns the total to thread 0 (other threads: 0); sh.bad is set where the
+// bookkeeping gave up.  Ends behind a barrier.
+template <int DT>
+__device__ __forceinline__ double rec_window_sum(RecShared &sh, const void *iq, int64_t lo, int64_t w, double norm) {
+    const int tid = threadIdx.x, grp = tid >> 3, j = tid & 7;
+    auto term = [&](int64_t i) -> double { return MagLoad<DT>::mag(iq, lo + i) / norm; };
+    // ---- piece after piece of 8192, each in rounds of (emit leaves, sum leaves, run the additions) ----
+    double total = 0.0;                                            // (thread 0's: ((0 + pw(piece 0)) + pw(piece 1)) + ...)
+    if (tid == 0) sh.bad = 0;
+    __syncthreads();
+    for (int64_t piece = 0; piece < w && !sh.bad; piece += kPwChunk) {
+        __syncthreads();                                               // (every thread has read sh.bad)
+        if (tid == 0) {
+            sh.vsp = 0; sh.sp = 1;
+            sh.frames[0].off = piece; sh.frames[0].len = w - piece < kPwChunk ? w - piece : kPwChunk; sh.frames[0].stage = 0;
+        }
+        __syncthreads();
+        while (sh.sp > 0 && !sh.bad) {                                 // (shared: every thread reads the same values behind the barrier)
+            __syncthreads();                                           // ... and all of them before thread 0 writes them again
+            if (tid == 0) {
+                int sp = sh.sp, nl = 0, no = 0;
+                while (sp > 0 && nl < kRecLeaves && no < kRecOps) {
+                    RecFrame f = sh.frames[sp - 1];
+                    if (f.len <= kPwLeaf) {
+                        sh.leaf_off[nl] = f.off; sh.leaf_len[nl] = (int)f.len; ++nl;
+                        sh.ops[no++] = 0; --sp;
+                    } else if (f.stage == 2) {
+                        sh.ops[no++] = 1; --sp;
+                    } else if (sp >= kRecStack) {
+                        sh.bad = 1; break;                             // (deeper than any 64-bit length goes)
+                    } else {
+                        const int64_t n2 = pw_split(f.len);
+                        sh.frames[sp - 1].stage = f.stage + 1;
+                        sh.frames[sp].off = f.stage == 0 ? f.off : f.off + n2;
+                        sh.frames[sp].len = f.stage == 0 ? n2 : f.len - n2;
+                        sh.frames[sp].stage = 0;
+                        ++sp;
+                    }
+                }
+                sh.sp = sp; sh.n_leaves = nl; sh.n_ops = no;
+            }
+            __syncthreads();
+            const int nl = sh.n_leaves;
+            int len = 0, lim = 0;
+            int64_t off = 0;
+            if (grp < nl) {
+                len = sh.leaf_len[grp]; off = sh.leaf_off[grp]; lim = len - (len % 8);
+                if (len >= 8) {
+                    double r = term(off + j);
+                    for (int i = 8; i < lim; i += 8) r += term(off + i + j);
+                    sh.acc[tid] = r;
+                }
+            }
+            __syncthreads();
+            if (grp < nl && j == 0) {
+                double res;
+                if (len < 8) {
+                    res = 0.0;
+                    for (int i = 0; i < len; ++i) res += term(off + i);
+                } else {
+                    const double *r = sh.acc + tid;
+                    res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+                    for (int i = lim; i < len; ++i) res += term(off + i);
+                }
+                sh.leaf_sum[grp] = res;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                int vsp = sh.vsp, li = 0;
+                for (int o = 0; o < sh.n_ops; ++o) {
+                    if (sh.ops[o] == 0) {
+                        if (vsp < kRecStack) sh.values[vsp] = sh.leaf_sum[li];
+                        else sh.bad = 1;
+                        ++vsp; ++li;
+                    } else {
+                        if (vsp >= 2 && vsp <= kRecStack) sh.values[vsp - 2] = sh.values[vsp - 2] + sh.values[vsp - 1];
+                        else sh.bad = 1;
+                        --vsp;
+                    }
+                }
+                sh.vsp = vsp;
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            if (sh.vsp == 1 && !sh.bad) total += sh.values[0];
+            else sh.bad = 1;
+        }
+        __syncthreads();
+    }
+    return total;
+}
+
+// the ASK padding of a message of L bits followed by `pause` samples (divisor <= 1: none)
+__device__ __forceinline__ int64_t rec_n_pad(int64_t L, int64_t pause, int64_t sps, int64_t divisor) {
+    if (divisor > 1 && L >= 0) {
+        const int64_t missing = (divisor - L % divisor) % divisor;
+        if (missing > 0 && pause >= sps * missing) return missing;
+    }
+    return 0;
+}
+
 template <int DT>
 __global__ __launch_bounds__(kRecThreads) void k_msg_records(RecArgs a) {
-    __shared__ RecFrame s_frames[kRecStack];
-    __shared__ double s_values[kRecStack];
-    __shared__ double s_acc[kRecThreads];
-    __shared__ double s_leaf_sum[kRecLeaves];
-    __shared__ int64_t s_leaf_off[kRecLeaves];
-    __shared__ int s_leaf_len[kRecLeaves];
-    __shared__ unsigned char s_ops[kRecOps];
-    __shared__ int s_sp, s_vsp, s_n_leaves, s_n_ops, s_bad;
+    __shared__ RecShared sh;
     URH_TAIL_PRIO();
-    const int tid = threadIdx.x, grp = tid >> 3, j = tid & 7;
+    const int tid = threadIdx.x;
     int64_t n_msg = a.counts[1];
     if (n_msg > a.cap_msg) n_msg = a.cap_msg;
     if (n_msg > a.cap_rec) n_msg = a.cap_rec;
@@ -71,11 +183,7 @@ __global__ __launch_bounds__(kRecThreads) void k_msg_records(RecArgs a) {
     for (int64_t m = blockIdx.x; m < n_msg; m += gridDim.x) {
         // ---- the message's scalars: padding, first and middle position, window (every thread alike) ----
         const int64_t L = a.msg_off[m + 1] - a.msg_off[m], pause = a.pauses[m], po = a.pos_off[m], np = a.pos_off[m + 1] - po;
-        int64_t n_pad = 0;
-        if (a.divisor > 1 && L >= 0) {
-            const int64_t missing = (a.divisor - L % a.divisor) % a.divisor;
-            if (missing > 0 && pause >= a.sps * missing) n_pad = missing;
-        }
+        const int64_t n_pad = rec_n_pad(L, pause, a.sps, a.divisor);
         // a padded message keeps its entries 0 .. np - 2 (np - 2: the start S of the closing pause, or the last bit of a trailing message whose
         // short pause is borrowed from); np - 1 + t becomes A + (t + 1) * sps for t < n_pad, A that entry np - 2
         const int64_t k = (L + n_pad) / 2;
@@ -88,100 +196,120 @@ __global__ __launch_bounds__(kRecThreads) void k_msg_records(RecArgs a) {
             mid = a.pos[po + rel] + (in_pad ? (k - rel) * a.sps : 0);
             py_slice(mid, mid + a.sps, a.n, &lo, &w);
         }
-        auto term = [&](int64_t i) -> double { return MagLoad<DT>::mag(a.iq, lo + i) / a.norm; };
-        // ---- np.mean of the window's terms: piece after piece of 8192, each in rounds of (emit leaves, sum leaves, run the additions) ----
-        double total = 0.0;                                            // (thread 0's: ((0 + pw(piece 0)) + pw(piece 1)) + ...)
-        if (tid == 0) s_bad = 0;
-        __syncthreads();
-        for (int64_t piece = 0; piece < w && !s_bad; piece += kPwChunk) {
-            __syncthreads();                                               // (every thread has read s_bad)
-            if (tid == 0) {
-                s_vsp = 0; s_sp = 1;
-                s_frames[0].off = piece; s_frames[0].len = w - piece < kPwChunk ? w - piece : kPwChunk; s_frames[0].stage = 0;
-            }
-            __syncthreads();
-            while (s_sp > 0 && !s_bad) {                                   // (shared: every thread reads the same values behind the barrier)
-                __syncthreads();                                           // ... and all of them before thread 0 writes them again
-                if (tid == 0) {
-                    int sp = s_sp, nl = 0, no = 0;
-                    while (sp > 0 && nl < kRecLeaves && no < kRecOps) {
-                        RecFrame f = s_frames[sp - 1];
-                        if (f.len <= kPwLeaf) {
-                            s_leaf_off[nl] = f.off; s_leaf_len[nl] = (int)f.len; ++nl;
-                            s_ops[no++] = 0; --sp;
-                        } else if (f.stage == 2) {
-                            s_ops[no++] = 1; --sp;
-                        } else if (sp >= kRecStack) {
-                            s_bad = 1; break;                              // (deeper than any 64-bit length goes)
-                        } else {
-                            const int64_t n2 = pw_split(f.len);
-                            s_frames[sp - 1].stage = f.stage + 1;
-                            s_frames[sp].off = f.stage == 0 ? f.off : f.off + n2;
-                            s_frames[sp].len = f.stage == 0 ? n2 : f.len - n2;
-                            s_frames[sp].stage = 0;
-                            ++sp;
-                        }
-                    }
-                    s_sp = sp; s_n_leaves = nl; s_n_ops = no;
-                }
-                __syncthreads();
-                const int nl = s_n_leaves;
-                int len = 0, lim = 0;
-                int64_t off = 0;
-                if (grp < nl) {
-                    len = s_leaf_len[grp]; off = s_leaf_off[grp]; lim = len - (len % 8);
-                    if (len >= 8) {
-                        double r = term(off + j);
-                        for (int i = 8; i < lim; i += 8) r += term(off + i + j);
-                        s_acc[tid] = r;
-                    }
-                }
-                __syncthreads();
-                if (grp < nl && j == 0) {
-                    double res;
-                    if (len < 8) {
-                        res = 0.0;
-                        for (int i = 0; i < len; ++i) res += term(off + i);
-                    } else {
-                        const double *r = s_acc + tid;
-                        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-                        for (int i = lim; i < len; ++i) res += term(off + i);
-                    }
-                    s_leaf_sum[grp] = res;
-                }
-                __syncthreads();
-                if (tid == 0) {
-                    int vsp = s_vsp, li = 0;
-                    for (int o = 0; o < s_n_ops; ++o) {
-                        if (s_ops[o] == 0) {
-                            if (vsp < kRecStack) s_values[vsp] = s_leaf_sum[li];
-                            else s_bad = 1;
-                            ++vsp; ++li;
-                        } else {
-                            if (vsp >= 2 && vsp <= kRecStack) s_values[vsp - 2] = s_values[vsp - 2] + s_values[vsp - 1];
-                            else s_bad = 1;
-                            --vsp;
-                        }
-                    }
-                    s_vsp = vsp;
-                }
-                __syncthreads();
-            }
-            if (tid == 0) {
-                if (s_vsp == 1 && !s_bad) total += s_values[0];
-                else s_bad = 1;
-            }
-            __syncthreads();
-        }
+        // ---- np.mean of the window's terms ----
+        const double total = rec_window_sum<DT>(sh, a.iq, lo, w, a.norm);
         if (tid == 0) {
             urhgpu_msg_record r;
-            const bool good = ok && !s_bad;
+            const bool good = ok && !sh.bad;
             r.rssi = (good && w > 0) ? total / (double)w : __builtin_nan("");
             r.first_pos = first; r.mid_pos = mid;
             r.n_pad = (int32_t)n_pad; r.flag = good ? 1 : (ok ? -1 : 0);  // (-1: the summation's bookkeeping gave up -- not reached for any 64-bit length)
             a.rec[m] = r;
         }
         __syncthreads();                                               // (the next message's round starts from a clean state)
+    }
+}
+
+// ---- the records of one rank of a sharded capture (include/urhgpu.h, "message records of a sharded capture") ----------------------------
+struct ShardRecArgs {
+    RecArgs a;                   // iq: the shard; n: the CAPTURE's length (windows are clipped at its end); positions are global
+    int64_t pos_base, n_local;   // the shard holds samples [pos_base, pos_base + n_local)
+    int64_t cap_rows, cap_bits;
+    const void *window;          // the first message's window, assembled from the ranks' samples (window_len samples; may be null)
+    int64_t window_len;
+    int64_t first[URHGPU_SHARD_REC_FIRST_WORDS];     // the descriptor of the first message closed here, from the gathered words
+};
+
+// have the pass's outputs on this rank stayed inside their capacities (ShardResult.check_capacity)
+__device__ __forceinline__ bool shard_caps_held(const int64_t *counts, int64_t cap_rows, int64_t cap_msg, int64_t cap_bits, int64_t cap_pos) {
+    return counts[4] <= cap_rows && counts[1] <= cap_msg && counts[2] <= cap_bits && counts[3] <= cap_pos;
+}
+
+template <int DT>
+__global__ __launch_bounds__(kRecThreads) void k_shard_msg_records(ShardRecArgs s) {
+    __shared__ RecShared sh;
+    URH_TAIL_PRIO();
+    const RecArgs &a = s.a;
+    const int tid = threadIdx.x;
+    int64_t n_msg = a.counts[1];
+    if (n_msg > a.cap_msg) n_msg = a.cap_msg;
+    if (n_msg > a.cap_rec) n_msg = a.cap_rec;
+    int64_t n_pos = a.counts[3];
+    if (n_pos > a.cap_pos) n_pos = a.cap_pos;
+    const bool held = shard_caps_held(a.counts, s.cap_rows, a.cap_msg, s.cap_bits, a.cap_pos);
+    for (int64_t m = blockIdx.x; m < n_msg; m += gridDim.x) {
+        int64_t n_pad, first = 0, mid = 0, lo = 0, w = 0;
+        bool ok;
+        if (m == 0) {
+            // the first message closed here may have begun on earlier ranks: everything about it comes from the gathered data
+            n_pad = s.first[3];
+            ok = held && s.first[0] == 1 && s.first[6] == 1;
+            if (ok) { first = s.first[4]; mid = s.first[5]; }
+        } else {
+            // every later one starts behind a pause row that ends in this shard: k_msg_records' arithmetic on the rank's own outputs
+            const int64_t L = a.msg_off[m + 1] - a.msg_off[m], pause = a.pauses[m], po = a.pos_off[m], np = a.pos_off[m + 1] - po;
+            n_pad = rec_n_pad(L, pause, a.sps, a.divisor);
+            const int64_t k = (L + n_pad) / 2;
+            const bool in_pad = n_pad > 0 && k > np - 2;
+            const int64_t rel = in_pad ? np - 2 : k;
+            ok = held && L >= 0 && po >= 0 && np >= 1 && rel >= 0 && rel < np && po + np <= n_pos;
+            if (ok) {
+                first = a.pos[po];
+                mid = a.pos[po + rel] + (in_pad ? (k - rel) * a.sps : 0);
+            }
+        }
+        if (ok) py_slice(mid, mid + a.sps, a.n, &lo, &w);
+        // where the window's samples are: the assembled buffer (first message only), or the shard -- nothing outside it is ever read
+        const bool assembled = m == 0 && s.first[7] == 1 && s.window != nullptr && w <= s.window_len;
+        const bool outside = ok && w > 0 && !assembled && (lo < s.pos_base || lo + w > s.pos_base + s.n_local);
+        if (outside) w = 0;
+        const void *src = assembled ? s.window : a.iq;
+        const double total = rec_window_sum<DT>(sh, src, assembled ? 0 : lo - s.pos_base, w, a.norm);
+        if (tid == 0) {
+            urhgpu_msg_record r;
+            const bool good = ok && !outside && !sh.bad;
+            r.rssi = (good && w > 0) ? total / (double)w : __builtin_nan("");
+            r.first_pos = first; r.mid_pos = mid;
+            r.n_pad = (int32_t)n_pad; r.flag = good ? 1 : (!ok ? 0 : (outside ? -2 : -1));
+            a.rec[m] = r;
+        }
+        __syncthreads();
+    }
+}
+
+// one wavefront: the rank's summary words (include/urhgpu.h), lane i stores word i
+__global__ __launch_bounds__(64) void k_shard_rec_summary(const int64_t *msg_off, const int64_t *pauses, const int64_t *pos_off, const int64_t *counts,
+                                                          int64_t cap_rows, int64_t cap_msg, int64_t cap_bits, int64_t cap_pos, int64_t pos_base,
+                                                          int64_t n_local, int64_t *words) {
+    URH_TAIL_PRIO();
+    const bool held = shard_caps_held(counts, cap_rows, cap_msg, cap_bits, cap_pos);
+    const int64_t n_msg = counts[1] < cap_msg ? counts[1] : cap_msg, n_bits = counts[2] < cap_bits ? counts[2] : cap_bits;
+    const int64_t n_pos = counts[3] < cap_pos ? counts[3] : cap_pos;
+    int64_t v = 0;
+    switch (threadIdx.x) {
+        case 0: v = pos_base; break;
+        case 1: v = n_local; break;
+        case 2: v = n_msg; break;
+        case 3: v = n_msg > 0 ? msg_off[1] : n_bits; break;            // bits before the first close (all of them when none closes)
+        case 4: v = n_msg > 0 ? pos_off[1] : n_pos; break;
+        case 5: v = n_msg > 0 ? n_bits - msg_off[n_msg] : 0; break;    // bits behind the last close
+        case 6: v = n_msg > 0 ? n_pos - pos_off[n_msg] : 0; break;
+        case 7: v = n_msg > 0 ? pauses[0] : 0; break;
+        case 8: v = held ? 1 : 0; break;
+        case 9: v = n_pos; break;
+        default: break;
+    }
+    if (threadIdx.x < URHGPU_SHARD_REC_SUMMARY_WORDS) words[threadIdx.x] = v;
+}
+
+// one wavefront: values[i] = pos[index[i]] where this rank holds the entry asked for (index[i] >= 0), 0 elsewhere
+__global__ __launch_bounds__(64) void k_shard_rec_lookup(const int64_t *pos, const int64_t *counts, int64_t cap_pos, const int64_t *index, int64_t n,
+                                                         int64_t *values) {
+    URH_TAIL_PRIO();
+    const int64_t n_pos = counts[3] < cap_pos ? counts[3] : cap_pos;
+    for (int64_t i = threadIdx.x; i < n; i += 64) {
+        const int64_t at = index[i];
+        values[i] = (at >= 0 && at < n_pos) ? pos[at] : 0;
     }
 }
 
@@ -241,6 +369,20 @@ int launch_msg_records(const void *d_iq, int64_t n, const urhgpu_params *p, cons
 
 }  // namespace urh
 
+namespace {
+
+// behind the pass: on the tail stream while a pipelined pass's tail is pending there, on the context's stream otherwise
+bool records_on_tail(const urhgpu_ctx *ctx) { return ctx->pipelined && ctx->tail_pending && ctx->tail_stream && ctx->last_tail == ctx->tail_stream; }
+
+// what every sharded records call asks of the pass's outputs on this rank
+int shard_rec_check(const urhgpu_outputs *out) {
+    if (!out || !out->msg_off || !out->pauses || !out->pos_off || !out->pos || !out->counts) return URHGPU_ERR_ARG;
+    if (out->cap_rows < 0 || out->cap_msg < 0 || out->cap_bits < 0 || out->cap_pos < 0) return URHGPU_ERR_ARG;
+    return URHGPU_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int urhgpu_msg_records_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_params *p, const urhgpu_outputs *out,
@@ -248,11 +390,72 @@ int urhgpu_msg_records_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const u
     if (!ctx) return URHGPU_ERR_ARG;
     RecordsScope scope;                                      // (host waits below here are counted: urhgpu_test_records_host_syncs)
     URH_HIP(hipSetDevice(ctx->device));
-    // behind the pass: on the tail stream while a pipelined pass's tail is pending there, on the context's stream otherwise
-    const bool on_tail = ctx->pipelined && ctx->tail_pending && ctx->tail_stream && ctx->last_tail == ctx->tail_stream;
+    const bool on_tail = records_on_tail(ctx);
     hipStream_t s = on_tail ? ctx->tail_stream : ctx->stream;
     URH_TRY(launch_msg_records(d_iq, n, p, out, message_length_divisor, d_rec, cap_msg, h_rec, s));
     // urhgpu_ctx_join waits for the event of the pass recorded last: move it behind the records
+    if (on_tail) URH_HIP(hipEventRecord(ctx->ev_tail[(ctx->flip + 2) % 3], ctx->tail_stream));
+    return URHGPU_OK;
+}
+
+int urhgpu_shard_records_summary_dev(urhgpu_ctx *ctx, int64_t n_local, int64_t pos_base, const urhgpu_outputs *out, void *d_words) {
+    if (!ctx || !d_words || n_local < 0 || pos_base < 0) return URHGPU_ERR_ARG;
+    URH_TRY(shard_rec_check(out));
+    if ((uintptr_t)d_words & 7) return URHGPU_ERR_ARG;
+    URH_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = records_on_tail(ctx) ? ctx->tail_stream : ctx->stream;
+    hipLaunchKernelGGL(k_shard_rec_summary, dim3(1), dim3(64), 0, s, out->msg_off, out->pauses, out->pos_off, out->counts, out->cap_rows, out->cap_msg,
+                       out->cap_bits, out->cap_pos, pos_base, n_local, (int64_t *)d_words);
+    URH_HIP(hipGetLastError());
+    return URHGPU_OK;
+}
+
+int urhgpu_shard_records_lookup_dev(urhgpu_ctx *ctx, const urhgpu_outputs *out, const void *d_index, int64_t n, void *d_values) {
+    if (!ctx || n < 0 || (n > 0 && (!d_index || !d_values))) return URHGPU_ERR_ARG;
+    URH_TRY(shard_rec_check(out));
+    if (((uintptr_t)d_index & 7) || ((uintptr_t)d_values & 7)) return URHGPU_ERR_ARG;
+    if (n == 0) return URHGPU_OK;
+    URH_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = records_on_tail(ctx) ? ctx->tail_stream : ctx->stream;
+    hipLaunchKernelGGL(k_shard_rec_lookup, dim3(1), dim3(64), 0, s, out->pos, out->counts, out->cap_pos, (const int64_t *)d_index, n, (int64_t *)d_values);
+    URH_HIP(hipGetLastError());
+    return URHGPU_OK;
+}
+
+int urhgpu_shard_msg_records_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int64_t pos_base, int64_t n_total, const urhgpu_params *p,
+                                 const urhgpu_outputs *out, int64_t message_length_divisor, const int64_t *first, const void *d_window,
+                                 int64_t window_len, void *d_rec, int64_t cap_msg, void *h_rec) {
+    if (!ctx || !d_iq || !p || !first || !d_rec || cap_msg < 0) return URHGPU_ERR_ARG;
+    if (n_local <= 0 || pos_base < 0 || pos_base > n_total - n_local || window_len < 0 || (window_len > 0 && !d_window)) return URHGPU_ERR_ARG;
+    URH_TRY(shard_rec_check(out));
+    if (message_length_divisor < 1 || message_length_divisor > (int64_t(1) << 30) || p->samples_per_symbol < 1) return URHGPU_ERR_ARG;
+    if (((uintptr_t)d_rec & 15) || ((uintptr_t)h_rec & 15)) return URHGPU_ERR_ARG;
+    if (dtype_bytes(p->dtype) == 0) return URHGPU_ERR_DTYPE;
+    if (((uintptr_t)d_iq | (uintptr_t)d_window) & (uintptr_t)(dtype_bytes(p->dtype) - 1)) return URHGPU_ERR_ARG;
+    const int64_t cap = std::min<int64_t>(cap_msg, out->cap_msg);
+    if (cap == 0) return URHGPU_OK;
+    URH_HIP(hipSetDevice(ctx->device));
+    const bool on_tail = records_on_tail(ctx);
+    hipStream_t s = on_tail ? ctx->tail_stream : ctx->stream;
+    ShardRecArgs a{};
+    a.a = RecArgs{d_iq, n_total, out->msg_off, out->pauses, out->pos_off, out->pos, out->counts, out->cap_msg, out->cap_pos, cap_msg,
+                  (int64_t)p->samples_per_symbol, p->mod == URHGPU_MOD_ASK ? message_length_divisor : 1, records_norm(p->dtype), (urhgpu_msg_record *)d_rec};
+    a.pos_base = pos_base; a.n_local = n_local; a.cap_rows = out->cap_rows; a.cap_bits = out->cap_bits;
+    a.window = window_len > 0 ? d_window : nullptr; a.window_len = window_len;
+    for (int i = 0; i < URHGPU_SHARD_REC_FIRST_WORDS; ++i) a.first[i] = first[i];
+    const int blocks = (int)std::min<int64_t>(cap, kRecMaxBlocks);
+    switch (p->dtype) {
+        case URHGPU_DT_I8: hipLaunchKernelGGL(k_shard_msg_records<URHGPU_DT_I8>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
+        case URHGPU_DT_U8: hipLaunchKernelGGL(k_shard_msg_records<URHGPU_DT_U8>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
+        case URHGPU_DT_I16: hipLaunchKernelGGL(k_shard_msg_records<URHGPU_DT_I16>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
+        case URHGPU_DT_U16: hipLaunchKernelGGL(k_shard_msg_records<URHGPU_DT_U16>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
+        default: hipLaunchKernelGGL(k_shard_msg_records<URHGPU_DT_F32>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
+    }
+    URH_HIP(hipGetLastError());
+    if (h_rec) {
+        hipLaunchKernelGGL(k_msg_records_mirror, dim3(1), dim3(64), 0, s, (const uint4 *)d_rec, (uint4 *)h_rec, out->counts, out->cap_msg, cap_msg);
+        URH_HIP(hipGetLastError());
+    }
     if (on_tail) URH_HIP(hipEventRecord(ctx->ev_tail[(ctx->flip + 2) % 3], ctx->tail_stream));
     return URHGPU_OK;
 }

@@ -469,6 +469,88 @@ class GpuShardEngine(DevicePipeline):
         _lib.check(lib.urhgpu_shard_dc_stats(self.ctx.handle, st))
         return {"chunks": int(st[0]), "derived": int(st[1] + st[5]), "reevaluated": int(st[2] + st[6])}
 
+    # ---- message records across the shards (sharding.py: message_records; csrc/msg_records.hip, "sharded capture") ----
+    def _records_outputs(self, res):
+        """the C descriptor of a ShardResult's buffers: what the records kernels read of the pass (positions required)"""
+        if res.pos_buf is None:
+            raise ValueError("message_records needs the positions of the pass (write_bit_sample_pos)")
+        o = _lib.Outputs()
+        o.rows = res.rows_buf.data_ptr(); o.cap_rows = int(res.rows_buf.shape[0])
+        o.bits = res.bits_buf.data_ptr(); o.cap_bits = int(res.bits_buf.shape[0])
+        o.msg_off = res.msg_off_buf.data_ptr(); o.pauses = res.pauses_buf.data_ptr(); o.cap_msg = int(res.pauses_buf.shape[0])
+        o.pos = res.pos_buf.data_ptr(); o.cap_pos = int(res.pos_buf.shape[0])
+        o.pos_off = res.pos_off_buf.data_ptr()
+        o.counts = res.counts.data_ptr()
+        return o
+
+    def _records_shard(self, iq_local):
+        torch = self.torch
+        iq = torch.view_as_real(iq_local) if iq_local.dtype == torch.complex64 else iq_local
+        if iq.dim() != 2 or iq.shape[1] != 2:
+            raise ValueError("IQ must be an (N, 2) tensor or complex64 (N,)")
+        npdt = _torch_dtype(iq)
+        self._own(iq, "message_records")
+        return iq, npdt
+
+    def records_summary(self, iq_local, res, pos_base):
+        """int64 (REC_SUMMARY_WORDS,): this rank's summary words, from the pass's device counts and offsets (nothing read back)"""
+        from .sharding import REC_SUMMARY_WORDS
+        iq, _ = self._records_shard(iq_local)                  # everything a rank can get wrong on its own, before anything is exchanged
+        o = self._records_outputs(res)
+        self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
+        words = self.torch.empty(REC_SUMMARY_WORDS, dtype=self.torch.int64, device=self.device)
+        _lib.check(_lib.load().urhgpu_shard_records_summary_dev(self.ctx.handle, int(iq.shape[0]), int(pos_base), C.byref(o), C.c_void_p(words.data_ptr())))
+        return words
+
+    def records_lookup(self, res, index):
+        """int64 (len(index),): the position entries asked of this rank (index: local indices, -1 where another rank holds the entry)"""
+        torch = self.torch
+        self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        o = self._records_outputs(res)
+        d_index = torch.from_numpy(np.ascontiguousarray(index, dtype=np.int64)).to(self.device)
+        values = torch.empty(len(index), dtype=torch.int64, device=self.device)
+        _lib.check(_lib.load().urhgpu_shard_records_lookup_dev(self.ctx.handle, C.byref(o), C.c_void_p(d_index.data_ptr()), len(index),
+                                                               C.c_void_p(values.data_ptr())))
+        values._urh_keep = d_index
+        return values
+
+    def records_window_part(self, iq_local, pos_base, spans, w_max):
+        """uint8 (len(spans), w_max, bytes per sample): of every window [lo, lo + w) asked for, the raw samples this shard holds, in their
+        place; zeros elsewhere (plumbing: slices of the shard)"""
+        torch = self.torch
+        iq, npdt = self._records_shard(iq_local)
+        raw = iq.view(torch.uint8).view(int(iq.shape[0]), 2 * npdt.itemsize)
+        part = torch.zeros((len(spans), int(w_max), 2 * npdt.itemsize), dtype=torch.uint8, device=self.device)
+        a0, b0 = int(pos_base), int(pos_base) + int(iq.shape[0])
+        for j, (lo, w) in enumerate(spans):
+            a, b = max(lo, a0), min(lo + w, b0)
+            if b > a:
+                part[j, a - lo:b - lo] = raw[a - a0:b - a0]
+        return part
+
+    def records_finish(self, iq_local, res, pos_base, n_total, p, divisor, first, window):
+        """the records kernel -> this rank's records on the host (protocol.RECORD_DTYPE, one per message closed here)"""
+        from .protocol import RECORD_DTYPE
+        torch = self.torch
+        iq, npdt = self._records_shard(iq_local)
+        o, cp = self._records_outputs(res), p.to_c(npdt)
+        self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)      # the read-back below waits on this stream
+        cap = max(int(o.cap_msg), 1)
+        d_rec = self._buf("shard_records", (cap * RECORD_DTYPE.itemsize,), torch.uint8)
+        block = self._pinned.get(("records", "shard"))
+        if block is None or block.numel() < cap * RECORD_DTYPE.itemsize:
+            block = torch.zeros(cap * RECORD_DTYPE.itemsize, dtype=torch.uint8).pin_memory()
+            self._pinned[("records", "shard")] = block
+        first = np.ascontiguousarray(first, dtype=np.int64)
+        if window is not None:
+            window = window.contiguous()
+        _lib.check(_lib.load().urhgpu_shard_msg_records_dev(
+            self.ctx.handle, C.c_void_p(iq.data_ptr()), int(iq.shape[0]), int(pos_base), int(n_total), C.byref(cp), C.byref(o), int(divisor),
+            first.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(window.data_ptr()) if window is not None else None,
+            int(window.shape[0]) if window is not None else 0, C.c_void_p(d_rec.data_ptr()), cap, C.c_void_p(block.data_ptr())))
+        n_msg = min(int(res.counts[1:2].cpu()[0]), cap)       # waits for the kernels: the shard and the window are free again, the mirror is complete
+        return block.numpy().view(RECORD_DTYPE)[:n_msg].copy()
+
     def rows(self, summaries):
         torch = self.torch
         self._keep += (summaries,)
