@@ -518,6 +518,30 @@ int urhgpu_shard_costas_spec_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_lo
                                  const void *d_halo, int64_t n_halo, const urhgpu_params *p, const urhgpu_outputs *out, void *d_summary);
 int urhgpu_shard_costas_resolve_dev(urhgpu_ctx *ctx, const uint32_t *start_state, uint32_t *d_end_state);
 
+/* ASK / FSK with the demodulated signal first: the shard's demodulation as a phase of its own, for passes that need the whole capture's
+ * demodulated signal before they can slice it -- an automatic center, which the ranks detect across their shards between this phase and the
+ * runs phase (urh_amd/sharding.py, iq_to_bits_auto).  The shard is demodulated ONCE; the runs phase then segments out->qad.
+ *   urhgpu_shard_demod_dev: arguments as urhgpu_shard_launch_dev (d_left_halo: the two raw samples before the shard, NULL on rank 0), and
+ *       out->qad is required, n_total > 2, pos_base >= 1 on ranks > 0.  URHGPU_ERR_UNSUPPORTED for every modulation but ASK and FSK (PSK has
+ *       its Costas phases) and on a pipelined context (the caller reads gathered values on the host between the phases).  Writes rows
+ *       [pos_base, pos_base + n_local) of afp_demod(whole capture) into out->qad on the context's stream: global sample 0 gets the
+ *       modulation's NOISE constant (on rank 0 only), a rank > 0 computes its first FSK value from the halo's last sample, the gate is
+ *       p->noise_threshold.  On ranks > 0 it also computes the SEAM VALUE, afp_demod's value of global sample pos_base - 1 -- demod_one(halo[0],
+ *       halo[1]) with the gate on halo[1]; the NOISE constant where pos_base == 1 -- into a device float the context's shard session owns:
+ *       this is why the halo has two samples, and it is the left halo of the segmentation, so that the ranks do not exchange their last
+ *       demodulated values.  The session records that the shard's qad is resolved, and for which d_iq, n_local, out->qad, modulation, sample
+ *       type and noise threshold.
+ *   urhgpu_shard_runs_dev, called next with exactly these (p->center may differ: the detected one; d_left_halo as given here, it is not
+ *       read): segments out->qad -- the qad-input kernels of a PSK pass, the session's seam value as the left halo -- instead of running
+ *       the fused hot kernel; ASK keeps its generic tail and the merge exchange, FSK the tile tail; the later phases are unchanged.  The
+ *       record is taken by that call and dropped by urhgpu_shard_prelaunch_dev, urhgpu_shard_launch_dev and urhgpu_shard_costas_spec_dev;
+ *       without it, or with other buffers or another gate, urhgpu_shard_runs_dev behaves as it always did.
+ *   urhgpu_shard_seam_value: the seam value of the context's last urhgpu_shard_demod_dev on a rank > 0, read back to *seam (HOST); waits
+ *       for the context's stream.  For tests and diagnostics: no pass needs it on the host. */
+int urhgpu_shard_demod_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int64_t pos_base, int64_t n_total, int rank, int world,
+                           const void *d_left_halo, const urhgpu_params *p, const urhgpu_outputs *out);
+int urhgpu_shard_seam_value(urhgpu_ctx *ctx, float *seam);
+
 /* Magnitude chunk statistics for AutoInterpretation.detect_noise_level
  * (src/urh/ainterpretation/AutoInterpretation.py:60-91): chunks of `chunk` samples taken from the END
  * of the capture backwards; d_sum[k] (float64) / d_max[k] (float64) for chunk k counted from the end. */

@@ -161,6 +161,8 @@ PROTOTYPES = {
     "urhgpu_costas_halo_samples": (_i64, [C.POINTER(Params)]),
     "urhgpu_shard_costas_spec_dev": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _i, _vp, _i64, C.POINTER(Params), C.POINTER(Outputs), _vp]),
     "urhgpu_shard_costas_resolve_dev": (_i, [_vp, C.POINTER(C.c_uint32), _vp]),
+    "urhgpu_shard_demod_dev": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _i, _vp, C.POINTER(Params), C.POINTER(Outputs)]),
+    "urhgpu_shard_seam_value": (_i, [_vp, C.POINTER(C.c_float)]),
     "urhgpu_magnitude_chunk_stats_dev": (_i, [_vp, _vp, _i, _i64, _i64, _i64, _vp, _vp]),
     "urhgpu_segment_runs_dev": (_i, [_vp, _vp, _i, _i64, _f, _vp, _i64, _vp]),
     "urhgpu_message_ranges_dev": (_i, [_vp, _vp, _i, _i64, _f, _vp, _i64, C.POINTER(_i64), _vp, _i64, C.POINTER(_i64), C.POINTER(_i)]),

@@ -2007,6 +2007,43 @@ int launch_afp_demod(const RunArgs &a, int dtype, int mod, int grid, hipStream_t
     }
 }
 
+// The seam value of a shard (urhgpu_shard_demod_dev): afp_demod's value of the sample BEFORE the shard, global sample pos_base - 1, from the
+// two raw samples of the left halo -- demod_one(halo[0], halo[1]), gated on halo[1], the arithmetic k_afp_demod applies to that sample on the
+// rank that holds it.  pos_base == 1: that sample is the capture's first, result[0] = NOISE (:361).  One lane.
+template <int DT, int MOD>
+__global__ void k_afp_seam(const RunArgs p, float *out) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    float q = p.noise_val;
+    if (p.pos_base >= 2) {
+        float pc = 0, pd = 0, c = 0, d = 0;
+        Iq<DT>::load1(p.left_halo, 0, pc, pd);
+        Iq<DT>::load1(p.left_halo, 1, c, d);
+        q = demod_one<MOD>(pc, pd, c, d, p, 0.f);
+    }
+    *out = q;
+}
+
+template <int DT>
+static int launch_seam_2(const RunArgs &a, int mod, float *d_out, hipStream_t s) {
+    switch (mod) {
+        case URHGPU_MOD_ASK: hipLaunchKernelGGL((k_afp_seam<DT, URHGPU_MOD_ASK>), dim3(1), dim3(64), 0, s, a, d_out); return URHGPU_OK;
+        case URHGPU_MOD_FSK: hipLaunchKernelGGL((k_afp_seam<DT, URHGPU_MOD_FSK>), dim3(1), dim3(64), 0, s, a, d_out); return URHGPU_OK;
+        default: return URHGPU_ERR_UNSUPPORTED;
+    }
+}
+
+int launch_afp_seam(const RunArgs &a, int dtype, int mod, float *d_out, hipStream_t s) {
+    if (!a.left_halo || !d_out) return URHGPU_ERR_ARG;
+    switch (dtype) {
+        case URHGPU_DT_F32: return launch_seam_2<URHGPU_DT_F32>(a, mod, d_out, s);
+        case URHGPU_DT_I8: return launch_seam_2<URHGPU_DT_I8>(a, mod, d_out, s);
+        case URHGPU_DT_U8: return launch_seam_2<URHGPU_DT_U8>(a, mod, d_out, s);
+        case URHGPU_DT_I16: return launch_seam_2<URHGPU_DT_I16>(a, mod, d_out, s);
+        case URHGPU_DT_U16: return launch_seam_2<URHGPU_DT_U16>(a, mod, d_out, s);
+        default: return URHGPU_ERR_DTYPE;
+    }
+}
+
 void launch_test_div(uint64_t seed, int reps, unsigned long long *d_mismatches, hipStream_t s) {
     hipLaunchKernelGGL(k_test_div, dim3(4096), dim3(256), 0, s, seed, reps, d_mismatches);
 }

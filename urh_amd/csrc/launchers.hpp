@@ -73,6 +73,8 @@ int launch_demod_runs_iq(const RunArgs &a, int dtype, int mod, bool write_qad, h
 int launch_runs_qad(const RunArgs &a, hipStream_t s, HotEvents *ev = nullptr);
 bool runs_streamable(const RunArgs &a);       // RunArgs::progress is honoured for these arguments (bit-plane kernel, whole tiles)
 int launch_afp_demod(const RunArgs &a, int dtype, int mod, int grid, hipStream_t s);
+// sharded captures: *d_out = afp_demod's value of global sample a.pos_base - 1 from the two raw samples a.left_halo (ASK / FSK; k_afp_seam)
+int launch_afp_seam(const RunArgs &a, int dtype, int mod, float *d_out, hipStream_t s);
 void launch_test_div(uint64_t seed, int reps, unsigned long long *d_mismatches, hipStream_t s);
 void launch_test_sincosf_fast(unsigned long long *d_mismatches, hipStream_t s);
 void launch_test_atan2f(const float *y, const float *x, int64_t n, float *out, hipStream_t s);

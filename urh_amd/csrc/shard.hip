@@ -29,6 +29,11 @@ struct ShardSession {
     // PSK: the rank's Costas pass (urhgpu_shard_costas_*), whose output the runs phase reads instead of the IQ
     CostasShard costas;
     int costas_phase = 0;          // 1: speculated (summary out), 2: resolved (the shard's qad written), 0: none / taken by the runs phase
+    // ASK / FSK: the demodulation phase (urhgpu_shard_demod_dev), after which the runs phase segments the shard's qad like a PSK pass
+    bool demod_done = false;       // the shard's qad is written, for exactly the buffers and the gate below; taken by the runs phase
+    const void *demod_iq = nullptr; float *demod_qad = nullptr; int64_t demod_n = 0;
+    int demod_mod = 0, demod_dtype = 0; float demod_noise = 0.f;
+    float *d_seam = nullptr;       // device float of the session: afp_demod's value of global sample pos_base - 1 (the left halo of the segmentation)
 };
 
 ShardSession *session(urhgpu_ctx *ctx) {
@@ -38,7 +43,12 @@ ShardSession *session(urhgpu_ctx *ctx) {
 
 }  // namespace
 
-void urh::free_shard_session(urhgpu_ctx *ctx) { delete (ShardSession *)ctx->shard; ctx->shard = nullptr; }
+void urh::free_shard_session(urhgpu_ctx *ctx) {
+    ShardSession *ss = (ShardSession *)ctx->shard;
+    if (ss && ss->d_seam) (void)hipFree(ss->d_seam);
+    delete ss;
+    ctx->shard = nullptr;
+}
 
 extern "C" {
 
@@ -61,6 +71,13 @@ static int shard_launch(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int6
     const bool psk = (p->mod == URHGPU_MOD_PSK);
     if (psk && (ctx->pipelined || part != 0)) return URHGPU_ERR_UNSUPPORTED;
     if (psk && (ss->costas_phase != 2 || out->qad != ss->costas.out || n_local != ss->costas.n || d_iq != ss->costas.iq)) return URHGPU_ERR_ARG;
+    // ASK / FSK behind urhgpu_shard_demod_dev, for exactly the buffers and the gate it demodulated with: the same route, the halo being the
+    // session's seam value.  Without that state: the fused hot kernel, as ever.
+    const bool dem = !psk && part == 0 && !ctx->pipelined && ss->demod_done && out->qad && out->qad == ss->demod_qad && n_local == ss->demod_n &&
+                     d_iq == ss->demod_iq && p->mod == ss->demod_mod && p->dtype == ss->demod_dtype && p->noise_threshold == ss->demod_noise;
+    ss->demod_done = false;
+    const bool from_qad = psk || dem;
+    if (dem) d_left_halo = (rank > 0) ? (const void *)ss->d_seam : nullptr;
     ss->piped = ctx->pipelined;
     if (ss->piped) URH_TRY(begin_pipelined_pass(ctx)); else URH_TRY(join_tail(ctx));
     // ASK passes (generic tail: a dozen under-occupied launches and one more exchange) keep the caller's stream for the hot kernel and
@@ -97,8 +114,8 @@ static int shard_launch(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int6
         if (world > 1) ss->tile.d_row_base = ss->d_small + 4;
     }
     RunArgs &a = ss->run;
-    URH_TRY(hot_run_args(ctx, p, pl, n_local, pos_base, !psk, &a));            // (PSK reads its shard's qad: no max_magnitude)
-    a.in = psk ? (const void *)out->qad : d_iq; a.qad = psk ? nullptr : out->qad; a.left_halo = d_left_halo;
+    URH_TRY(hot_run_args(ctx, p, pl, n_local, pos_base, !from_qad, &a));       // (the qad-input routes read the shard's qad: no max_magnitude)
+    a.in = from_qad ? (const void *)out->qad : d_iq; a.qad = from_qad ? nullptr : out->qad; a.left_halo = d_left_halo;
     a.lds_pad = !ctx->pipelined ? 0 : (ss->use_tile ? ctx->hot_lds_pad : ctx->hot_lds_pad_sharded);
     a.chunks = ss->table + rank;               // this rank's chunks sit at table[rank .. rank + n_chunks)
     a.slab = ss->slab;
@@ -107,7 +124,7 @@ static int shard_launch(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int6
     // Pipelined: what the tail stream waits for as in digitize.  Everything after this launch goes to the tail stream -- also the first
     // chunk of a prelaunched pass, which waits for the halo exchange: the caller's stream never waits for a collective (the exchanges
     // of one communicator run in issue order, so the halo of pass i + 1 queues behind the last exchange of pass i's tail).
-    URH_TRY(hot_launch(ctx, a, p, !psk, s, ss->piped && n_local % kTile == 0, ss->piped ? ctx->ev_hot : nullptr,
+    URH_TRY(hot_launch(ctx, a, p, !from_qad, s, ss->piped && n_local % kTile == 0, ss->piped ? ctx->ev_hot : nullptr,
                        ss->piped ? ctx->tail_stream : nullptr, nullptr));
     ss->costas_phase = 0;
     URH_HIP(hipGetLastError());
@@ -117,6 +134,7 @@ static int shard_launch(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int6
 int urhgpu_shard_prelaunch_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int64_t pos_base, int64_t n_total,
                                int rank, int world, const urhgpu_params *p, const urhgpu_outputs *out) {
     if (p && p->mod == URHGPU_MOD_PSK) return URHGPU_ERR_UNSUPPORTED;    // PSK: urhgpu_shard_costas_* first, then urhgpu_shard_runs_dev
+    if (ctx && ctx->shard) ((ShardSession *)ctx->shard)->demod_done = false;     // the fused hot kernel was asked for
     URH_TRY(shard_launch(ctx, d_iq, n_local, pos_base, n_total, rank, world, nullptr, p, out, rank > 0 ? 1 : 0));
     ((ShardSession *)ctx->shard)->phase = -1;
     return URHGPU_OK;
@@ -126,6 +144,7 @@ int urhgpu_shard_launch_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, 
                             int rank, int world, const void *d_left_halo, const urhgpu_params *p, const urhgpu_outputs *out) {
     if ((rank == 0) != (d_left_halo == nullptr)) return URHGPU_ERR_ARG;
     if (p && p->mod == URHGPU_MOD_PSK) return URHGPU_ERR_UNSUPPORTED;    // PSK: urhgpu_shard_costas_* first, then urhgpu_shard_runs_dev
+    if (ctx && ctx->shard) ((ShardSession *)ctx->shard)->demod_done = false;     // the fused hot kernel was asked for
     URH_TRY(shard_launch(ctx, d_iq, n_local, pos_base, n_total, rank, world, d_left_halo, p, out, 0));
     ((ShardSession *)ctx->shard)->phase = -2;
     return URHGPU_OK;
@@ -168,6 +187,53 @@ int urhgpu_shard_runs_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, in
     else URH_TRY(launch_shard_summary(r, ctx->d_tickets + 1, s));
     URH_HIP(hipGetLastError());
     ss->phase = 1;
+    return URHGPU_OK;
+}
+
+// ---- ASK / FSK: the demodulation phase on its own (include/urhgpu.h) ----------------------------------------------------------------
+int urhgpu_shard_demod_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int64_t pos_base, int64_t n_total, int rank, int world,
+                           const void *d_left_halo, const urhgpu_params *p, const urhgpu_outputs *out) {
+    if (!ctx || !p || !out || !d_iq || !out->qad || !out->rows || !out->counts) return URHGPU_ERR_ARG;
+    if (world < 1 || world > kMaxWorld || rank < 0 || rank >= world || n_local < 2 || pos_base < 0 || pos_base + n_local > n_total || n_total <= 2)
+        return URHGPU_ERR_ARG;
+    if (rank == 0 ? pos_base != 0 : pos_base < 1) return URHGPU_ERR_ARG;
+    if ((rank == 0) != (d_left_halo == nullptr)) return URHGPU_ERR_ARG;
+    if (dtype_bytes(p->dtype) == 0) return URHGPU_ERR_DTYPE;
+    if (p->mod != URHGPU_MOD_ASK && p->mod != URHGPU_MOD_FSK) return URHGPU_ERR_UNSUPPORTED;      // (PSK has its Costas phases)
+    URH_TRY(check_params(p, true));
+    if (((uintptr_t)d_iq & 15) || ((uintptr_t)out->qad & 7)) return URHGPU_ERR_ARG;
+    if (ctx->pipelined) return URHGPU_ERR_UNSUPPORTED;
+    URH_HIP(hipSetDevice(ctx->device));
+    URH_TRY(join_tail(ctx));
+    ShardSession *ss = session(ctx);
+    if (!ss) return URHGPU_ERR_ARG;
+    ss->demod_done = false;
+    ss->costas_phase = 0;
+    ss->phase = 0;                                           // (a pass left behind its hot launch is over: the runs phase starts a new one)
+    if (!ss->d_seam) URH_HIP(hipMalloc((void **)&ss->d_seam, 64));
+    // rows [pos_base, pos_base + n_local) of afp_demod(whole capture): sample 0 of rank 0 is NOISE, a later rank's first FSK value comes from the
+    // halo's last sample; whole chunks of 8192 through the streaming kernel, the remainder through k_afp_demod (launch_afp_demod)
+    RunArgs a;
+    URH_TRY(hot_run_args(ctx, p, make_plan(ctx, n_local, p->tolerance), n_local, pos_base, true, &a));
+    a.in = d_iq; a.qad = out->qad; a.left_halo = d_left_halo;
+    const int64_t rows = (n_local + 511) / 512;
+    const int grid = (int)std::min<int64_t>(rows, (int64_t)ctx->prop.multiProcessorCount * 16);
+    URH_TRY(launch_afp_demod(a, p->dtype, p->mod, grid, ctx->stream));
+    if (rank > 0) URH_TRY(launch_afp_seam(a, p->dtype, p->mod, ss->d_seam, ctx->stream));
+    URH_HIP(hipGetLastError());
+    ss->demod_iq = d_iq; ss->demod_qad = out->qad; ss->demod_n = n_local;
+    ss->demod_mod = p->mod; ss->demod_dtype = p->dtype; ss->demod_noise = p->noise_threshold;
+    ss->demod_done = true;
+    return URHGPU_OK;
+}
+
+int urhgpu_shard_seam_value(urhgpu_ctx *ctx, float *seam) {
+    if (!ctx || !seam) return URHGPU_ERR_ARG;
+    ShardSession *ss = (ShardSession *)ctx->shard;
+    if (!ss || !ss->d_seam) return URHGPU_ERR_ARG;
+    URH_HIP(hipSetDevice(ctx->device));
+    URH_HIP(hipMemcpyAsync(seam, ss->d_seam, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    URH_HIP(hipStreamSynchronize(ctx->stream));
     return URHGPU_OK;
 }
 
@@ -313,6 +379,7 @@ int urhgpu_shard_costas_spec_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_lo
     ShardSession *ss = session(ctx);
     if (!ss) return URHGPU_ERR_ARG;
     ss->costas_phase = 0;
+    ss->demod_done = false;
     CostasShard &cs = ss->costas;
     cs.iq = d_iq; cs.n = n_local; cs.out = out->qad; cs.p = *p;
     cs.origin = (rank == 0) ? 1 : 0;

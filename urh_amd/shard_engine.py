@@ -316,6 +316,43 @@ class GpuShardEngine(DevicePipeline):
         """the center the pass's remaining phases (the pulse table) use instead of the parameters' own"""
         self._pre[2].center = float(center)
 
+    # ---- ASK / FSK: the demodulation phase on its own (sharding.py: iq_to_bits_auto; urhgpu_shard_demod_dev) ----
+    def demod_own(self, iq_local, left_halo=None):
+        """everything a rank can get wrong about the arguments of a pass that demodulates first, on its own: refused before anything is
+        exchanged (shape, sample type, device, contiguity, the halo handed over with the shard, a pipelined engine)"""
+        torch = self.torch
+        if self.tail_stream is not None:
+            raise ValueError("a pass that demodulates first runs on an engine that is not pipelined: GpuShardEngine(pipelined=False) "
+                             "(gathered values are read on the host between its phases)")
+        iq = torch.view_as_real(iq_local) if iq_local.dtype == torch.complex64 else iq_local
+        if iq.dim() != 2 or iq.shape[1] != 2:
+            raise ValueError("IQ must be an (N, 2) tensor or complex64 (N,)")
+        _torch_dtype(iq)
+        self._own(iq, "iq_to_bits_auto")
+        if left_halo is not None:
+            halo = self.halo_view(left_halo)
+            if halo.dtype != iq.dtype or halo.device != iq.device:
+                raise ValueError("left_halo: the two samples before the shard, in the shard's sample type and on its device")
+
+    def demod(self, iq_local, left, pos_base, n_total, rank, world, p):
+        """demodulate the shard once into the result's qad (left: the two raw samples before it, None on rank 0) and leave the seam value
+        -- the demodulated value of the sample before the shard -- on the device: `runs` then segments the qad"""
+        iq, n, cp, o = self._setup(iq_local, p, True, n_total)
+        self._pre = (iq, n, cp, o)
+        self._keep += (left,)
+        _lib.check(_lib.load().urhgpu_shard_demod_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, int(pos_base), int(n_total), int(rank), int(world),
+                                                      C.c_void_p(left.data_ptr()) if left is not None else None, C.byref(cp), C.byref(o)))
+
+    def demod_qad(self):
+        """the shard's demodulated signal (float32 (n_local,)) once `demod` has run: what an auto-center pass estimates from"""
+        return self._res.qad
+
+    def demod_seam(self):
+        """the seam value of the last `demod` on a rank > 0, read back (a numpy float32): tests and diagnostics"""
+        v = (C.c_float * 1)()
+        _lib.check(_lib.load().urhgpu_shard_seam_value(self.ctx.handle, v))
+        return np.frombuffer(v, dtype=np.float32)[0].copy()        # (the bits as they are: no trip through a Python float)
+
     # ---- the estimators' partial reductions (sharding.py: detect_noise_level / detect_center; csrc/shard_estimators.hip) ----
     def _own(self, t, what):
         """everything a rank can get wrong about a shard on its own, refused before anything is exchanged"""

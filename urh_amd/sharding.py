@@ -37,6 +37,22 @@ all-gathers (one for the noise level; four for the center: kept counts, two reco
 rank's global offset, histogram counts), every result a pure function of gathered data (`pairwise_combine`, `center_parts`).  A PSK
 pass detects its own center with `auto_center=True`.
 
+Automatic passes: `iq_to_bits_auto(auto_noise=..., auto_center=...)` opens a sharded capture the way DevicePipeline.iq_to_bits(auto_noise=True,
+auto_center=True) opens one on a single GPU -- the reference's defaults -- with the same bits.  auto_noise: `detect_noise_level` first (one
+all-gather more), the pass gates with its value; where that is not below the sample type's max_magnitude every rank raises ValueError, decided
+from the gathered value.  auto_center, PSK: as above.  auto_center, ASK and FSK -- whose fused hot kernel needs the center before the
+demodulated signal exists -- take a route of their own that demodulates every shard ONCE:
+
+    1. halo        as above (or handed over with the shard: halo_given)
+    2. demodulate  the shard into the result's qad (urhgpu_shard_demod_dev: the demodulation-only kernels), and from the halo's two raw samples
+                   the SEAM VALUE: the demodulated value of the sample before the shard, kept on the device
+    3. center      `detect_center` of the ranks' demodulated signals (four all-gathers at most); p.center where it finds none
+    4. summary / rows / flags as above, the runs segmented from the qad with that center (the qad-input kernels of the PSK pass), the seam
+                   value being the left halo: the ranks do not exchange their last demodulated values
+
+The route reads gathered values on the host and therefore refuses a pipelined engine, like PSK.  `last_auto` records the noise level, the
+center, whether it was detected, and the number of all-gathers.
+
 DC correction: `dc_correct` subtracts the mean of the WHOLE capture from every shard, bit-equal with numpy's `x - np.mean(x, axis=0)`.
 Integers: one all-gather of the ranks' exact int64 column sums.  float32: the mean is the strictly sequential float32 sum of the capture,
 carried across the ranks like the Costas state:
@@ -290,6 +306,21 @@ class RcclComm:
         kernel and picks the result up after it): enqueued right here, on the current stream"""
         out = self.all_gather(t)
         return lambda: out
+
+
+class _CountingComm:
+    """a communicator that counts the all-gathers passing through it (iq_to_bits_auto: `last_auto`)"""
+
+    def __init__(self, comm):
+        self.comm, self.rank, self.world, self.count = comm, comm.rank, comm.world, 0
+
+    def all_gather(self, t):
+        self.count += 1
+        return self.comm.all_gather(t)
+
+    def all_gather_start(self, t):
+        self.count += 1
+        return self.comm.all_gather_start(t)
 
 
 class ThreadComm:
@@ -758,6 +789,8 @@ class ShardedPipeline:
         self.last_center = None                  # the center the last pass's pulse table was built with (auto_center: the detected one)
         self.last_dc = None                      # the last dc_correct: mean, all-gathers, this rank's stitch statistics
         self.last_records = None                 # the last message_records: all-gathers, windows exchanged
+        self.last_auto = None                    # the last iq_to_bits_auto: noise, center, center_detected, all_gathers
+        self._center_found = False               # the last pass's pulse table was built with a center it detected
 
     # bench.py / DevicePipeline compatible surface ------------------------------------------------
     @property
@@ -965,7 +998,8 @@ class ShardedPipeline:
         Costas exchange has written it and builds its pulse table with the detected center (p.center where detection gives None);
         `last_center` is the value used.  ASK / FSK raise ValueError: their fused hot kernel needs the center before the demodulated
         signal exists.  The recipe there is two passes: one with want_qad=True, `detect_center(result.qad)`, then a second pass with
-        that center.
+        that center -- or `iq_to_bits_auto(auto_center=True)`, which demodulates the shard once, detects the center across the shards and
+        slices from the demodulated signal; it also takes auto_noise (every modulation).
         msg_records: refused (ValueError) as an option of the pass -- a message's middle window may lie in another rank's shard; the recipe is
         iq_to_bits, then `message_records` on the same shard and the pass's result.
         dc_correction: refused (ValueError) as an option of the pass; the recipe is `dc_correct` (the mean of the WHOLE capture, carried
@@ -1014,6 +1048,113 @@ class ShardedPipeline:
             merged_all = c.all_gather(merge) if merge is not None else None
             flags = e.bits_prepare(merged_all)
             return e.bits_finish(c.all_gather(flags))
+
+    def iq_to_bits_auto(self, iq_local, p, auto_noise=False, auto_center=False, center_max_size=None, want_qad=True, pos_base=None, n_total=None,
+                        halo_given=False, left_halo=None, left_raw=None):
+        """The pass of DevicePipeline.iq_to_bits(auto_noise=..., auto_center=..., center_max_size=...) on a sharded capture, bit for bit: the
+        same ShardResult as iq_to_bits (stitch, message_records, stitch_records and message_data work on it unchanged).  iq_local, pos_base,
+        n_total, halo_given / left_halo, left_raw (PSK), want_qad: as iq_to_bits.
+        auto_noise, auto_center and center_max_size MUST BE THE SAME ON EVERY RANK: they add collectives.
+        auto_noise: noise = detect_noise_level(iq_local, pos_base, n_total) -- one all-gather, the same value on every rank -- and the pass
+        runs with dataclasses.replace(p, noise_threshold=noise).  Where the noise level is not below the sample type's max_magnitude (compared
+        as doubles) the reference demodulates nothing (Signal.py:474-484): EVERY rank raises ValueError, decided from the gathered value, and
+        none enters a further collective.  What the reference raises for a level that is not a number (math.ceil) is raised on every rank alike.
+        auto_center: the pulse table is built with detect_center(demodulated signal of the WHOLE capture, center_max_size); p.center where
+        that gives None.  PSK: the PSK pass of iq_to_bits.  ASK / FSK: the shard is demodulated once into the result's qad together with the
+        seam value (the demodulated value of the sample before the shard, from the two raw samples of the halo), the center is detected
+        across the shards, and runs, rows and bits follow from the qad with that center (module docstring, "Automatic passes").  This route
+        needs want_qad=True and an engine that is not pipelined (ValueError otherwise: it reads gathered values on the host).
+        Without auto_center, ASK / FSK take the fused pass of iq_to_bits with the replaced parameters (a pipelined engine is fine there).
+        Modulations other than ASK, FSK and PSK raise ValueError.  Everything a rank can get wrong on its own is refused before the first
+        collective.  `last_center` is the center the pulse table was built with; `last_auto` = {"noise": the detected level or None,
+        "center": the center used, "center_detected": whether detect_center found it, "all_gathers": all-gathers of this call}.  ASK / FSK
+        with auto_center: the halo's unless halo_given, detect_center's, summaries + (ASK) merge + flags, one more with auto_noise."""
+        import dataclasses
+        from .sniffer import max_magnitude
+        e = self.engine
+        auto_noise, auto_center = bool(auto_noise), bool(auto_center)
+        mod = p.modulation_type
+        if mod not in ("ASK", "FSK", "PSK"):
+            raise ValueError(f"iq_to_bits_auto: ASK, FSK and PSK passes only (got {mod})")
+        if auto_center and not want_qad:
+            raise ValueError("auto_center needs the demodulated signal (want_qad=True)")
+        if center_max_size is not None and int(center_max_size) < 0:
+            raise ValueError("detect_center: max_size must not be negative")
+        n_local = int(iq_local.shape[0])
+        pos_base = self.rank * n_local if pos_base is None else int(pos_base)
+        n_total = self.world * n_local if n_total is None else int(n_total)
+        if pos_base < 0 or pos_base + n_local > n_total:
+            raise ValueError("iq_to_bits_auto: the shard does not lie inside the capture")
+        psk = mod == "PSK"
+        own_route = auto_center and not psk
+        # everything this rank can get wrong on its own, now: later refusals would leave the other ranks in a collective
+        if auto_noise:
+            self._estimator_engine("noise_partials")
+        if psk or own_route:
+            if n_total <= 2:
+                raise ValueError(f"{mod}: a capture of two samples or fewer does not shard")
+            if getattr(e, "tail_stream", None) is not None:
+                raise ValueError(f"{'PSK shards run' if psk else 'an ASK / FSK pass with auto_center runs'} on an engine that is not pipelined: "
+                                 "gathered values are read on the host between the phases")
+        if psk:
+            if auto_center:
+                self._estimator_engine("costas_qad", "set_center", "compact_gt", "pairwise_partial", "histogram")
+            if self.rank > 0:
+                need = costas_halo_samples(p.costas_loop_bandwidth, pos_base)
+                have = 0 if left_raw is None else int(left_raw.shape[0])
+                if have < need:
+                    raise ValueError(f"PSK: rank {self.rank} needs the {need} raw samples before its shard as left_raw (got {have})")
+        else:
+            if halo_given and self.rank > 0 and left_halo is None:
+                raise ValueError("halo_given: ranks > 0 pass the two samples before their shard as left_halo")
+            if own_route:
+                self._estimator_engine("demod_own", "demod", "demod_qad", "set_center", "compact_gt", "pairwise_partial", "histogram")
+                e.demod_own(iq_local, left_halo if (halo_given and self.rank > 0) else None)
+        counted = _CountingComm(self.comm)
+        self.comm, comm = counted, self.comm
+        try:
+            noise = None
+            if auto_noise:
+                noise = self.detect_noise_level(iq_local, pos_base, n_total)       # raises on every rank alike (gathered statistics)
+                dt = str(iq_local.dtype).replace("torch.", "")
+                limit = max_magnitude(np.float32 if dt == "complex64" else dt)
+                if not (float(noise) < float(limit)):                               # decided from the gathered value: every rank raises
+                    raise ValueError(f"iq_to_bits_auto: the detected noise level {float(noise)!r} is not below the sample type's max_magnitude "
+                                     f"{float(limit)!r}: the reference demodulates nothing of such a capture (Signal.quad_demod)")
+                p = dataclasses.replace(p, noise_threshold=noise)
+            self._center_found = False
+            if psk:
+                res = self._iq_to_bits_psk(iq_local, p, pos_base, n_total, left_raw, auto_center, center_max_size)
+            elif not own_route:
+                res = self.iq_to_bits(iq_local, p, want_qad=want_qad, pos_base=pos_base, n_total=n_total, halo_given=halo_given, left_halo=left_halo)
+            else:
+                res = self._iq_to_bits_demod_first(iq_local, p, pos_base, n_total, bool(halo_given), left_halo, center_max_size)
+        finally:
+            self.comm = comm
+        self.last_auto = {"noise": noise, "center": self.last_center, "center_detected": self._center_found, "all_gathers": counted.count}
+        return res
+
+    def _iq_to_bits_demod_first(self, iq_local, p, pos_base, n_total, halo_given, left_halo, center_max_size):
+        """ASK / FSK with auto_center (module docstring, "Automatic passes"); the caller has checked this rank's arguments"""
+        e, c = self.engine, self.comm
+        left = None
+        if halo_given:
+            if self.rank > 0:
+                left = e.halo_view(left_halo) if hasattr(e, "halo_view") else left_halo
+        else:
+            halos = c.all_gather(e.tail(iq_local, p))
+            left = halos[self.rank - 1] if self.rank > 0 else None
+        e.demod(iq_local, left, pos_base, n_total, self.rank, self.world, p)
+        self.last_center = p.center
+        center = self.detect_center(e.demod_qad(), center_max_size)
+        if center is not None:
+            self.last_center = float(center)
+            self._center_found = True
+            e.set_center(self.last_center)
+        summary = e.runs(iq_local, left, pos_base, n_total, self.rank, self.world, p, True)     # from the qad; its left halo is the seam value
+        merge = e.rows(c.all_gather(summary))
+        flags = e.bits_prepare(c.all_gather(merge) if merge is not None else None)
+        return e.bits_finish(c.all_gather(flags))
 
     def message_records(self, iq_local, result, p, message_length_divisor=1, pos_base=None, n_total=None):
         """One urhgpu_msg_record (protocol.RECORD_DTYPE) per message that closes on this rank, in order, as a numpy structured array: the
@@ -1073,7 +1214,7 @@ class ShardedPipeline:
         self.last_records = {"all_gathers": gathers, "windows": len(outside)}
         return rec
 
-    def _iq_to_bits_psk(self, iq_local, p, pos_base, n_total, left_raw, auto_center=False):
+    def _iq_to_bits_psk(self, iq_local, p, pos_base, n_total, left_raw, auto_center=False, center_max_size=None):
         """the PSK pass (module docstring, steps 0-4).  Everything a rank can get wrong on its own is checked before the first collective."""
         e, c = self.engine, self.comm
         if auto_center:
@@ -1097,9 +1238,10 @@ class ShardedPipeline:
         left = lasts[self.rank - 1] if self.rank > 0 else None
         self.last_center = p.center
         if auto_center:
-            center = self.detect_center(e.costas_qad())
+            center = self.detect_center(e.costas_qad(), center_max_size)
             if center is not None:
                 self.last_center = float(center)
+                self._center_found = True
                 e.set_center(self.last_center)
         summary = e.runs(iq_local, left, pos_base, n_total, self.rank, self.world, p, True)
         merge = e.rows(c.all_gather(summary))
