@@ -41,6 +41,27 @@ ShardSession *session(urhgpu_ctx *ctx) {
     return (ShardSession *)ctx->shard;
 }
 
+// the shard's place in the capture, as every entry point that opens a pass checks it: min_total is the shortest capture the route takes,
+// min_base_later_ranks the samples a rank > 0 needs in front of its shard
+int check_shard_geometry(int world, int rank, int64_t n_local, int64_t pos_base, int64_t n_total, int64_t min_total, int64_t min_base_later_ranks) {
+    if (world < 1 || world > kMaxWorld || rank < 0 || rank >= world || n_local < 2 || pos_base < 0 || pos_base + n_local > n_total ||
+        n_total < min_total)
+        return URHGPU_ERR_ARG;
+    return (rank == 0 ? pos_base != 0 : pos_base < min_base_later_ranks) ? URHGPU_ERR_ARG : URHGPU_OK;
+}
+
+// the stream of the phases behind the hot kernel
+hipStream_t tail_stream_of(const urhgpu_ctx *ctx, const ShardSession *ss) { return ss->piped ? ctx->tail_stream : ctx->stream; }
+
+// what bits_prepare and bits_finish tell the expansion kernels about this rank's place in the table
+BitsParams shard_bits_params(const ShardSession *ss) {
+    BitsParams bp = bits_params(&ss->p);
+    bp.d_row_base = ss->d_row_base; bp.d_ts_carry = ss->use_tile ? nullptr : ss->d_small;
+    bp.d_absorbed = (ss->p.mod == URHGPU_MOD_ASK) ? ss->d_small + 1 : nullptr;
+    bp.d_extra = (const int32_t *)(ss->d_small + 2); bp.is_last_rank = (ss->rank == ss->world - 1) ? 1 : 0;
+    return bp;
+}
+
 }  // namespace
 
 void urh::free_shard_session(urhgpu_ctx *ctx) {
@@ -57,9 +78,7 @@ extern "C" {
 static int shard_launch(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int64_t pos_base, int64_t n_total, int rank, int world,
                         const void *d_left_halo, const urhgpu_params *p, const urhgpu_outputs *out, int part) {
     if (!ctx || !p || !out || !d_iq || !out->rows || !out->counts) return URHGPU_ERR_ARG;
-    if (world < 1 || world > kMaxWorld || rank < 0 || rank >= world || n_local < 2 || pos_base < 0 || pos_base + n_local > n_total)
-        return URHGPU_ERR_ARG;
-    if (rank == 0 && pos_base != 0) return URHGPU_ERR_ARG;
+    URH_TRY(check_shard_geometry(world, rank, n_local, pos_base, n_total, 0, 0));
     if (dtype_bytes(p->dtype) == 0) return URHGPU_ERR_DTYPE;
     URH_TRY(check_params(p, true));
     if (((uintptr_t)d_iq & 15) || (out->qad && ((uintptr_t)out->qad & 7))) return URHGPU_ERR_ARG;
@@ -161,7 +180,7 @@ int urhgpu_shard_runs_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, in
         // prelaunched: only the first chunk (it needs the halo) is still missing, or (-2) nothing
         if (ss->rank != rank || ss->world != world || ss->n_local != n_local || ss->run.in != d_iq) return URHGPU_ERR_ARG;
         URH_HIP(hipSetDevice(ctx->device));
-        s = ss->piped ? ctx->tail_stream : ctx->stream;
+        s = tail_stream_of(ctx, ss);
         if (rank > 0 && ss->phase == -1) {
             RunArgs a = ss->run;
             a.left_halo = d_left_halo; a.launch_part = 2;
@@ -170,7 +189,7 @@ int urhgpu_shard_runs_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, in
     } else {
         URH_TRY(shard_launch(ctx, d_iq, n_local, pos_base, n_total, rank, world, d_left_halo, p, out, 0));
         ss = (ShardSession *)ctx->shard;
-        s = ss->piped ? ctx->tail_stream : ctx->stream;      // pipelined: shard_launch made the tail stream wait for the hot kernel
+        s = tail_stream_of(ctx, ss);      // pipelined: shard_launch made the tail stream wait for the hot kernel
     }
     // local resolve pass: the shard on its own -> its summary
     const Plan &pl = ss->pl;
@@ -194,9 +213,7 @@ int urhgpu_shard_runs_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, in
 int urhgpu_shard_demod_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int64_t pos_base, int64_t n_total, int rank, int world,
                            const void *d_left_halo, const urhgpu_params *p, const urhgpu_outputs *out) {
     if (!ctx || !p || !out || !d_iq || !out->qad || !out->rows || !out->counts) return URHGPU_ERR_ARG;
-    if (world < 1 || world > kMaxWorld || rank < 0 || rank >= world || n_local < 2 || pos_base < 0 || pos_base + n_local > n_total || n_total <= 2)
-        return URHGPU_ERR_ARG;
-    if (rank == 0 ? pos_base != 0 : pos_base < 1) return URHGPU_ERR_ARG;
+    URH_TRY(check_shard_geometry(world, rank, n_local, pos_base, n_total, 3, 1));
     if ((rank == 0) != (d_left_halo == nullptr)) return URHGPU_ERR_ARG;
     if (dtype_bytes(p->dtype) == 0) return URHGPU_ERR_DTYPE;
     if (p->mod != URHGPU_MOD_ASK && p->mod != URHGPU_MOD_FSK) return URHGPU_ERR_UNSUPPORTED;      // (PSK has its Costas phases)
@@ -242,7 +259,7 @@ int urhgpu_shard_rows_dev(urhgpu_ctx *ctx, const void *d_summaries, int64_t *d_m
     ShardSession *ss = (ShardSession *)ctx->shard;
     if (!ss || ss->phase != 1) return URHGPU_ERR_ARG;
     URH_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ss->piped ? ctx->tail_stream : ctx->stream;
+    hipStream_t s = tail_stream_of(ctx, ss);
     const int rank = ss->rank, world = ss->world;
     const Plan &pl = ss->pl;
     const bool ask = (ss->p.mod == URHGPU_MOD_ASK);
@@ -298,16 +315,13 @@ int urhgpu_shard_bits_prepare_dev(urhgpu_ctx *ctx, const int64_t *d_merge_all, i
     if (ask && !d_merge_all) return URHGPU_ERR_ARG;
     if (!ss->out.bits || !ss->out.msg_off || !ss->out.pauses || !ss->out.pos_off) return URHGPU_ERR_ARG;
     URH_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ss->piped ? ctx->tail_stream : ctx->stream;
+    hipStream_t s = tail_stream_of(ctx, ss);
     int64_t *d_n_rows = ss->d_small + 3;
     if (ask) launch_merge_fix(ss->out.rows, d_n_rows, d_merge_all, ss->rank, ss->world, ss->d_small + 1, s);
-    BitsParams bp = bits_params(&ss->p);
-    bp.d_row_base = ss->d_row_base; bp.d_ts_carry = ss->d_small; bp.d_absorbed = ask ? ss->d_small + 1 : nullptr;
-    bp.d_extra = (const int32_t *)(ss->d_small + 2); bp.is_last_rank = (ss->rank == ss->world - 1) ? 1 : 0;
+    const BitsParams bp = shard_bits_params(ss);
     ScanState sst;
     const int64_t cap = std::max<int64_t>(ss->out.cap_rows, 1);
     if (ss->use_tile) {
-        bp.d_ts_carry = nullptr;
         URH_TRY(scan_state(ctx, tile_desc_cap(cap, ss->tile.n_chunks), &sst));
         URH_TRY(launch_tile_bits_prepare(ss->tile, ss->out.rows, d_n_rows, cap, bp, ss->bits_scratch, d_flags, sst, s));
     } else {
@@ -324,19 +338,15 @@ int urhgpu_shard_bits_finish_dev(urhgpu_ctx *ctx, const int64_t *d_flags_all) {
     ShardSession *ss = (ShardSession *)ctx->shard;
     if (!ss || ss->phase != 3) return URHGPU_ERR_ARG;
     URH_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ss->piped ? ctx->tail_stream : ctx->stream;
-    const bool ask = (ss->p.mod == URHGPU_MOD_ASK);
+    hipStream_t s = tail_stream_of(ctx, ss);
     launch_bits_extra(d_flags_all, ss->rank, ss->world, (int32_t *)(ss->d_small + 2), s);
-    BitsParams bp = bits_params(&ss->p);
-    bp.d_row_base = ss->d_row_base; bp.d_ts_carry = ss->d_small; bp.d_absorbed = ask ? ss->d_small + 1 : nullptr;
-    bp.d_extra = (const int32_t *)(ss->d_small + 2); bp.is_last_rank = (ss->rank == ss->world - 1) ? 1 : 0;
+    BitsParams bp = shard_bits_params(ss);
     bp.d_rows_needed = ctx->d_counts + 8;
     const urhgpu_outputs &o = ss->out;
     BitsOut bo{o.bits, o.cap_bits, o.msg_off, o.pauses, o.cap_msg, o.pos, o.cap_pos, o.pos_off, o.counts};
     ScanState sst;
     const int64_t cap = std::max<int64_t>(o.cap_rows, 1);
     if (ss->use_tile) {
-        bp.d_ts_carry = nullptr;
         URH_TRY(scan_state(ctx, tile_desc_cap(cap, ss->tile.n_chunks), &sst));
         URH_TRY(launch_tile_bits_finish(ss->tile, o.rows, ss->d_small + 3, cap, bp, bo, ss->bits_scratch, sst, s));
     } else {
@@ -362,10 +372,7 @@ int64_t urhgpu_costas_halo_samples(const urhgpu_params *p) {
 int urhgpu_shard_costas_spec_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_local, int64_t pos_base, int64_t n_total, int rank, int world,
                                  const void *d_halo, int64_t n_halo, const urhgpu_params *p, const urhgpu_outputs *out, void *d_summary) {
     if (!ctx || !p || !out || !d_iq || !out->qad || !d_summary) return URHGPU_ERR_ARG;
-    if (world < 1 || world > kMaxWorld || rank < 0 || rank >= world || n_local < 2 || pos_base < 0 || pos_base + n_local > n_total ||
-        n_total <= 2)
-        return URHGPU_ERR_ARG;
-    if (rank == 0 ? pos_base != 0 : pos_base < 2) return URHGPU_ERR_ARG;
+    URH_TRY(check_shard_geometry(world, rank, n_local, pos_base, n_total, 3, 2));
     if (p->mod != URHGPU_MOD_PSK) return URHGPU_ERR_ARG;
     if (dtype_bytes(p->dtype) == 0) return URHGPU_ERR_DTYPE;
     URH_TRY(check_params(p, true));

@@ -1,5 +1,5 @@
 """Per-rank GPU engine of the sharded IQ->bits pass: the four urhgpu_shard_* phases of liburhgpu.so
-(include/urhgpu.h) behind the engine interface urh_amd/sharding.py orchestrates.  torch is plumbing
+(include/urhgpu.h) behind the engine interface urh_amd/sharding/pipeline.py orchestrates.  torch is plumbing
 (device buffers, the stream, the tensors the all-gathers move); all arithmetic is in the HIP kernels."""
 import ctypes as C
 
@@ -147,49 +147,79 @@ class GpuShardEngine(DevicePipeline):
         return HostBits.from_blob(hblob.data_ptr(), params, n_samples=int(qad.shape[0]) if qad is not None else 0,
                                   d_qad=qad.data_ptr() if qad is not None else 0)
 
+    # ---- plumbing shared by the phases ----
+    def _rows_view(self, t, what=None, own=True):
+        """(n, 2) view of a tensor of a sample type, (n, 2) or complex64 (n,), and its numpy dtype.  what None: the view alone (no dtype).
+        what given: shape and sample type are checked and, with own, what else a rank can get wrong about a shard on its own (`_own`)"""
+        iq = self.torch.view_as_real(t) if t.dtype == self.torch.complex64 else t
+        if what is None:
+            return iq, None
+        if iq.dim() != 2 or iq.shape[1] != 2:
+            raise ValueError("IQ must be an (N, 2) tensor or complex64 (N,)")
+        npdt = _torch_dtype(iq)
+        if own:
+            self._own(iq, what)
+        return iq, npdt
+
+    def _own(self, t, what):
+        """everything a rank can get wrong about a shard on its own, refused before anything is exchanged"""
+        if not t.is_cuda or t.device != self.device:
+            raise ValueError(f"{what}: the shard lies on {t.device}, the engine runs on {self.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: the shard must be contiguous")
+
+    @staticmethod
+    def _outputs(qad, rows, bits, msg_off, pauses, pos, pos_off, counts):
+        """the C descriptor of a result's buffers, the capacities being their lengths"""
+        o = _lib.Outputs()
+        o.qad = qad.data_ptr() if qad is not None else None
+        o.rows = rows.data_ptr(); o.cap_rows = int(rows.shape[0])
+        o.bits = bits.data_ptr(); o.cap_bits = int(bits.shape[0])
+        o.msg_off = msg_off.data_ptr(); o.pauses = pauses.data_ptr(); o.cap_msg = int(pauses.shape[0])
+        o.pos = pos.data_ptr() if pos is not None else None
+        o.cap_pos = int(pos.shape[0]) if pos is not None else 0
+        o.pos_off = pos_off.data_ptr()
+        o.counts = counts.data_ptr()
+        return o
+
+    def _call(self, fn_name, *args, set_stream=True):
+        """one call into the library on this engine's context, its return code checked.  set_stream: the context works on the current torch
+        stream; False for the phases of a pass, which keep the streams its `_setup` chose (they run under tail_context)"""
+        if set_stream:
+            self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(getattr(_lib.load(), fn_name)(self.ctx.handle, *args))
+
     def tail(self, iq_local, p):
-        torch = self.torch
-        if iq_local.dtype == torch.complex64:
-            iq_local = torch.view_as_real(iq_local)
-        return iq_local[-2:].contiguous()                     # (2, 2): samples n-2, n-1
+        return self._rows_view(iq_local)[0][-2:].contiguous()  # (2, 2): samples n-2, n-1
 
     def halo_view(self, left_halo):
         """(2, 2) view of a caller-provided halo (complex64 (2,) or (2, 2) in the capture's dtype)"""
-        torch = self.torch
-        if left_halo.dtype == torch.complex64:
-            left_halo = torch.view_as_real(left_halo)
+        left_halo, _ = self._rows_view(left_halo)
         if tuple(left_halo.shape) != (2, 2):
             raise ValueError("left_halo: the two samples before the shard, shape (2, 2)")
         return left_halo.contiguous()
 
     def fir_tail(self, iq_local, k):
-        torch = self.torch
-        if iq_local.dtype == torch.complex64:
-            iq_local = torch.view_as_real(iq_local)
-        return iq_local[-k:].contiguous()
+        return self._rows_view(iq_local)[0][-k:].contiguous()
 
     def fir(self, iq_local, taps, left):
         """complex64 FIR of this shard (float32 (N, 2) or complex64 (N,)) with `left` (the m-1 preceding samples) as history"""
         torch = self.torch
-        x = torch.view_as_real(iq_local) if iq_local.dtype == torch.complex64 else iq_local
-        h = torch.view_as_real(taps) if taps.dtype == torch.complex64 else taps
+        x, h = self._rows_view(iq_local)[0], self._rows_view(taps)[0]
         if x.dtype != torch.float32 or h.dtype != torch.float32 or not x.is_contiguous():
             raise ValueError("FIR needs contiguous float32 / complex64 samples and taps")
         if h.dim() != 2 or h.shape[1] != 2:
             raise ValueError("taps: complex64 (m,) or float32 (m, 2)")          # a flat float32 vector would be read as twice the taps
         h = h.contiguous()
         out = torch.empty_like(x)
-        self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(_lib.load().urhgpu_fir_filter_dev(self.ctx.handle, C.c_void_p(x.data_ptr()), x.shape[0], C.c_void_p(h.data_ptr()),
-                                                     h.shape[0], C.c_void_p(left.data_ptr()) if left is not None else None,
-                                                     C.c_void_p(out.data_ptr())))
+        self._call("urhgpu_fir_filter_dev", C.c_void_p(x.data_ptr()), x.shape[0], C.c_void_p(h.data_ptr()), h.shape[0],
+                   C.c_void_p(left.data_ptr()) if left is not None else None, C.c_void_p(out.data_ptr()))
         self._fir_keep = (x, h, left)
         return out if iq_local.dtype != torch.complex64 else torch.view_as_complex(out)
 
     def _setup(self, iq, p, want_qad, n_total=0):
         torch = self.torch
-        if iq.dtype == torch.complex64:
-            iq = torch.view_as_real(iq)
+        iq, _ = self._rows_view(iq)
         if iq.dim() != 2 or iq.shape[1] != 2 or not iq.is_contiguous():
             raise ValueError("IQ must be a contiguous (N, 2) tensor")
         npdt = _torch_dtype(iq)
@@ -209,15 +239,7 @@ class GpuShardEngine(DevicePipeline):
         pos_off = self._buf("pos_off", (cap_msg + 1,), torch.int64)
         pos = self._buf("pos", (cap_pos,), torch.int64) if p.write_bit_sample_pos else None
         counts = self._buf("counts", (5,), torch.int64)
-        o = _lib.Outputs()
-        o.qad = qad.data_ptr() if qad is not None else None
-        o.rows = rows.data_ptr(); o.cap_rows = cap_rows
-        o.bits = bits.data_ptr(); o.cap_bits = cap_bits
-        o.msg_off = msg_off.data_ptr(); o.pauses = pauses.data_ptr(); o.cap_msg = cap_msg
-        o.pos = pos.data_ptr() if pos is not None else None
-        o.cap_pos = cap_pos if pos is not None else 0
-        o.pos_off = pos_off.data_ptr()
-        o.counts = counts.data_ptr()
+        o = self._outputs(qad, rows, bits, msg_off, pauses, pos, pos_off, counts)
         self._hslot = None
         if self.host_results:
             k, cap = self._host_slot(cap_rows, cap_bits, cap_msg, cap_pos if pos is not None else 0, pos is not None)
@@ -229,44 +251,39 @@ class GpuShardEngine(DevicePipeline):
         self._res = ShardResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, self.ctx)
         self._ask = p.modulation_type == "ASK"
         self._keep = (iq,)                                     # keep the inputs alive until the pass is over
+        # here and not at every phase: the phases behind the hot launch run under tail_context, where the current stream is the tail stream
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
-        return iq, n, cp, o
+        self._pre = (iq, n, cp, o)                             # the pass as set up, until `runs` takes it
+        return self._pre
 
     def runs_begin(self, iq, pos_base, n_total, rank, world, p, want_qad):
         """start the hot kernel on every chunk but the first while the halo all-gather is still in flight"""
         iq, n, cp, o = self._setup(iq, p, want_qad, n_total)
-        self._pre = (iq, n, cp, o)
-        _lib.check(_lib.load().urhgpu_shard_prelaunch_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, int(pos_base), int(n_total),
-                                                          int(rank), int(world), C.byref(cp), C.byref(o)))
+        self._call("urhgpu_shard_prelaunch_dev", C.c_void_p(iq.data_ptr()), n, int(pos_base), int(n_total), int(rank), int(world), C.byref(cp),
+                   C.byref(o), set_stream=False)
 
     def runs_launch(self, iq, left, pos_base, n_total, rank, world, p, want_qad):
         """the whole hot launch: the halo came with the shard (no exchange)"""
         iq, n, cp, o = self._setup(iq, p, want_qad, n_total)
-        self._pre = (iq, n, cp, o)
         self._keep += (left,)
-        _lib.check(_lib.load().urhgpu_shard_launch_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, int(pos_base), int(n_total),
-                                                       int(rank), int(world), C.c_void_p(left.data_ptr()) if left is not None else None,
-                                                       C.byref(cp), C.byref(o)))
+        self._call("urhgpu_shard_launch_dev", C.c_void_p(iq.data_ptr()), n, int(pos_base), int(n_total), int(rank), int(world),
+                   C.c_void_p(left.data_ptr()) if left is not None else None, C.byref(cp), C.byref(o), set_stream=False)
 
     def runs(self, iq, left, pos_base, n_total, rank, world, p, want_qad):
         torch = self.torch
-        pre = getattr(self, "_pre", None)
-        if pre is not None:
-            iq, n, cp, o = pre
-            self._pre = None
-        else:
-            iq, n, cp, o = self._setup(iq, p, want_qad, n_total)
+        if getattr(self, "_pre", None) is None:                 # no hot launch, Costas or demodulation phase has set the pass up
+            self._setup(iq, p, want_qad, n_total)
+        (iq, n, cp, o), self._pre = self._pre, None
         self._keep += (left,)
         if left is not None and getattr(self, "tail_stream", None) is not None:
             left.record_stream(self.tail_stream)                # gathered under the caller's stream, read by the first chunk on the tail stream
         summary = self._buf("summary", (9,), torch.int64)      # URHGPU_SHARD_SUMMARY_BYTES = 72
         lh = C.c_void_p(left.data_ptr()) if left is not None else None
-        _lib.check(_lib.load().urhgpu_shard_runs_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, int(pos_base), int(n_total),
-                                                     int(rank), int(world), lh, C.byref(cp), C.byref(o),
-                                                     C.c_void_p(summary.data_ptr())))
+        self._call("urhgpu_shard_runs_dev", C.c_void_p(iq.data_ptr()), n, int(pos_base), int(n_total), int(rank), int(world), lh, C.byref(cp),
+                   C.byref(o), C.c_void_p(summary.data_ptr()), set_stream=False)
         return summary
 
-    # ---- PSK: the Costas loop across shards (sharding.py, steps 1-4; include/urhgpu.h) ----
+    # ---- PSK: the Costas loop across shards (sharding/costas.py, steps 1-4; include/urhgpu.h) ----
     def costas_spec(self, iq_local, left_raw, pos_base, n_total, rank, world, p):
         """speculate the shard (its first chunk warms up in left_raw, the raw samples before it; None on rank 0) -> the summary
         (uint8 device tensor of COSTAS_SUMMARY_BYTES)"""
@@ -275,10 +292,9 @@ class GpuShardEngine(DevicePipeline):
         if self.tail_stream is not None:
             raise ValueError("PSK shards run on an engine that is not pipelined: GpuShardEngine(pipelined=False)")
         iq, n, cp, o = self._setup(iq_local, p, True, n_total)    # the qad always: the runs phase segments it
-        self._pre = (iq, n, cp, o)
         halo = None
         if left_raw is not None:
-            halo = torch.view_as_real(left_raw) if left_raw.dtype == torch.complex64 else left_raw
+            halo, _ = self._rows_view(left_raw)
             if halo.dtype != iq.dtype or halo.dim() != 2 or halo.shape[1] != 2:
                 raise ValueError("left_raw: raw samples in the shard's dtype, (m, 2) or complex64 (m,)")
             halo = halo.contiguous()
@@ -286,16 +302,15 @@ class GpuShardEngine(DevicePipeline):
         summary = self._buf("costas_summary", (COSTAS_SUMMARY_BYTES,), torch.uint8)
         self._costas_end = self._buf("costas_end", (2,), torch.int32)
         self._costas_end.zero_()
-        _lib.check(_lib.load().urhgpu_shard_costas_spec_dev(
-            self.ctx.handle, C.c_void_p(iq.data_ptr()), n, int(pos_base), int(n_total), int(rank), int(world),
-            C.c_void_p(halo.data_ptr()) if halo is not None else None, int(halo.shape[0]) if halo is not None else 0,
-            C.byref(cp), C.byref(o), C.c_void_p(summary.data_ptr())))
+        self._call("urhgpu_shard_costas_spec_dev", C.c_void_p(iq.data_ptr()), n, int(pos_base), int(n_total), int(rank), int(world),
+                   C.c_void_p(halo.data_ptr()) if halo is not None else None, int(halo.shape[0]) if halo is not None else 0,
+                   C.byref(cp), C.byref(o), C.c_void_p(summary.data_ptr()), set_stream=False)
         return summary
 
     def costas_resolve(self, start):
         """stitch the shard from its true start state (freq bits, phase bits) and write its qad"""
         st = (C.c_uint32 * 2)(int(start[0]), int(start[1]))
-        _lib.check(_lib.load().urhgpu_shard_costas_resolve_dev(self.ctx.handle, st, C.c_void_p(self._costas_end.data_ptr())))
+        self._call("urhgpu_shard_costas_resolve_dev", st, C.c_void_p(self._costas_end.data_ptr()), set_stream=False)
 
     def costas_end(self):
         """the shard's true end state (2 x int32: float32 bits) once it has resolved, zeros before"""
@@ -316,19 +331,14 @@ class GpuShardEngine(DevicePipeline):
         """the center the pass's remaining phases (the pulse table) use instead of the parameters' own"""
         self._pre[2].center = float(center)
 
-    # ---- ASK / FSK: the demodulation phase on its own (sharding.py: iq_to_bits_auto; urhgpu_shard_demod_dev) ----
+    # ---- ASK / FSK: the demodulation phase on its own (sharding/pipeline.py: iq_to_bits_auto; urhgpu_shard_demod_dev) ----
     def demod_own(self, iq_local, left_halo=None):
         """everything a rank can get wrong about the arguments of a pass that demodulates first, on its own: refused before anything is
         exchanged (shape, sample type, device, contiguity, the halo handed over with the shard, a pipelined engine)"""
-        torch = self.torch
         if self.tail_stream is not None:
             raise ValueError("a pass that demodulates first runs on an engine that is not pipelined: GpuShardEngine(pipelined=False) "
                              "(gathered values are read on the host between its phases)")
-        iq = torch.view_as_real(iq_local) if iq_local.dtype == torch.complex64 else iq_local
-        if iq.dim() != 2 or iq.shape[1] != 2:
-            raise ValueError("IQ must be an (N, 2) tensor or complex64 (N,)")
-        _torch_dtype(iq)
-        self._own(iq, "iq_to_bits_auto")
+        iq, _ = self._rows_view(iq_local, "iq_to_bits_auto")
         if left_halo is not None:
             halo = self.halo_view(left_halo)
             if halo.dtype != iq.dtype or halo.device != iq.device:
@@ -338,10 +348,9 @@ class GpuShardEngine(DevicePipeline):
         """demodulate the shard once into the result's qad (left: the two raw samples before it, None on rank 0) and leave the seam value
         -- the demodulated value of the sample before the shard -- on the device: `runs` then segments the qad"""
         iq, n, cp, o = self._setup(iq_local, p, True, n_total)
-        self._pre = (iq, n, cp, o)
         self._keep += (left,)
-        _lib.check(_lib.load().urhgpu_shard_demod_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, int(pos_base), int(n_total), int(rank), int(world),
-                                                      C.c_void_p(left.data_ptr()) if left is not None else None, C.byref(cp), C.byref(o)))
+        self._call("urhgpu_shard_demod_dev", C.c_void_p(iq.data_ptr()), n, int(pos_base), int(n_total), int(rank), int(world),
+                   C.c_void_p(left.data_ptr()) if left is not None else None, C.byref(cp), C.byref(o), set_stream=False)
 
     def demod_qad(self):
         """the shard's demodulated signal (float32 (n_local,)) once `demod` has run: what an auto-center pass estimates from"""
@@ -350,32 +359,18 @@ class GpuShardEngine(DevicePipeline):
     def demod_seam(self):
         """the seam value of the last `demod` on a rank > 0, read back (a numpy float32): tests and diagnostics"""
         v = (C.c_float * 1)()
-        _lib.check(_lib.load().urhgpu_shard_seam_value(self.ctx.handle, v))
+        self._call("urhgpu_shard_seam_value", v, set_stream=False)
         return np.frombuffer(v, dtype=np.float32)[0].copy()        # (the bits as they are: no trip through a Python float)
 
-    # ---- the estimators' partial reductions (sharding.py: detect_noise_level / detect_center; csrc/shard_estimators.hip) ----
-    def _own(self, t, what):
-        """everything a rank can get wrong about a shard on its own, refused before anything is exchanged"""
-        if not t.is_cuda or t.device != self.device:
-            raise ValueError(f"{what}: the shard lies on {t.device}, the engine runs on {self.device}")
-        if not t.is_contiguous():
-            raise ValueError(f"{what}: the shard must be contiguous")
-        self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
-
+    # ---- the estimators' partial reductions (sharding/pipeline.py: detect_noise_level / detect_center; csrc/shard_estimators.hip) ----
     def noise_partials(self, iq_local, pos_base, n_total, chunk, n_chunks):
         """float64 (2, n_chunks): fp64 sum and max of the magnitudes of the intersection of every chunk with the shard"""
         from .signal_functions import dtype_code
-        torch = self.torch
-        iq = torch.view_as_real(iq_local) if iq_local.dtype == torch.complex64 else iq_local
-        if iq.dim() != 2 or iq.shape[1] != 2:
-            raise ValueError("IQ must be an (N, 2) tensor or complex64 (N,)")
-        code = dtype_code(_torch_dtype(iq))
-        self._own(iq, "detect_noise_level")
-        out = torch.empty((2, int(n_chunks)), dtype=torch.float64, device=self.device)
+        iq, npdt = self._rows_view(iq_local, "detect_noise_level")
+        out = self.torch.empty((2, int(n_chunks)), dtype=self.torch.float64, device=self.device)
         if n_chunks:
-            _lib.check(_lib.load().urhgpu_magnitude_chunk_partials_dev(
-                self.ctx.handle, C.c_void_p(iq.data_ptr()), code, int(iq.shape[0]), int(pos_base), int(n_total), int(chunk), int(n_chunks),
-                C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr())))
+            self._call("urhgpu_magnitude_chunk_partials_dev", C.c_void_p(iq.data_ptr()), dtype_code(npdt), int(iq.shape[0]), int(pos_base),
+                       int(n_total), int(chunk), int(n_chunks), C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()))
         out._urh_keep = iq
         return out
 
@@ -388,41 +383,35 @@ class GpuShardEngine(DevicePipeline):
         n = int(x.shape[0])
         kept = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
         cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
-        _lib.check(_lib.load().urhgpu_compact_gt_dev(self.ctx.handle, C.c_void_p(x.data_ptr()), n, float(thr), C.c_void_p(kept.data_ptr()),
-                                                     C.c_void_p(cnt.data_ptr())))
+        self._call("urhgpu_compact_gt_dev", C.c_void_p(x.data_ptr()), n, float(thr), C.c_void_p(kept.data_ptr()), C.c_void_p(cnt.data_ptr()))
         kept._urh_keep = x
         return kept, cnt
 
     def pairwise_partial(self, x, g_off, m_total, mode, mean, words):
         """the record of urhgpu_pairwise_partial_f32_dev for x = elements [g_off, g_off + len(x)) of a sequence of m_total, padded with
         zeros to `words` float32 (every rank gathers the same shape)"""
-        torch = self.torch
-        self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
-        rec = torch.zeros(int(words), dtype=torch.float32, device=self.device)
+        rec = self.torch.zeros(int(words), dtype=self.torch.float32, device=self.device)
         n_out = C.c_int64(0)
-        _lib.check(_lib.load().urhgpu_pairwise_partial_f32_dev(self.ctx.handle, C.c_void_p(x.data_ptr()) if x.numel() else None, int(x.shape[0]),
-                                                               int(g_off), int(m_total), int(mode), float(mean), C.c_void_p(rec.data_ptr()),
-                                                               int(words), C.byref(n_out)))
+        self._call("urhgpu_pairwise_partial_f32_dev", C.c_void_p(x.data_ptr()) if x.numel() else None, int(x.shape[0]), int(g_off), int(m_total),
+                   int(mode), float(mean), C.c_void_p(rec.data_ptr()), int(words), C.byref(n_out))
         rec._urh_keep = x
         return rec
 
     def histogram(self, x, edges):
         """np.histogram(x, bins=edges) of the rank's elements: int64 (len(edges) - 1,) on the device"""
         torch = self.torch
-        self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
         d_edges = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.float64)).to(self.device)
         counts = torch.empty(len(edges) - 1, dtype=torch.int64, device=self.device)
-        _lib.check(_lib.load().urhgpu_histogram_f32_dev(self.ctx.handle, C.c_void_p(x.data_ptr()) if x.numel() else None, int(x.shape[0]),
-                                                        C.c_void_p(d_edges.data_ptr()), len(edges), C.c_void_p(counts.data_ptr())))
+        self._call("urhgpu_histogram_f32_dev", C.c_void_p(x.data_ptr()) if x.numel() else None, int(x.shape[0]), C.c_void_p(d_edges.data_ptr()),
+                   len(edges), C.c_void_p(counts.data_ptr()))
         counts._urh_keep = (x, d_edges)
         return counts
 
-    # ---- DC correction across the shards (sharding.py: dc_correct; csrc/dc_correct.hip, "sharded captures") ----
+    # ---- DC correction across the shards (sharding/pipeline.py: dc_correct; csrc/dc_correct.hip, "sharded captures") ----
     def _dc_rows(self, t, what):
         """(n, 2) view of a tensor of a sample type or complex64 (n,), and its dtype code"""
         from .filter import _TORCH_CODES
-        torch = self.torch
-        x = torch.view_as_real(t) if t.dtype == torch.complex64 else t
+        x, _ = self._rows_view(t)
         code = _TORCH_CODES.get(str(x.dtype))
         if code is None:
             raise ValueError(f"{what}: Unsupported dtype {x.dtype}")
@@ -453,10 +442,8 @@ class GpuShardEngine(DevicePipeline):
     def dc_sums(self, iq_local):
         """int64 (3,): n_local and the two column sums (float32 captures: the bits of two float64 sums)"""
         x, code = self._dc_rows(iq_local, "dc_correct")
-        self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
         words = self.torch.empty(3, dtype=self.torch.int64, device=self.device)
-        _lib.check(_lib.load().urhgpu_shard_dc_sums_dev(self.ctx.handle, C.c_void_p(x.data_ptr()) if x.shape[0] else None, int(x.shape[0]), code,
-                                                        C.c_void_p(words.data_ptr())))
+        self._call("urhgpu_shard_dc_sums_dev", C.c_void_p(x.data_ptr()) if x.shape[0] else None, int(x.shape[0]), code, C.c_void_p(words.data_ptr()))
         words._urh_keep = x
         self._dc_single = None
         return words
@@ -464,10 +451,9 @@ class GpuShardEngine(DevicePipeline):
     def dc_spec(self, iq_local, base):
         """int32 (2, 2, 4): the shard's records [column][path] {entry, exit, room, flags}, speculated from the float64 sums in front"""
         x, _ = self._dc_rows(iq_local, "dc_correct")
-        self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
         recs = self.torch.empty((2, 2, 4), dtype=self.torch.int32, device=self.device)
-        _lib.check(_lib.load().urhgpu_shard_dc_spec_dev(self.ctx.handle, C.c_void_p(x.data_ptr()) if x.shape[0] else None, int(x.shape[0]),
-                                                        (C.c_double * 2)(float(base[0]), float(base[1])), C.c_void_p(recs.data_ptr())))
+        self._call("urhgpu_shard_dc_spec_dev", C.c_void_p(x.data_ptr()) if x.shape[0] else None, int(x.shape[0]),
+                   (C.c_double * 2)(float(base[0]), float(base[1])), C.c_void_p(recs.data_ptr()))
         recs._urh_keep = x
         return recs
 
@@ -477,9 +463,8 @@ class GpuShardEngine(DevicePipeline):
         out = self.torch.zeros(2, dtype=self.torch.int32, device=self.device)
         if entry is not None:
             x, _ = self._dc_rows(iq_local, "dc_correct")
-            self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(_lib.load().urhgpu_shard_dc_resolve_dev(self.ctx.handle, C.c_void_p(x.data_ptr()) if x.shape[0] else None, int(x.shape[0]),
-                                                               (C.c_uint32 * 2)(int(entry[0]), int(entry[1])), C.c_void_p(out.data_ptr())))
+            self._call("urhgpu_shard_dc_resolve_dev", C.c_void_p(x.data_ptr()) if x.shape[0] else None, int(x.shape[0]),
+                       (C.c_uint32 * 2)(int(entry[0]), int(entry[1])), C.c_void_p(out.data_ptr()))
             out._urh_keep = x
         return out
 
@@ -487,67 +472,47 @@ class GpuShardEngine(DevicePipeline):
         """t minus the mean (host: two float32 for float32 samples, two float64 otherwise), into a new tensor or t itself"""
         x, code = self._dc_rows(t, "dc_correct")
         res = self.torch.empty_like(t) if out is None else out
-        y = self.torch.view_as_real(res) if res.dtype == self.torch.complex64 else res
+        y, _ = self._rows_view(res)
         m = np.ascontiguousarray(mean, dtype=np.float32 if code == _lib.DT_F32 else np.float64)
-        self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(_lib.load().urhgpu_shard_dc_apply_dev(self.ctx.handle, C.c_void_p(x.data_ptr()) if x.shape[0] else None, int(x.shape[0]), code,
-                                                         C.c_void_p(m.ctypes.data), C.c_void_p(y.data_ptr()) if x.shape[0] else None))
+        self._call("urhgpu_shard_dc_apply_dev", C.c_void_p(x.data_ptr()) if x.shape[0] else None, int(x.shape[0]), code, C.c_void_p(m.ctypes.data),
+                   C.c_void_p(y.data_ptr()) if x.shape[0] else None)
         res._urh_keep = x
         return res
 
     def dc_stats(self):
         """this rank's stitches of the last dc_correct: chunks per column, chunks derived from their records, chunks re-evaluated serially"""
-        lib, st = _lib.load(), (C.c_int64 * 8)()
+        st = (C.c_int64 * 8)()
         single = getattr(self, "_dc_single", None)
         if single is not None:
             if single:
-                _lib.check(lib.urhgpu_test_dc_stats(self.ctx.handle, st))
+                self._call("urhgpu_test_dc_stats", st, set_stream=False)
             return {"chunks": int(st[0]), "derived": int(st[1]), "reevaluated": int(st[2])}
-        _lib.check(lib.urhgpu_shard_dc_stats(self.ctx.handle, st))
+        self._call("urhgpu_shard_dc_stats", st, set_stream=False)
         return {"chunks": int(st[0]), "derived": int(st[1] + st[5]), "reevaluated": int(st[2] + st[6])}
 
-    # ---- message records across the shards (sharding.py: message_records; csrc/msg_records.hip, "sharded capture") ----
+    # ---- message records across the shards (sharding/pipeline.py: message_records; csrc/msg_records.hip, "sharded capture") ----
     def _records_outputs(self, res):
         """the C descriptor of a ShardResult's buffers: what the records kernels read of the pass (positions required)"""
         if res.pos_buf is None:
             raise ValueError("message_records needs the positions of the pass (write_bit_sample_pos)")
-        o = _lib.Outputs()
-        o.rows = res.rows_buf.data_ptr(); o.cap_rows = int(res.rows_buf.shape[0])
-        o.bits = res.bits_buf.data_ptr(); o.cap_bits = int(res.bits_buf.shape[0])
-        o.msg_off = res.msg_off_buf.data_ptr(); o.pauses = res.pauses_buf.data_ptr(); o.cap_msg = int(res.pauses_buf.shape[0])
-        o.pos = res.pos_buf.data_ptr(); o.cap_pos = int(res.pos_buf.shape[0])
-        o.pos_off = res.pos_off_buf.data_ptr()
-        o.counts = res.counts.data_ptr()
-        return o
-
-    def _records_shard(self, iq_local):
-        torch = self.torch
-        iq = torch.view_as_real(iq_local) if iq_local.dtype == torch.complex64 else iq_local
-        if iq.dim() != 2 or iq.shape[1] != 2:
-            raise ValueError("IQ must be an (N, 2) tensor or complex64 (N,)")
-        npdt = _torch_dtype(iq)
-        self._own(iq, "message_records")
-        return iq, npdt
+        return self._outputs(None, res.rows_buf, res.bits_buf, res.msg_off_buf, res.pauses_buf, res.pos_buf, res.pos_off_buf, res.counts)
 
     def records_summary(self, iq_local, res, pos_base):
         """int64 (REC_SUMMARY_WORDS,): this rank's summary words, from the pass's device counts and offsets (nothing read back)"""
         from .sharding import REC_SUMMARY_WORDS
-        iq, _ = self._records_shard(iq_local)                  # everything a rank can get wrong on its own, before anything is exchanged
+        iq, _ = self._rows_view(iq_local, "message_records")   # everything a rank can get wrong on its own, before anything is exchanged
         o = self._records_outputs(res)
-        self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
         words = self.torch.empty(REC_SUMMARY_WORDS, dtype=self.torch.int64, device=self.device)
-        _lib.check(_lib.load().urhgpu_shard_records_summary_dev(self.ctx.handle, int(iq.shape[0]), int(pos_base), C.byref(o), C.c_void_p(words.data_ptr())))
+        self._call("urhgpu_shard_records_summary_dev", int(iq.shape[0]), int(pos_base), C.byref(o), C.c_void_p(words.data_ptr()))
         return words
 
     def records_lookup(self, res, index):
         """int64 (len(index),): the position entries asked of this rank (index: local indices, -1 where another rank holds the entry)"""
         torch = self.torch
-        self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
         o = self._records_outputs(res)
         d_index = torch.from_numpy(np.ascontiguousarray(index, dtype=np.int64)).to(self.device)
         values = torch.empty(len(index), dtype=torch.int64, device=self.device)
-        _lib.check(_lib.load().urhgpu_shard_records_lookup_dev(self.ctx.handle, C.byref(o), C.c_void_p(d_index.data_ptr()), len(index),
-                                                               C.c_void_p(values.data_ptr())))
+        self._call("urhgpu_shard_records_lookup_dev", C.byref(o), C.c_void_p(d_index.data_ptr()), len(index), C.c_void_p(values.data_ptr()))
         values._urh_keep = d_index
         return values
 
@@ -555,7 +520,7 @@ class GpuShardEngine(DevicePipeline):
         """uint8 (len(spans), w_max, bytes per sample): of every window [lo, lo + w) asked for, the raw samples this shard holds, in their
         place; zeros elsewhere (plumbing: slices of the shard)"""
         torch = self.torch
-        iq, npdt = self._records_shard(iq_local)
+        iq, npdt = self._rows_view(iq_local, "message_records")
         raw = iq.view(torch.uint8).view(int(iq.shape[0]), 2 * npdt.itemsize)
         part = torch.zeros((len(spans), int(w_max), 2 * npdt.itemsize), dtype=torch.uint8, device=self.device)
         a0, b0 = int(pos_base), int(pos_base) + int(iq.shape[0])
@@ -569,9 +534,8 @@ class GpuShardEngine(DevicePipeline):
         """the records kernel -> this rank's records on the host (protocol.RECORD_DTYPE, one per message closed here)"""
         from .protocol import RECORD_DTYPE
         torch = self.torch
-        iq, npdt = self._records_shard(iq_local)
+        iq, npdt = self._rows_view(iq_local, "message_records")
         o, cp = self._records_outputs(res), p.to_c(npdt)
-        self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)      # the read-back below waits on this stream
         cap = max(int(o.cap_msg), 1)
         d_rec = self._buf("shard_records", (cap * RECORD_DTYPE.itemsize,), torch.uint8)
         block = self._pinned.get(("records", "shard"))
@@ -581,10 +545,11 @@ class GpuShardEngine(DevicePipeline):
         first = np.ascontiguousarray(first, dtype=np.int64)
         if window is not None:
             window = window.contiguous()
-        _lib.check(_lib.load().urhgpu_shard_msg_records_dev(
-            self.ctx.handle, C.c_void_p(iq.data_ptr()), int(iq.shape[0]), int(pos_base), int(n_total), C.byref(cp), C.byref(o), int(divisor),
-            first.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(window.data_ptr()) if window is not None else None,
-            int(window.shape[0]) if window is not None else 0, C.c_void_p(d_rec.data_ptr()), cap, C.c_void_p(block.data_ptr())))
+        self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)      # the read-back below waits on this stream
+        self._call("urhgpu_shard_msg_records_dev", C.c_void_p(iq.data_ptr()), int(iq.shape[0]), int(pos_base), int(n_total), C.byref(cp), C.byref(o),
+                   int(divisor), first.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(window.data_ptr()) if window is not None else None,
+                   int(window.shape[0]) if window is not None else 0, C.c_void_p(d_rec.data_ptr()), cap, C.c_void_p(block.data_ptr()),
+                   set_stream=False)
         n_msg = min(int(res.counts[1:2].cpu()[0]), cap)       # waits for the kernels: the shard and the window are free again, the mirror is complete
         return block.numpy().view(RECORD_DTYPE)[:n_msg].copy()
 
@@ -592,21 +557,21 @@ class GpuShardEngine(DevicePipeline):
         torch = self.torch
         self._keep += (summaries,)
         merge = self._buf("merge", (5,), torch.int64) if self._ask else None
-        _lib.check(_lib.load().urhgpu_shard_rows_dev(self.ctx.handle, C.c_void_p(summaries.data_ptr()),
-                                                     C.c_void_p(merge.data_ptr()) if merge is not None else None))
+        self._call("urhgpu_shard_rows_dev", C.c_void_p(summaries.data_ptr()), C.c_void_p(merge.data_ptr()) if merge is not None else None,
+                   set_stream=False)
         return merge
 
     def bits_prepare(self, merged_all):
         torch = self.torch
         self._keep += (merged_all,)
         flags = self._buf("flags", (3,), torch.int64)
-        _lib.check(_lib.load().urhgpu_shard_bits_prepare_dev(
-            self.ctx.handle, C.c_void_p(merged_all.data_ptr()) if merged_all is not None else None, C.c_void_p(flags.data_ptr())))
+        self._call("urhgpu_shard_bits_prepare_dev", C.c_void_p(merged_all.data_ptr()) if merged_all is not None else None,
+                   C.c_void_p(flags.data_ptr()), set_stream=False)
         return flags
 
     def bits_finish(self, flags_all):
         self._keep += (flags_all,)
-        _lib.check(_lib.load().urhgpu_shard_bits_finish_dev(self.ctx.handle, C.c_void_p(flags_all.data_ptr())))
+        self._call("urhgpu_shard_bits_finish_dev", C.c_void_p(flags_all.data_ptr()), set_stream=False)
         if self._hslot is not None:
             self._res._host = (self, self._hslot, self._queue_host_copy(self._hslot), self._slot_pass[self._hslot])
         res, self._res = self._res, None
