@@ -2,6 +2,7 @@
 # A/B of one tuning key (urhgpu_ctx_set_tuning, include/urhgpu.h) or one build flag on the default bench line (GPU box):
 #   tools/ab.sh key=VALUE [key=VALUE ...]          e.g.  tools/ab.sh stream_policy=0 hot_cus_removed_per_xcd=6
 #   tools/ab.sh --build TAG -DURH_X=1 [...]        builds urh_amd/liburhgpu_TAG.so first (python -m urh_amd.build --tag) and runs it against the default
+#                                                   e.g.  tools/ab.sh --build tile1 -DURH_TILE_CHUNKS=1   (one chunk per tile of the row table: the layout before kTileChunks)
 # prints ms_per_step / kernel ms / single-capture ms of the default run and of the variant, three alternating runs each
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
 ENVV=""; LIB=""

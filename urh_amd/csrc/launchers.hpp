@@ -296,6 +296,7 @@ struct BitsSegment {         // tiles [c0, c1) (the last one: + the tile of the 
     int64_t c0, c1;
     int rows_index;          // rows segment whose end is c1: d_n_rows = &state->rows_at[rows_index]
     SegState *state;
+    int64_t scan_b0;         // tile-scan workgroups of the pass's bits segments before this one (sum of their tile_scan_blocks)
 };
 struct SegPackDst {          // where a bits segment's share of the compact blob goes: pinned HOST memory (device-accessible), see k_pack_seg
     void *host;              // nullptr: nothing is shipped
@@ -323,6 +324,7 @@ struct TileTailMem {
 size_t tile_rdesc_bytes(int64_t n_chunks);
 size_t tile_tail_bytes(int64_t n_chunks);
 int64_t tile_desc_cap(int64_t cap_rows, int64_t n_chunks);
+int64_t tile_scan_blocks(int64_t c0, int64_t c1, int final);   // tile-scan workgroups of the bits segment over the chunks [c0, c1)
 int launch_tile_rows(const ResolveArgs &r, const EmitArgs &e, const TileTailMem &m, const BitsParams *bp, hipStream_t s);
 int launch_tile_bits(const TileTailMem &m, const int64_t *rows, const int64_t *d_n_rows, int64_t cap_rows, const BitsParams &bp,
                      const BitsOut &o, void *scratch, const ScanState &ss, hipStream_t s);

@@ -757,11 +757,13 @@ __device__ __forceinline__ ResElem res_of_chunk(int cnt, uint32_t c_first_state,
 struct TileTail {            // scratch of the tile tail (carved from the context's arena)
     ResElem *ploc;           // [n_chunks] exclusive prefix inside the chunk's resolve workgroup
     ResElem *btot;           // [resolve workgroups] totals
-    VecK<4> *agg;            // [n_chunks + 1] per tile: (bits, long pauses, samples, data rows) of its rows
-    VecK<4> *excl;           // [n_chunks + 1] exclusive prefix of agg (tile scan)
-    int64_t *tile_off;       // [n_chunks + 1] first row of the tile
-    int32_t *tile_cnt;       // [n_chunks + 1] rows in the tile
-    int64_t *d_n_tiles;      // = n_chunks + 1 (device copy for the scan kernel)
+    // tiles: kTileChunks consecutive chunks each (table passes of sharded captures: one), then the tile of the table's last row; the
+    // arrays are sized for one chunk per tile
+    VecK<4> *agg;            // [tiles] per tile: (bits, long pauses, samples, data rows) of its rows
+    VecK<4> *excl;           // [tiles] exclusive prefix of agg (tile scan)
+    int64_t *tile_off;       // [tiles] first row of the tile
+    int32_t *tile_cnt;       // [tiles] rows in the tile
+    int64_t *d_n_tiles;      // (a spare device word)
     int32_t *huge_count;     // [2] persistent, alternating by pass parity; zero between uses
     int parity;
     int want_bits;
@@ -1004,6 +1006,16 @@ constexpr int kEmitWaves = 4;
 #define URH_TAIL_CPW 4
 #endif
 constexpr int kTailCPW = URH_TAIL_CPW;
+// Chunks per TILE of the row table (agg / excl / tile_off / tile_cnt, the unit of k_tile_scan and k_expand_tiles).  A tile is what one
+// tail wavefront owns, kTailCPW consecutive chunks: the row kernel reduces and stores once per wavefront, the tile scan has a quarter of
+// the tiles, the expansion walks one tile's rows in full 64-row iterations.  -DURH_TILE_CHUNKS=1 restores one chunk per tile (A/B
+// builds).  Table passes of sharded captures always run one chunk per tile (TC = 1 instantiations): a summary entry of another shard is
+// a tile without rows whose samples stand in FRONT of this GPU's first row, which a tile shared with local chunks could not express.
+#ifndef URH_TILE_CHUNKS
+#define URH_TILE_CHUNKS URH_TAIL_CPW
+#endif
+constexpr int kTileChunks = URH_TILE_CHUNKS;
+static_assert(kTileChunks >= 1 && kTailCPW % kTileChunks == 0, "a wavefront's chunks are a whole number of tiles");
 #ifndef URH_EXPAND_PREFETCH
 #define URH_EXPAND_PREFETCH 1
 #endif
@@ -1063,6 +1075,8 @@ struct EmitTileArgs {
 };
 
 __host__ __device__ static inline int64_t tail_waves(int64_t n_items) { return (n_items + kTailCPW - 1) / kTailCPW; }
+// tiles that hold the rows of n_chunks chunks, tc chunks per tile (the tile of the table's last row comes behind them)
+__host__ __device__ static inline int64_t chunk_tiles(int64_t n_chunks, int tc) { return (n_chunks + tc - 1) / tc; }
 
 // a row's state and length into the shipped sections (EmitTileArgs::h_state / h_len): int32 lengths, or uint16 with the escape list
 __device__ __forceinline__ void ship_row(const EmitTileArgs &g, int64_t idx, int64_t state, int64_t len) {
@@ -1091,6 +1105,9 @@ __device__ __forceinline__ void ship_row(const EmitTileArgs &g, int64_t idx, int
 // rows span (positions telescope) is its tile's sample count, so that the exclusive tile scan hands this GPU's first tile the
 // total_samples before its first row; bits, long pauses and data rows stay per GPU (their cross-shard part is the flags exchange).
 // Rows are indexed from this GPU's first one (row_base, also left in *ft.d_row_base for the kernels that follow).
+// TC: chunks per tile.  The wavefront's chunks are kTailCPW / TC whole tiles: what a tile's rows contribute is accumulated per lane across
+// its chunks and reduced ONCE, behind the tile's last chunk.
+template <int TC>
 __global__ __launch_bounds__(64 * kEmitWaves) URH_EMIT_OCC void k_emit_rows_tiles(const EmitTileArgs g) {
     URH_TAIL_PRIO();
     const EmitArgs &a = g.e;
@@ -1138,7 +1155,7 @@ __global__ __launch_bounds__(64 * kEmitWaves) URH_EMIT_OCC void k_emit_rows_tile
             if (lane == 0) g.seg->rows_at[g.seg_k] = (r.rows != nullptr && pre.cnt > r.cap_rows) ? r.cap_rows : pre.cnt;
             return;
         }
-        const int64_t c = r.n_chunks;
+        const int64_t c = chunk_tiles(r.n_chunks, TC);       // the last tile
         int64_t row_end = pre.cnt;                         // this GPU's rows are global rows [row_base, row_end) (+ the last row on the last GPU)
         if (table && lc1 < r.n_chunks) row_end = res_before_entry(g.ft, init, lc1, r.n_chunks, lane).cnt;
         if (lane == 0) {
@@ -1174,9 +1191,16 @@ __global__ __launch_bounds__(64 * kEmitWaves) URH_EMIT_OCC void k_emit_rows_tile
         }
         return;
     }
+    // what the open tile's rows contribute to _ppseq_to_bits: bits (64-bit sum), long pauses and data rows (two 32-bit counts in one
+    // word), per lane until the tile closes; the samples need no sum over rows -- row lengths telescope: a chunk's rows span (position
+    // of its last accepted run) - prev_pos -- and the tile's first row and row count (wave-uniform)
+    int64_t acc_bits = 0;
+    uint64_t acc_ld = 0;
+    int64_t my_last_pos = 0;
+    int64_t t_samples = 0, t_off = 0, t_total = 0;
     for (int jc = 0; jc < n_mine; ++jc) {
         const int64_t c = c0 + jc;
-        const bool local = (c >= lc0 && c < lc1);
+        const bool local = (TC > 1) || (c >= lc0 && c < lc1);      // (TC > 1: never a table)
         const uint64_t *slab = a.slab + (c - lc0) * a.slab_stride;          // (local entries only)
         // the next chunk's records are on their way while this one is worked on
         uint64_t rec_next = 0;
@@ -1208,11 +1232,7 @@ __global__ __launch_bounds__(64 * kEmitWaves) URH_EMIT_OCC void k_emit_rows_tile
             rec = rec_next;
             continue;
         }
-        // what the chunk's rows contribute to _ppseq_to_bits: bits (64-bit sum), long pauses and data rows (two 32-bit counts in one
-        // word); the samples need no sum at all -- row lengths telescope: sum = (position of the chunk's last accepted run) - prev_pos
-        int64_t acc_bits = 0;
-        uint64_t acc_ld = 0;
-        int64_t my_last_pos = 0;
+        if (jc % TC == 0) { acc_bits = 0; acc_ld = 0; t_samples = 0; t_total = 0; t_off = out_off - row_base; }
         const bool in_regs = cnt <= 64;                      // every record this chunk has is in `rec`
         // record of row j's run (j + skip) and of the run before it, from the neighbours' registers
         const uint64_t rec_j = skip ? (uint64_t)__shfl_down((long long)rec, 1) : rec;
@@ -1242,19 +1262,23 @@ __global__ __launch_bounds__(64 * kEmitWaves) URH_EMIT_OCC void k_emit_rows_tile
                 acc_ld += (uint64_t)v.v[1] | ((uint64_t)v.v[3] << 32);
                 if (v.v[0] > kHugeBits) {
                     const int slot = atomicAdd(g.ft.huge_count + g.ft.parity, 1);
-                    if (slot < g.huge_cap) { g.huge[slot].tile = c; g.huge[slot].row = gi - row_base; }
+                    if (slot < g.huge_cap) { g.huge[slot].tile = c / TC; g.huge[slot].row = gi - row_base; }
                 }
             }
         }
-        VecK<4> acc; acc.zero();
-        if (g.ft.want_bits && total > 0) {
+        // the lane that wrote the chunk's last row knows where it ends (prev_pos = -1 before the table's first row: its length is position + 1)
+        if (g.ft.want_bits && total > 0) t_samples += lane_bcast(my_last_pos, (int)((total - 1) & 63)) - prev_pos;
+        t_total += total;
+        if (jc % TC == TC - 1 || jc == n_mine - 1) {         // the tile closes
+            VecK<4> acc; acc.zero();
+            if (g.ft.want_bits && t_total > 0) {
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { acc_bits += __shfl_xor(acc_bits, o); acc_ld += (uint64_t)__shfl_xor((long long)acc_ld, o); }
-            const int64_t last_pos = __shfl(my_last_pos, (int)((total - 1) & 63));       // the lane that wrote the chunk's last row
-            acc.v[0] = acc_bits; acc.v[1] = (int64_t)(acc_ld & 0xFFFFFFFFull); acc.v[3] = (int64_t)(acc_ld >> 32);
-            acc.v[2] = last_pos - prev_pos;                  // (prev_pos = -1 before the table's first row: its length is position + 1)
+                for (int o = 32; o > 0; o >>= 1) { acc_bits += __shfl_xor(acc_bits, o); acc_ld += (uint64_t)__shfl_xor((long long)acc_ld, o); }
+                acc.v[0] = acc_bits; acc.v[1] = (int64_t)(acc_ld & 0xFFFFFFFFull); acc.v[3] = (int64_t)(acc_ld >> 32);
+                acc.v[2] = t_samples;
+            }
+            if (lane == 0) { g.ft.agg[c / TC] = acc; g.ft.tile_off[c / TC] = t_off; g.ft.tile_cnt[c / TC] = (int32_t)t_total; }
         }
-        if (lane == 0) { g.ft.agg[c] = acc; g.ft.tile_off[c] = out_off - row_base; g.ft.tile_cnt[c] = (int32_t)total; }
         rec = rec_next;
     }
 }
@@ -1276,9 +1300,11 @@ struct TileScanArgs {
     GranDesc *desc;
     unsigned long long epoch;
     // a segment of a streamed pass: workgroups [b0, b0 + gridDim.x) -- the look-back reaches into the descriptors the earlier segments'
-    // launches published under the same epoch --, n_tiles = the segment's end, *d_n_rows = the rows that are final so far (the
-    // "trailing group" the walk records is then the group that is still open: what the segment's group scan starts the next one from)
-    int64_t b0;
+    // launches published under the same epoch --, over the tiles [t_base, n_tiles): a segment starts on kSegAlign chunks, which is fewer
+    // tiles than a workgroup scans, so the workgroups of a pass are counted (tile_scan_blocks), not derived from the tile index;
+    // *d_n_rows = the rows that are final so far (the "trailing group" the walk records is then the group that is still open: what the
+    // segment's group scan starts the next one from)
+    int64_t b0, t_base;
     SegState *seg;
     int seg_parity;          // segment index & 1
 };
@@ -1290,7 +1316,7 @@ __global__ __launch_bounds__(kScanBlock) URH_TAIL_OCC void k_tile_scan(const Til
     __shared__ int64_t s_off[kScanBlock], s_end[kScanBlock];
     __shared__ int s_count;
     const int64_t b = a.b0 + blockIdx.x, nb = a.b0 + gridDim.x;
-    const int64_t t = b * kScanBlock + threadIdx.x;
+    const int64_t t = a.t_base + (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // one round trip
     const int64_t n = *a.d_n_rows;
@@ -1377,6 +1403,7 @@ __global__ __launch_bounds__(kScanBlock) URH_TAIL_OCC void k_tile_scan(const Til
 struct ExpandTileArgs {
     const int64_t *rows;
     const int64_t *d_n_rows;
+    const VecK<4> *agg;
     const VecK<4> *excl;
     const int64_t *tile_off;
     const int32_t *tile_cnt;
@@ -1390,20 +1417,25 @@ struct ExpandTileArgs {
     int32_t huge_cap;
     int parity;
     int64_t n_tiles;
-    int64_t t_base;          // first tile of this launch (0; a segment of a streamed pass: its first chunk)
+    int64_t t_base;          // first tile of this launch (0; a segment of a streamed pass: the tile of its first chunk)
     uint32_t *h_pos;         // see GroupStore::h_pos (nullptr: positions are not shipped by this kernel)
 };
 constexpr unsigned kHugeBlocksX = 16, kHugeBlocksY = 16;
 
-// one wavefront per kTailCPW consecutive tiles (see kTailCPW); workgroups beyond the tiles expand the listed huge rows, kHugeBlocksX
-// workgroups per row
-__host__ __device__ static inline int64_t expand_tile_blocks(int64_t n_tiles) { return (tail_waves(n_tiles) + kEmitWaves - 1) / kEmitWaves; }
+// one wavefront per kTailCPW chunks' tiles -- ONE tile of kTileChunks = kTailCPW chunks, or kTailCPW / TC consecutive tiles of TC chunks
+// (see kTailCPW, kTileChunks); workgroups beyond the tiles expand the listed huge rows, kHugeBlocksX workgroups per row
+__host__ __device__ static inline int64_t expand_tile_blocks(int64_t n_tiles, int tc) {
+    const int64_t tpw = kTailCPW / tc;
+    return ((n_tiles + tpw - 1) / tpw + kEmitWaves - 1) / kEmitWaves;
+}
 
+template <int TC>
 __global__ __launch_bounds__(64 * kEmitWaves) URH_EXPAND_OCC void k_expand_tiles(const ExpandTileArgs a) {
+    constexpr int kTPW = kTailCPW / TC;                    // tiles per wavefront
     URH_TAIL_PRIO();
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int bps = (int)a.bp.bps;
-    const int64_t tile_blocks = expand_tile_blocks(a.n_tiles - a.t_base);
+    const int64_t tile_blocks = expand_tile_blocks(a.n_tiles - a.t_base, TC);
     if ((int64_t)blockIdx.x >= tile_blocks) {
         // ---- huge rows ----
         const int64_t n = *a.d_n_rows;
@@ -1459,9 +1491,9 @@ __global__ __launch_bounds__(64 * kEmitWaves) URH_EXPAND_OCC void k_expand_tiles
         }
         return;
     }
-    const int64_t t0 = a.t_base + ((int64_t)blockIdx.x * kEmitWaves + wave) * kTailCPW;
+    const int64_t t0 = a.t_base + ((int64_t)blockIdx.x * kEmitWaves + wave) * kTPW;
     if (t0 >= a.n_tiles) return;
-    const int n_mine = (int)((a.n_tiles - t0 < kTailCPW) ? a.n_tiles - t0 : kTailCPW);
+    const int n_mine = (int)((a.n_tiles - t0 < kTPW) ? a.n_tiles - t0 : kTPW);
     // ---- round trip 1: everything that does not depend on loaded data; lane j holds the metadata of tile t0 + j ----
     const int64_t n = *a.d_n_rows;
     const int64_t n_groups = *a.d_n_groups;
@@ -1469,7 +1501,12 @@ __global__ __launch_bounds__(64 * kEmitWaves) URH_EXPAND_OCC void k_expand_tiles
     const int hc = a.huge_count[a.parity];
     int64_t off_l = 0; int32_t tcnt_l = 0;
     VecK<4> run_l; run_l.zero();
-    if (lane < n_mine) { off_l = a.tile_off[t0 + lane]; tcnt_l = a.tile_cnt[t0 + lane]; run_l = a.excl[t0 + lane]; }
+    int narrow_l = 0;                                      // the tile's bits and samples are below 2^31: its in-tile scans run in 32 bits
+    if (lane < n_mine) {
+        off_l = a.tile_off[t0 + lane]; tcnt_l = a.tile_cnt[t0 + lane]; run_l = a.excl[t0 + lane];
+        const int64_t tb = a.agg[t0 + lane].v[0], tsm = a.agg[t0 + lane].v[2];
+        narrow_l = (tb >= 0 && tb < (int64_t(1) << 31) && tsm >= 0 && tsm < (int64_t(1) << 31)) ? 1 : 0;
+    }
     const int64_t own_limit = (hc > a.huge_cap) ? INT64_MAX : kHugeBits;   // longer rows are on the list
     // ---- round trip 2: the group every tile starts in (nearly every row of a tile belongs to it), and the first tile's rows ----
     GroupOut go_l; go_l.bits_start = 0; go_l.out_bits = 0; go_l.out_pos = 0; go_l.is_msg = 0; go_l.pad = 0;
@@ -1482,6 +1519,7 @@ __global__ __launch_bounds__(64 * kEmitWaves) URH_EXPAND_OCC void k_expand_tiles
     for (int jt = 0; jt < n_mine; ++jt) {
         const int64_t off = lane_bcast(off_l, jt);
         const int32_t tcnt = lane_bcast((int)tcnt_l, jt);
+        const bool narrow = lane_bcast(narrow_l, jt) != 0;
         VecK<4> run;
         run.v[0] = lane_bcast(run_l.v[0], jt); run.v[1] = lane_bcast(run_l.v[1], jt); run.v[2] = lane_bcast(run_l.v[2], jt); run.v[3] = 0;
         GroupOut go0;
@@ -1520,17 +1558,31 @@ __global__ __launch_bounds__(64 * kEmitWaves) URH_EXPAND_OCC void k_expand_tiles
                 v = row_value(type, row.y, i == 0 && row0g, a.bp);
             }
 #endif
-            // inclusive wave scans of what the expansion needs: bits and samples (64-bit), long pauses (32-bit: a tile has few rows)
+            // inclusive wave scans of what the expansion needs: bits, samples, long pauses (32-bit: a tile has few rows).  Bits and samples
+            // in 32 bits where the whole tile's sums fit (wave-uniform, from the tile's aggregate: a stream capture is below 2^31 samples,
+            // a tile's bits too unless it holds a huge row; rows of a table never have a negative bit count, and a negative length -- the
+            // table's last row -- makes the tile's samples negative or is the tile's only row), in 64 bits otherwise
             int64_t in_bits = v.v[0], in_ts = v.v[2];
             int in_l = (int)v.v[1];
 #if URH_DPP_SCAN
             in_bits = wave_incl_sum_dpp(in_bits); in_ts = wave_incl_sum_dpp(in_ts); in_l = wave_incl_sum_dpp(in_l);
 #else
+            if (narrow) {
+                uint32_t b32 = (uint32_t)v.v[0], t32 = (uint32_t)v.v[2];
 #pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int64_t ub = __shfl_up(in_bits, o), ut = __shfl_up(in_ts, o);
-                const int ul = __shfl_up(in_l, o);
-                if (lane >= o) { in_bits += ub; in_ts += ut; in_l += ul; }
+                for (int o = 1; o < 64; o <<= 1) {
+                    const uint32_t ub = (uint32_t)__shfl_up((int)b32, o), ut = (uint32_t)__shfl_up((int)t32, o);
+                    const int ul = __shfl_up(in_l, o);
+                    if (lane >= o) { b32 += ub; t32 += ut; in_l += ul; }
+                }
+                in_bits = (int64_t)b32; in_ts = (int64_t)t32;
+            } else {
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int64_t ub = __shfl_up(in_bits, o), ut = __shfl_up(in_ts, o);
+                    const int ul = __shfl_up(in_l, o);
+                    if (lane >= o) { in_bits += ub; in_ts += ut; in_l += ul; }
+                }
             }
 #endif
             int64_t kb = 0, ob = 0, op = 0, ts = 0;
@@ -1818,11 +1870,23 @@ TileCarve carve_tile(const TileTailMem &m) {
 }
 }  // namespace
 
-// the tile scan runs one workgroup per 256 tiles: descriptor memory sized (bits_desc_bytes) for this many "rows" holds them
+// the tile scan runs one workgroup per 256 tiles: descriptor memory sized (bits_desc_bytes) for this many "rows" holds them (sized for
+// one chunk per tile, the most there can be)
+// chunks per tile of a pass: table passes of sharded captures (they have a row base) keep one chunk per tile
+static inline int tile_chunks_of(const TileTailMem &m) { return m.d_row_base ? 1 : kTileChunks; }
+
 int64_t tile_desc_cap(int64_t cap_rows, int64_t n_chunks) { return std::max<int64_t>(cap_rows, 8 * (n_chunks + 2) + kScanTile); }
 
-size_t tile_rdesc_bytes(int64_t n_chunks) {        // resolve scan + tile scan descriptors
-    return (size_t)(resolve_blocks(n_chunks) + 2 + (n_chunks + 1 + kScanBlock - 1) / kScanBlock + 2) * sizeof(GranDesc);
+// workgroups of the tile scan over the tiles of the chunks [c0, c1) (final: + the tile of the table's last row), tc chunks per tile
+static inline int64_t tile_scan_blocks_tc(int64_t c0, int64_t c1, int final, int tc) {
+    const int64_t t1 = final ? chunk_tiles(c1, tc) + 1 : c1 / tc;
+    return (t1 - c0 / tc + kScanBlock - 1) / kScanBlock;
+}
+int64_t tile_scan_blocks(int64_t c0, int64_t c1, int final) { return tile_scan_blocks_tc(c0, c1, final, kTileChunks); }
+
+size_t tile_rdesc_bytes(int64_t n_chunks) {        // resolve scan + tile scan descriptors (one chunk per tile at most; every segment of a
+                                                   // streamed pass starts a tile-scan workgroup of its own)
+    return (size_t)(resolve_blocks(n_chunks) + 2 + (n_chunks + 1 + kScanBlock - 1) / kScanBlock + kMaxSegments + 2) * sizeof(GranDesc);
 }
 
 size_t tile_tail_bytes(int64_t n_chunks) {
@@ -1848,7 +1912,11 @@ int launch_tile_rows(const ResolveArgs &r, const EmitArgs &e, const TileTailMem 
     SegGate no_gate;
     memset(&no_gate, 0, sizeof(no_gate));
     if (!(g_tail_skip & 1)) hipLaunchKernelGGL(k_resolve_one, dim3(gb), dim3(kResolveBlock), 0, s, r, g.ft, (int64_t)0, no_gate);
-    if (!(g_tail_skip & 2)) hipLaunchKernelGGL(k_emit_rows_tiles, dim3((unsigned)((tail_waves(r.n_chunks) + 1 + kEmitWaves - 1) / kEmitWaves)), dim3(64 * kEmitWaves), 0, s, g);
+    const dim3 grid((unsigned)((tail_waves(r.n_chunks) + 1 + kEmitWaves - 1) / kEmitWaves));
+    if (!(g_tail_skip & 2)) {
+        if (tile_chunks_of(m) == 1) hipLaunchKernelGGL(k_emit_rows_tiles<1>, grid, dim3(64 * kEmitWaves), 0, s, g);
+        else hipLaunchKernelGGL(k_emit_rows_tiles<kTileChunks>, grid, dim3(64 * kEmitWaves), 0, s, g);
+    }
     return URHGPU_OK;
 }
 
@@ -1867,7 +1935,7 @@ __global__ void k_tile_flags(const int64_t *d_n_rows, const GroupInfo *groups, c
 int launch_tile_bits_prepare(const TileTailMem &m, const int64_t *rows, const int64_t *d_n_rows, int64_t cap_rows, const BitsParams &bp,
                              void *scratch, int64_t *d_flags, const ScanState &ss, hipStream_t s) {
     if (cap_rows <= 0) cap_rows = 1;
-    const int64_t nt = m.n_chunks + 1;
+    const int64_t nt = chunk_tiles(m.n_chunks, tile_chunks_of(m)) + 1;
     const int64_t cap_desc = tile_desc_cap(cap_rows, m.n_chunks);
     if (ss.desc_bytes < bits_desc_bytes(cap_desc)) return URHGPU_ERR_ARG;
     const TileCarve tc = carve_tile(m);
@@ -1875,7 +1943,7 @@ int launch_tile_bits_prepare(const TileTailMem &m, const int64_t *rows, const in
     const int64_t cap_groups = cap_rows + 1;
     GranDesc *tdesc = (GranDesc *)m.rdesc + resolve_blocks(m.n_chunks) + 2;
     TileScanArgs ta{rows, d_n_rows, tc.ft.agg, tc.ft.tile_off, tc.ft.tile_cnt, tc.ft.excl, b.groups, cap_groups, b.d_n_groups, nt, bp, tdesc,
-                    m.epoch, 0, nullptr, 0};
+                    m.epoch, 0, 0, nullptr, 0};
     const unsigned nb_ts = (unsigned)((nt + kScanBlock - 1) / kScanBlock);
     if (!(g_tail_skip & 4)) hipLaunchKernelGGL(k_tile_scan, dim3(nb_ts), dim3(kScanBlock), 0, s, ta);
     if (d_flags) hipLaunchKernelGGL(k_tile_flags, dim3(1), dim3(1), 0, s, d_n_rows, b.groups, b.d_n_groups, d_flags);
@@ -1885,7 +1953,8 @@ int launch_tile_bits_prepare(const TileTailMem &m, const int64_t *rows, const in
 int launch_tile_bits_finish(const TileTailMem &m, const int64_t *rows, const int64_t *d_n_rows, int64_t cap_rows, const BitsParams &bp,
                             const BitsOut &o, void *scratch, const ScanState &ss, hipStream_t s) {
     if (cap_rows <= 0) cap_rows = 1;
-    const int64_t nt = m.n_chunks + 1;
+    const int tch = tile_chunks_of(m);
+    const int64_t nt = chunk_tiles(m.n_chunks, tch) + 1;
     const int64_t cap_desc = tile_desc_cap(cap_rows, m.n_chunks);
     if (ss.desc_bytes < bits_desc_bytes(cap_desc)) return URHGPU_ERR_ARG;
     const TileCarve tc = carve_tile(m);
@@ -1897,10 +1966,13 @@ int launch_tile_bits_finish(const TileTailMem &m, const int64_t *rows, const int
     if (!(g_tail_skip & 8))
         hipLaunchKernelGGL((k_scan_lookback<3, GroupLoad, GroupStore, BitsCountsFinal, kGroupItems>), dim3(scan_grid(b.nbg)), dim3(kScanBlock), 0, s,
                            b.d_n_groups, gl, desc3, b.nbg, gs, fin, ++*ss.epoch, ss.tickets + 2, 0);
-    ExpandTileArgs ea{rows, d_n_rows, tc.ft.excl, tc.ft.tile_off, tc.ft.tile_cnt, b.gout, b.d_n_groups, o.bits, o.cap_bits, o.pos, o.cap_pos,
+    ExpandTileArgs ea{rows, d_n_rows, tc.ft.agg, tc.ft.excl, tc.ft.tile_off, tc.ft.tile_cnt, b.gout, b.d_n_groups, o.bits, o.cap_bits, o.pos, o.cap_pos,
                       bp, tc.huge, m.huge_count, kTileHugeCap, m.parity, nt, 0, nullptr};
-    const unsigned tile_blocks = (unsigned)expand_tile_blocks(nt);
-    if (!(g_tail_skip & 16)) hipLaunchKernelGGL(k_expand_tiles, dim3(tile_blocks + kHugeBlocksX * kHugeBlocksY), dim3(64 * kEmitWaves), 0, s, ea);
+    const dim3 grid((unsigned)expand_tile_blocks(nt, tch) + kHugeBlocksX * kHugeBlocksY);
+    if (!(g_tail_skip & 16)) {
+        if (tch == 1) hipLaunchKernelGGL(k_expand_tiles<1>, grid, dim3(64 * kEmitWaves), 0, s, ea);
+        else hipLaunchKernelGGL(k_expand_tiles<kTileChunks>, grid, dim3(64 * kEmitWaves), 0, s, ea);
+    }
     return URHGPU_OK;
 }
 
@@ -2119,7 +2191,7 @@ int launch_rows_segment(const ResolveArgs &r, const EmitArgs &e, const TileTailM
         return URHGPU_ERR_ARG;
     if (sg.c0 < 0 || sg.c0 % kSegAlign || sg.c1 <= sg.c0 || sg.c1 > r.n_chunks || (sg.final ? sg.c1 != r.n_chunks : (sg.c1 % kSegAlign != 0 || sg.c1 >= r.n_chunks)))
         return URHGPU_ERR_ARG;
-    static_assert(kSegAlign % kResolveBlock == 0 && kSegAlign % kScanBlock == 0 && kSegAlign % (kTailCPW * kEmitWaves) == 0, "segment alignment");
+    static_assert(kSegAlign % kResolveBlock == 0 && kSegAlign % kScanBlock == 0 && kSegAlign % (kTailCPW * kEmitWaves) == 0, "segment alignment");    // (whole wavefronts, so whole tiles too)
     if (sg.final && (r.d_n_rows != &state->rows_at[sg.index] || r.d_n_rows_needed != &state->rows_needed)) return URHGPU_ERR_ARG;
     if ((sg.h_state == nullptr) != (sg.h_len == nullptr) || sg.gate.seg != state) return URHGPU_ERR_ARG;
     const TileCarve tc = carve_tile(m);
@@ -2140,7 +2212,7 @@ int launch_rows_segment(const ResolveArgs &r, const EmitArgs &e, const TileTailM
     gate.fused = (sg.fuse_gate && gate.progress && !gate.init && resolve_blocks(sg.c1 - sg.c0) == 1) ? 1 : 0;
     if (!gate.fused && gate.progress) hipLaunchKernelGGL(k_seg_gate, dim3(1), dim3(64), 0, s, gate);
     if (!(g_tail_skip & 1)) hipLaunchKernelGGL(k_resolve_one, dim3((unsigned)resolve_blocks(sg.c1 - sg.c0)), dim3(kResolveBlock), 0, s, r, ft_resolve, sg.c0 / kResolveBlock, gate);
-    if (!(g_tail_skip & 2)) hipLaunchKernelGGL(k_emit_rows_tiles, dim3((unsigned)((g.w_end - g.w0 + 1 + kEmitWaves - 1) / kEmitWaves)), dim3(64 * kEmitWaves), 0, s, g);
+    if (!(g_tail_skip & 2)) hipLaunchKernelGGL(k_emit_rows_tiles<kTileChunks>, dim3((unsigned)((g.w_end - g.w0 + 1 + kEmitWaves - 1) / kEmitWaves)), dim3(64 * kEmitWaves), 0, s, g);
     return URHGPU_OK;
 }
 
@@ -2158,13 +2230,14 @@ int launch_bits_segment(const TileTailMem &m, const BitsParams &bp, const BitsOu
     SegState *st = sg.state;
     const int64_t *d_n_rows = &st->rows_at[sg.rows_index];
     const int parity = sg.index & 1;
-    // tile scan over the segment's tiles (the last segment: + the tile of the table's last row)
-    const int64_t t1 = sg.final ? m.n_chunks + 1 : sg.c1;
+    // tile scan over the segment's tiles (the last segment: + the tile of the table's last row); segment bounds are whole tiles
+    if (sg.scan_b0 < 0 || sg.scan_b0 + tile_scan_blocks(sg.c0, sg.c1, sg.final) > (m.n_chunks + 1 + kScanBlock - 1) / kScanBlock + kMaxSegments) return URHGPU_ERR_ARG;
+    const int64_t t0 = sg.c0 / kTileChunks, t1 = sg.final ? chunk_tiles(m.n_chunks, kTileChunks) + 1 : sg.c1 / kTileChunks;
     const int64_t cap_groups = cap_rows + 1;
     GranDesc *tdesc = (GranDesc *)m.rdesc + resolve_blocks(m.n_chunks) + 2;
     TileScanArgs ta{rows, d_n_rows, tc.ft.agg, tc.ft.tile_off, tc.ft.tile_cnt, tc.ft.excl, b.groups, cap_groups, &st->n_groups, t1, bp, tdesc,
-                    m.epoch, sg.c0 / kScanBlock, st, parity};
-    if (!(g_tail_skip & 4)) hipLaunchKernelGGL(k_tile_scan, dim3((unsigned)((t1 - sg.c0 + kScanBlock - 1) / kScanBlock)), dim3(kScanBlock), 0, s, ta);
+                    m.epoch, sg.scan_b0, t0, st, parity};
+    if (!(g_tail_skip & 4)) hipLaunchKernelGGL(k_tile_scan, dim3((unsigned)tile_scan_blocks(sg.c0, sg.c1, sg.final)), dim3(kScanBlock), 0, s, ta);
     // groups [the one that was open before this segment, the one that is open now]
     ScanDesc<3> *desc3 = (ScanDesc<3> *)((char *)ss.desc + (((size_t)(scan_blocks(cap_desc) + 1) * sizeof(ScanDesc<4>) + 255) & ~size_t(255)));
     GroupLoad gl{b.groups, &st->n_groups, nullptr, sg.final ? 1 : 0, bp.write_pos, sg.final ? 0 : 1};
@@ -2190,11 +2263,11 @@ int launch_bits_segment(const TileTailMem &m, const BitsParams &bp, const BitsOu
     if (!(g_tail_skip & 8))
         hipLaunchKernelGGL((k_scan_lookback<3, SegGroupLoad, SegGroupStore, SegFinal, kGroupItems>), dim3((unsigned)std::min<int64_t>(scan_grid(b.nbg), 32)),
                            dim3(kScanBlock), 0, s, &st->n_groups_local, sl, desc3, b.nbg, sst, fin, ++*ss.epoch, ss.tickets + 2, 0);
-    ExpandTileArgs ea{rows, d_n_rows, tc.ft.excl, tc.ft.tile_off, tc.ft.tile_cnt, b.gout, &st->n_groups, o.bits, o.cap_bits, o.pos, o.cap_pos,
-                      bp, tc.huge, m.huge_count, kTileHugeCap, m.parity, t1, sg.c0, h_pos};
-    const unsigned tile_blocks = (unsigned)expand_tile_blocks(t1 - sg.c0);
+    ExpandTileArgs ea{rows, d_n_rows, tc.ft.agg, tc.ft.excl, tc.ft.tile_off, tc.ft.tile_cnt, b.gout, &st->n_groups, o.bits, o.cap_bits, o.pos, o.cap_pos,
+                      bp, tc.huge, m.huge_count, kTileHugeCap, m.parity, t1, t0, h_pos};
+    const unsigned tile_blocks = (unsigned)expand_tile_blocks(t1 - t0, kTileChunks);
     if (g_tail_skip & 2048) ea.cap_bits = 0;                 // measurement: the expansion without its byte stores
-    if (!(g_tail_skip & 16)) hipLaunchKernelGGL(k_expand_tiles, dim3(tile_blocks + kHugeBlocksX * kHugeBlocksY), dim3(64 * kEmitWaves), 0, s, ea);
+    if (!(g_tail_skip & 16)) hipLaunchKernelGGL(k_expand_tiles<kTileChunks>, dim3(tile_blocks + kHugeBlocksX * kHugeBlocksY), dim3(64 * kEmitWaves), 0, s, ea);
     if (dst && dst->host) {
         if (((uintptr_t)o.bits & 7) || ((uintptr_t)dst->host & 15)) return URHGPU_ERR_ARG;
         SegPack pk{o.bits, o.msg_off, o.pauses, o.pos_off, o.pos, o.counts, cap_rows, o.cap_bits, o.cap_msg, o.cap_pos, has_pos, (char *)dst->host,

@@ -243,7 +243,7 @@ int StreamPass::tail(hipEvent_t ev_ready, hipEvent_t ev_rows, int len16) {
     for (int j = 0; j < Sb - 1; ++j) bits_end_at[j] = (int)((int64_t)(S - 1) * (j + 1) / (Sb - 1)) - 1;
     bits_end_at[Sb - 1] = S - 1;
     int jb = 0;
-    int64_t bits_from = 0;
+    int64_t bits_from = 0, scan_b0 = 0;
     // the LAST bits segment goes onto the rows stream, right behind the last rows: no event hop between two
     // streams on the chain that is exposed behind the hot kernel's end; the rows stream then waits for the bits segments before it
     for (int k = 0; k < S; ++k) {
@@ -256,7 +256,8 @@ int StreamPass::tail(hipEvent_t ev_ready, hipEvent_t ev_rows, int len16) {
         while (jb < Sb && bits_end_at[jb] < k) ++jb;           // (a bits segment that would end before the first rows segment: none)
         if (jb < Sb && bits_end_at[jb] == k) {
             const bool last = (jb == Sb - 1);
-            BitsSegment bs{jb, last ? 1 : 0, bits_from, bound[k + 1], k, st};
+            BitsSegment bs{jb, last ? 1 : 0, bits_from, bound[k + 1], k, st, scan_b0};
+            scan_b0 += tile_scan_blocks(bits_from, bound[k + 1], last ? 1 : 0);
             if (last) {
                 if (jb > 0) {                                  // behind the bits segments before it (their carries, their packed bytes)
                     URH_HIP(hipEventRecord(ctx->ev_bits[slot], tb));
