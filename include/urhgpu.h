@@ -1094,6 +1094,48 @@ int urhgpu_shard_msg_records_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_lo
                                  const urhgpu_outputs *out, int64_t message_length_divisor, const int64_t *first, const void *d_window,
                                  int64_t window_len, void *d_rec, int64_t cap_msg, void *h_rec);
 
+/* ---- a batch of captures in one pass: a wavefront per capture -------------------------------------------------------------------
+ * Every entry point above takes ONE capture per pass, and below a few hundred thousand samples a pass is all fixed cost (a dozen
+ * launches whose kernels run for microseconds).  A recording session is hundreds or thousands of short captures: here K of them lie
+ * back to back in one device buffer and are demodulated and digitised by THREE launches whatever K and the lengths are -- one
+ * wavefront walks one capture (afp_demod, grab_pulse_lens and _ppseq_to_bits followed almost literally: signal_functions.pyx:333-378,
+ * :392-495, ProtocolAnalyzer.py:323-414), one workgroup takes the prefix of the result sizes, one wavefront per capture packs its
+ * results.  Every capture's results are those of urhgpu_iq_to_bits_dev for that capture alone, bit for bit.  The counterpart of
+ * urhgpu_modulate_dev's batch of messages.  Long captures still belong to passes and streams: a wavefront walks its capture serially.
+ *   Input    d_iq: (total, 2) interleaved samples of p->dtype (any of the five), 16-byte aligned; d_start: device int64[k + 1], the first
+ *            sample of each capture (a capture may start at any sample; lengths 0 .. 2^31 - 1); one urhgpu_params for all.  ASK and FSK;
+ *            PSK and URHGPU_MOD_OTHER: URHGPU_ERR_UNSUPPORTED.  Any tolerance (uint16), bits_per_symbol 1 .. 7.
+ *   Plan     urhgpu_batch_plan (host arithmetic, works without a GPU): from the k lengths, the parameters and a row-capacity policy --
+ *            0: urhgpu_stream_capacities' formula with a floor of 64 rows instead of 4096, min(n / (tolerance + 1) + 2, max(64, 4 * (n /
+ *            samples_per_symbol) + 64)); 1: the hard bound n / (tolerance + 1) + 2, which cannot truncate; 2: cap_rows_fixed for every
+ *            capture -- plan[0 .. k) = the byte offset of each capture's region of the work buffer (disjoint, in order, 16-byte
+ *            aligned), plan[k .. 2k) = its row capacity, plan[2k .. 3k) = the launch order (a permutation, longest capture first, so
+ *            that the long ones do not trail), *work_bytes, and *blob_capacity = what the blobs of all captures can need at most.  The
+ *            caller uploads the plan as it is (device int64[3 k]) and allocates the two buffers.  A region's bit and message
+ *            capacities follow from its row capacity and cannot overflow while the rows fit.
+ *   Pass     urhgpu_iq_to_bits_batch_dev: asynchronous on the context's stream, the caller owns all memory, nothing is copied.
+ *            d_qad: NULL or float32[total], the demodulated signal of every capture at its samples' indices.  d_counts: int64[8 k],
+ *            per capture {rows stored, messages, bits, rows_needed, truncated, 0, 0, 0}.  d_dir: int64[k + 1], the byte offset of each
+ *            capture's blob in d_blob; d_dir[k] = the used part.  At d_dir[i] lies capture i's STANDARD compact result blob (above):
+ *            header flags 0, int8 row_state, int32 row_len, bits packed most significant first, no position section (positions are
+ *            a function of the rows: the host derives them).  A capture that outgrows its region stops storing and keeps counting:
+ *            truncated bit 0 is set, rows_needed is exact, the blob holds what fitted; a wavefront never writes outside its region
+ *            (truncated bit 3: the capture's start / end or its plan entry do not lie inside the buffers given -- nothing of it is
+ *            read or stored).  k = 0 and captures of length 0 are accepted.
+ *   Fetch    urhgpu_batch_fetch: the directory (one read of 8 (k + 1) bytes into h_dir), then ONE copy of d_dir[k] bytes into h_blob
+ *            (pinned memory: at PCIe speed); synchronous.  *total_bytes = d_dir[k] (also on URHGPU_ERR_CAPACITY: cap_host too small).
+ *   urhgpu_batch_step: samples a wavefront takes per step.  urhgpu_batch_launches: out2 = {kernel launches, copies} the two calls
+ *   above have issued on this context -- 3 per pass and 2 per fetch, whatever k and the lengths are. */
+int urhgpu_batch_step(void);
+int urhgpu_batch_plan(const int64_t *lengths, int64_t k, const urhgpu_params *p, int policy, int64_t cap_rows_fixed, int64_t *plan,
+                      int64_t *work_bytes, int64_t *blob_capacity);
+int urhgpu_iq_to_bits_batch_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k,
+                                const urhgpu_params *p, float *d_qad, void *d_work, int64_t work_bytes, int64_t *d_counts, int64_t *d_dir,
+                                void *d_blob, int64_t cap_blob);
+int urhgpu_batch_fetch(urhgpu_ctx *ctx, const int64_t *d_dir, int64_t k, const void *d_blob, int64_t *h_dir, void *h_blob, int64_t cap_host,
+                       int64_t *total_bytes);
+int urhgpu_batch_launches(urhgpu_ctx *ctx, int64_t *out2);
+
 #ifdef __cplusplus
 }
 #endif

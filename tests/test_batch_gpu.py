@@ -1,0 +1,263 @@
+"""DevicePipeline.iq_to_bits_batch (urh_amd/batch.py; include/urhgpu.h "a batch of captures") against the oracle: every capture of a batch
+comes back with the pulse table, bits, offsets, pauses, positions, position offsets and demodulated signal that oracle.afp_demod ->
+grab_pulse_lens -> ppseq_to_bits_flat give for that capture alone, whatever lies beside it in the buffer.  The exactness tests run with
+cap_rows="bound" (the default policy does overflow for ordinary inputs, which has a test of its own) and assert that NO capture was
+truncated."""
+import os
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN_CASES, load_golden, synth_fsk
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def pipe():
+    from urh_amd.pipeline import DevicePipeline
+    return DevicePipeline(0)
+
+
+def params(mod="FSK", bps=1, noise=0.0, tol=5, sps=100, pt=8):
+    from urh_amd.pipeline import DemodParams
+    center = 0.0 if mod == "FSK" else 0.4
+    spacing = 1.0 if bps == 1 else (0.3 if mod == "FSK" else 0.2)
+    return DemodParams(mod, bps, noise, center, spacing, tol, sps, 0.1, pt, False)
+
+
+def expected(oracle, iq, p):
+    qad = oracle.afp_demod(iq, p.noise_threshold, p.modulation_type, 2 ** p.bits_per_symbol)
+    pp = oracle.grab_pulse_lens(qad, p.center, p.tolerance, p.modulation_type, p.samples_per_symbol, p.bits_per_symbol, p.center_spacing)
+    return qad, np.asarray(pp).reshape(-1, 2), oracle.ppseq_to_bits_flat(pp, p.samples_per_symbol, p.bits_per_symbol, True, p.pause_threshold)
+
+
+def same(h, want, qad=None, tag=None):
+    wq, pp, flat = want
+    assert h.truncated == 0 and h.rows_needed == len(pp), (tag, h.truncated, h.rows_needed, len(pp))
+    assert np.array_equal(h.ppseq(), pp), tag
+    assert np.array_equal(h.bits(), flat[0]) and np.array_equal(h.msg_off, flat[1]) and np.array_equal(h.pauses, flat[2]), tag
+    assert np.array_equal(h.bit_sample_pos(), flat[3]) and np.array_equal(h.pos_offsets(), flat[4]), tag
+    for a, b in zip(h.flat(), flat):
+        assert np.array_equal(a, b), tag
+    if qad is not None:
+        assert np.array_equal(qad.cpu().numpy().view(np.uint32), wq.view(np.uint32)), tag
+
+
+def run_exact(pipe, oracle, caps, p, want_qad=True, **kw):
+    res = pipe.iq_to_bits_batch(caps, p, want_qad=want_qad, cap_rows="bound", **kw)
+    assert len(res) == len(caps) and res.truncated == []
+    for i, iq in enumerate(caps):
+        assert res[i].n_samples == len(iq) and res[i].seq == i
+        same(res[i], expected(oracle, iq, p), res.qad(i) if want_qad else None, (i, len(iq)))
+    return res
+
+
+def gap(iq, a, n):
+    iq = iq.copy()
+    iq[a:a + n] = 0
+    return iq
+
+
+@pytest.mark.parametrize("tol", [0, 5, 70])
+def test_lengths_around_the_tolerance_and_the_step(pipe, oracle, tol):
+    from urh_amd.batch import batch_step
+    S = batch_step()
+    lengths = [0, 1, 2, 3, max(tol - 1, 0), tol, tol + 1, tol + 2, S - 1, S, S + 1, 2 * S - 1, 2 * S, 2 * S + 1, 12_289, 70_001]
+    order = np.random.default_rng(tol).permutation(len(lengths))
+    caps = [synth_fsk(lengths[i], sps=10, seed=int(i), noise=0.05, pause_every=400, pause_len=130) for i in order]
+    p = params("FSK", 1, 0.1, tol, 10)
+    res = run_exact(pipe, oracle, caps, p)
+    if tol == 5:                     # the reference's negative final lengths come back as such
+        by_len = {len(c): res[i].ppseq().tolist() for i, c in enumerate(caps)}
+        assert by_len[1] == [[0, -4]] and by_len[3] == [[-1, -2]]
+        assert by_len[0] == []
+
+
+@pytest.mark.parametrize("sps,noise,bps", [(100, 0.0, 1), (100, 0.1, 1), (10, 0.1, 2), (8, 0.0, 3), (8, 0.1, 1)])
+def test_fsk_contents(pipe, oracle, sps, noise, bps):
+    from urh_amd.batch import batch_step
+    S, tol, pt = batch_step(), 5, 8
+    p = params("FSK", bps, noise, tol, sps, pt)
+    rng = np.random.default_rng(sps + bps)
+    base = synth_fsk(9001, sps=sps, seed=1, noise=0.03)
+    caps = [
+        synth_fsk(13_001, sps=sps, seed=2, noise=0.04, pause_every=3000, pause_len=700),           # gaps
+        (0.3 * rng.standard_normal((4001, 2))).astype(np.float32),                                   # noise only
+        np.zeros((1501, 2), np.float32),                                                              # everything gated: one PAUSE row
+        gap(base, S - 2, tol), gap(base, S - 3, tol + 1),                                             # a gap of tol / tol + 1 samples across a step boundary
+        gap(base, 2 * S - tol, tol), gap(base, 3 * S - 1, tol + 1),
+        gap(base, 1000, 3 * S + 17),                                                                  # longer than three steps
+        gap(gap(base, 0, 777), 9001 - 555, 555),                                                      # leading and trailing
+        gap(gap(base, 2000, pt * sps + sps // 2 - 1), 6000, pt * sps + sps // 2 + 2),                # pauses either side of pause_threshold symbols
+        gap(gap(base, 2000, (pt + 1) * sps), 5000, pt * sps),
+    ]
+    run_exact(pipe, oracle, caps, p)
+
+
+@pytest.mark.parametrize("bps,noise", [(1, 0.1), (2, 0.1), (1, 0.0)])
+def test_ask_contents(pipe, oracle, bps, noise):
+    p = params("ASK", bps, noise, 5, 100, 8)
+    caps = []
+    for i, n in enumerate((12_289, 20_001, 4096 * 3, 7001)):
+        iq = synth_fsk(n, sps=100, seed=100 + i, noise=0.04, pause_every=max(n // (2 + i % 3), 5000), pause_len=n // 19 + 901)
+        env = np.repeat(np.random.default_rng(i).integers(0, 2 ** bps, n // 100 + 1), 100)[:n] / (2 ** bps - 1)
+        iq = (iq * (0.05 + 0.95 * env)[:, None]).astype(np.float32)
+        caps.append(iq)
+        caps.append(gap(gap(iq, 1500, 37), 3000, 260))                                                # gaps shorter and longer than a symbol
+    caps.append(np.zeros((700, 2), np.float32))
+    run_exact(pipe, oracle, caps, p)
+
+
+@pytest.mark.parametrize("mod", ["FSK", "ASK"])
+@pytest.mark.parametrize("dtype", [np.float32, np.int8, np.uint8, np.int16, np.uint16])
+def test_sample_types_at_odd_offsets(pipe, oracle, mod, dtype):
+    """captures of odd length in front: the later ones start off 16-byte (int8: off 4-byte) alignment"""
+    scale = 1.0 if dtype == np.float32 else float(np.iinfo(dtype).max - np.iinfo(dtype).min) / 2
+    p = params(mod, 1, 0.2 * scale, 5, 20)
+    if mod == "ASK":
+        from dataclasses import replace
+        p = replace(p, center=0.3)
+    caps = [synth_fsk(n, sps=20, seed=n, noise=0.1, pause_every=500, pause_len=90, dtype=dtype) for n in (1, 3, 777, 5, 2049, 1, 4095, 64, 129)]
+    run_exact(pipe, oracle, caps, p)
+
+
+def test_the_neighbours_do_not_matter(pipe, oracle):
+    p = params("FSK", 1, 0.1, 5, 10)
+    x = synth_fsk(3001, sps=10, seed=5, noise=0.05, pause_every=700, pause_len=120)
+    loud = (3.0 * np.random.default_rng(0).standard_normal((555, 2))).astype(np.float32)
+    caps = [x, loud, x, np.zeros((63, 2), np.float32), synth_fsk(1000, sps=10, seed=6), x]
+    res = run_exact(pipe, oracle, caps, p)
+    for i in (2, 5):
+        assert np.array_equal(res[i].ppseq(), res[0].ppseq()) and np.array_equal(res[i].bits(), res[0].bits())
+        assert np.array_equal(res.qad(i).cpu().numpy().view(np.uint32), res.qad(0).cpu().numpy().view(np.uint32))
+
+
+@pytest.mark.parametrize("name", [c for c in GOLDEN_CASES if load_golden(c)["modulation_type"] != "PSK"])
+def test_reference_fixtures(pipe, oracle, name):
+    """[capture, its first half, capture] with the fixture's own parameters: entries 0 and 2 equal what the real reference recorded"""
+    from urh_amd.pipeline import DemodParams
+    g = load_golden(name)
+    assert g["modulation_type"] in ("ASK", "FSK")
+    p = DemodParams(g["modulation_type"], g["bits_per_symbol"], g["noise_threshold"], g["center"], g["center_spacing"], g["tolerance"],
+                    g["samples_per_symbol"], g["costas_loop_bandwidth"], g["pause_threshold"], False)
+    iq = g["iq"]
+    half = np.ascontiguousarray(iq[:len(iq) // 2])
+    res = pipe.iq_to_bits_batch([iq, half, iq], p, want_qad=True, cap_rows="bound")
+    assert res.truncated == []
+    for i in (0, 2):
+        h = res[i]
+        assert np.array_equal(res.qad(i).cpu().numpy().view(np.uint32), g["qad"].view(np.uint32))
+        assert np.array_equal(h.ppseq(), g["ppseq"])
+        assert np.array_equal(h.bits(), g["bits"]) and np.array_equal(h.msg_off, g["msg_off"]) and np.array_equal(h.pauses, g["pauses"])
+        assert np.array_equal(h.bit_sample_pos(), g["pos"]) and np.array_equal(h.pos_offsets(), g["pos_off"])
+    same(res[1], expected(oracle, half, p), res.qad(1), name)
+
+
+@pytest.mark.parametrize("k", [0, 1, 64, 65, 1025, 5000])
+def test_many_captures(pipe, oracle, k):
+    p = params("FSK", 1, 0.1, 2, 8)
+    rng = np.random.default_rng(k)
+    pool = synth_fsk(40_000, sps=8, seed=k, noise=0.08, pause_every=333, pause_len=41)
+    lengths = rng.integers(0, 301, k)
+    at = rng.integers(0, 39_000, k)
+    caps = [np.ascontiguousarray(pool[a:a + n]) for a, n in zip(at, lengths)]
+    res = run_exact(pipe, oracle, caps, p, want_qad=(k <= 65))
+    assert len(res) == k
+    if k == 0:
+        assert list(res) == [] and res.check() is res
+
+
+def test_a_capture_that_outgrows_its_region(pipe, oracle):
+    """default policy, tolerance 1, sps 100: 20 000 samples of noise make 3309 rows against a capacity of 864"""
+    from urh_amd import _lib
+    p = params("FSK", 1, 0.0, 1, 100)
+    noise = (0.3 * np.random.default_rng(1).standard_normal((20000, 2))).astype(np.float32)
+    caps = [synth_fsk(5001, sps=100, seed=1, noise=0.03), noise, synth_fsk(7001, sps=100, seed=2, noise=0.03, pause_every=2000, pause_len=900)]
+    want = [expected(oracle, c, p) for c in caps]
+    assert len(want[1][1]) == 3309
+    res = pipe.iq_to_bits_batch(caps, p, want_qad=True)
+    assert res.truncated == [1]
+    h = res[1]
+    assert h.truncated & 1 and h.rows_needed == 3309 and h.n_rows == 864
+    assert np.array_equal(h.ppseq(), want[1][1][:864])                         # what fitted is the table's beginning
+    with pytest.raises(_lib.UrhGpuError):
+        h.check()
+    for i in (0, 2):
+        same(res[i], want[i], res.qad(i), i)
+    again = res.retry(1)
+    assert again is res[1] and res.truncated == []
+    same(again, want[1], res.qad(1), "retry")
+    for i in (0, 2):                                                           # (the retry left the others' views alone)
+        same(res[i], want[i], res.qad(i), i)
+
+
+def test_a_long_capture_is_routed_through_a_pass(pipe, oracle):
+    p = params("FSK", 1, 0.1, 5, 100)
+    caps = [synth_fsk(n, sps=100, seed=n, noise=0.04, pause_every=5000, pause_len=1200) for n in (3001, 70_001, 0, 49_999, 50_000)]
+    res = run_exact(pipe, oracle, caps, p, long_from=50_000)
+    # ... and as device tensors, and already packed
+    import torch
+    dev = [torch.from_numpy(c).cuda() for c in caps]
+    want = [expected(oracle, c, p) for c in caps]
+    got = pipe.iq_to_bits_batch(dev, p, want_qad=True, cap_rows="bound", long_from=50_000)
+    for i in range(len(caps)):                     # (a batch's results are views that live until the pipeline's next batch)
+        same(got[i], want[i], got.qad(i), ("tensors", i))
+    starts = np.concatenate([[0], np.cumsum([len(c) for c in caps])])
+    packed = pipe.iq_to_bits_batch((torch.cat(dev), starts), p, want_qad=True, cap_rows="bound")
+    for i in range(len(caps)):
+        same(packed[i], want[i], packed.qad(i), ("packed", i))
+    assert len(res) == 5
+
+
+def test_launches_and_copies_do_not_depend_on_the_batch(pipe):
+    from urh_amd.batch import launch_counts
+    p = params("FSK", 1, 0.1, 2, 8)
+    pool = synth_fsk(20_000, sps=8, seed=9, noise=0.08, pause_every=333, pause_len=41)
+    spent = []
+    for k in (3, 5000):
+        caps = [pool[(37 * i) % 19_000:(37 * i) % 19_000 + (i % 300)] for i in range(k)]
+        before = launch_counts(pipe)
+        res = pipe.iq_to_bits_batch(caps, p)
+        after = launch_counts(pipe)
+        assert len(res) == k
+        spent.append((after[0] - before[0], after[1] - before[1]))
+    assert spent[0] == spent[1] == (3, 2), spent
+
+
+def test_options_of_a_pass_are_not_options_of_a_batch(pipe):
+    p = params()
+    caps = [synth_fsk(100, seed=1)]
+    for name in ("auto_center", "auto_noise", "msg_records", "dc_correction"):
+        with pytest.raises(ValueError):
+            pipe.iq_to_bits_batch(caps, p, **{name: True})
+    from dataclasses import replace
+    with pytest.raises(ValueError):
+        pipe.iq_to_bits_batch(caps, replace(p, modulation_type="PSK"))
+
+
+def test_fuzz(pipe, oracle):
+    """seeded batches of 40 captures of up to 20 000 samples with random choices from the lists above (URH_FUZZ_ROUNDS scales the
+    number of batches: 20 at the default of 4)"""
+    rounds = 5 * int(os.environ.get("URH_FUZZ_ROUNDS", "4"))
+    seed0 = int(os.environ.get("URH_FUZZ_SEED", "0"))
+    for r in range(rounds):
+        rng = np.random.default_rng(1000 * seed0 + r)
+        mod = str(rng.choice(["FSK", "ASK"]))
+        bps, tol, sps = int(rng.choice([1, 2, 3])), int(rng.choice([0, 5, 70])), int(rng.choice([100, 10, 8]))
+        dtype = [np.float32, np.int8, np.uint8, np.int16, np.uint16][int(rng.integers(0, 5))]
+        scale = 1.0 if dtype == np.float32 else float(np.iinfo(dtype).max - np.iinfo(dtype).min) / 2
+        p = params(mod, bps, float(rng.choice([0.0, 0.1])) * scale, tol, sps, int(rng.choice([0, 3, 8])))
+        caps = []
+        for i in range(40):
+            n = int(rng.choice([0, 1, 2, 3, 63, 64, 65, 127, 128, 129])) if rng.random() < 0.25 else int(rng.integers(0, 20_001) // int(rng.choice([1, 10, 100])))
+            iq = synth_fsk(n, sps=sps, seed=1000 * r + i, noise=float(rng.choice([0.02, 0.1, 0.4])), pause_every=int(rng.choice([0, 300, 2500])),
+                           pause_len=int(rng.choice([tol, tol + 1, 3 * 64 + 9, sps * 9 + 1, 40])), dtype=dtype)
+            if mod == "ASK" and dtype == np.float32 and n:
+                env = np.repeat(rng.integers(0, 2 ** bps, n // sps + 1), sps)[:n] / (2 ** bps - 1)
+                iq = (iq * (0.05 + 0.95 * env)[:, None]).astype(np.float32)
+            caps.append(iq)
+        res = pipe.iq_to_bits_batch(caps, p, want_qad=True, cap_rows="bound")
+        assert res.truncated == []
+        for i, iq in enumerate(caps):
+            same(res[i], expected(oracle, iq, p), res.qad(i), (r, i, mod, bps, tol, sps, np.dtype(dtype).name, len(iq)))

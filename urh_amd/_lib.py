@@ -230,6 +230,11 @@ PROTOTYPES = {
     "urhgpu_shard_dc_resolve_dev": (_i, [_vp, _vp, _i64, C.POINTER(C.c_uint32), _vp]),
     "urhgpu_shard_dc_apply_dev": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "urhgpu_shard_dc_stats": (_i, [_vp, C.POINTER(_i64)]),
+    "urhgpu_batch_step": (_i, []),
+    "urhgpu_batch_plan": (_i, [_vp, _i64, C.POINTER(Params), _i, _i64, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "urhgpu_iq_to_bits_batch_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _vp, _vp, _i64, _vp, _vp, _vp, _i64]),
+    "urhgpu_batch_fetch": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
+    "urhgpu_batch_launches": (_i, [_vp, C.POINTER(_i64)]),
 }
 
 _lib = None

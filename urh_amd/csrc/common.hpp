@@ -171,6 +171,7 @@ struct urhgpu_ctx {
     urh::Arena chunk_work;
     double *h_chunk = nullptr;             // pinned: {sum, max, sum not exact}
     long long chunk_launches = 0;          // kernel launches issued by urhgpu_chunk_power_stats_dev (urhgpu_chunk_stats_launches)
+    long long batch_launches = 0, batch_copies = 0;   // kernel launches / copies of urhgpu_iq_to_bits_batch_dev and urhgpu_batch_fetch (urhgpu_batch_launches)
     // automatic center inside a pass (urhgpu_detect_center_dev, urhgpu_iq_to_bits_auto_center_dev; msg_estimators.hip "center chain"): the
     // chain's scratch -- kept samples, tile tables, histogram pool, thresholds -- is its own, NOT the rotating pass arenas': every center
     // chain of a context runs on one stream, in order (center_stream), so the one scratch serves passes that overlap further down

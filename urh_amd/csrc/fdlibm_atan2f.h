@@ -23,6 +23,12 @@
 #define URH_HD static inline
 #endif
 
+// The correctly rounded fp32 quotient: the compiler's own division.  A translation unit may define URH_FDIV(a, b) before it includes this
+// file to reach the same float another way (batch.hip divides in fp64 and rounds once, see there).
+#ifndef URH_FDIV
+#define URH_FDIV(a, b) ((a) / (b))
+#endif
+
 URH_HD uint32_t urh_f2u(float f) {
     union { float f; uint32_t u; } v; v.f = f; return v.u;
 }
@@ -64,15 +70,15 @@ URH_HD float urh_atanf(float x) {
     float hi, lo, t;
     if (ix < 0x3f980000u) {                       // |x| < 1.1875
         if (ix < 0x3f300000u) {                   // 7/16 <= |x| < 11/16
-            hi = atanhi0; lo = atanlo0; t = (2.0f * ax - 1.0f) / (2.0f + ax);
+            hi = atanhi0; lo = atanlo0; t = URH_FDIV(2.0f * ax - 1.0f, 2.0f + ax);
         } else {                                  // 11/16 <= |x| < 19/16
-            hi = atanhi1; lo = atanlo1; t = (ax - 1.0f) / (ax + 1.0f);
+            hi = atanhi1; lo = atanlo1; t = URH_FDIV(ax - 1.0f, ax + 1.0f);
         }
     } else {
         if (ix < 0x401c0000u) {                   // |x| < 2.4375
-            hi = atanhi2; lo = atanlo2; t = (ax - 1.5f) / (1.0f + 1.5f * ax);
+            hi = atanhi2; lo = atanlo2; t = URH_FDIV(ax - 1.5f, 1.0f + 1.5f * ax);
         } else {                                  // 2.4375 <= |x| < 2^25
-            hi = atanhi3; lo = atanlo3; t = -1.0f / ax;
+            hi = atanhi3; lo = atanlo3; t = URH_FDIV(-1.0f, ax);
         }
     }
     float z = hi - ((urh_atanf_poly(t) - lo) - t);
@@ -118,7 +124,7 @@ URH_HD float urh_atan2f(float y, float x) {
     float z;
     if (k > 60) z = pi_o_2 + 0.5f * pi_lo;                    // |y/x| > 2^60
     else if ((hx >> 31) && k < -60) z = 0.0f;                 // |y|/x < -2^60
-    else z = urh_atanf(urh_u2f(urh_f2u(y / x) & 0x7fffffffu));
+    else z = urh_atanf(urh_u2f(urh_f2u(URH_FDIV(y, x)) & 0x7fffffffu));
     switch (m) {
         case 0: return z;
         case 1: return urh_u2f(urh_f2u(z) ^ 0x80000000u);

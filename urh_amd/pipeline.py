@@ -1112,6 +1112,23 @@ class DevicePipeline:
         _lib.check(_lib.load().urhgpu_iq_to_bits_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, C.byref(cp), C.byref(o)))
         return result()
 
+    def iq_to_bits_batch(self, captures, p: DemodParams, want_qad=False, cap_rows=None, long_from=None, **options):
+        """Many captures in one pass (urh_amd/batch.py; include/urhgpu.h "a batch of captures"): one upload, three launches whatever the
+        number of captures, one download.  For the short captures of a recording session, where a pass per capture is all fixed cost; long
+        captures still belong to passes and streams.
+        captures: a list of numpy arrays ((N, 2) of one of the five sample types, or complex64 (N,)) -- packed into ONE pinned staging buffer
+        and uploaded with one copy --, a list of device tensors, or (iq_cat, starts): the captures already back to back, capture k =
+        iq_cat[starts[k]:starts[k + 1]].
+        cap_rows: None = the stream's row capacity with a floor of 64 rows; "bound" = n / (tolerance + 1) + 2 per capture, which cannot
+        truncate; an int = that capacity for every capture.
+        long_from: a capture of that many samples or more goes through the ordinary iq_to_bits (a pass per capture) and takes its place in
+        the result; default batch.LONG_FROM_DEFAULT, the measured crossover.
+        Returns a batch.BatchBits: a sequence of HostBits, each equal to what iq_to_bits gives for that capture alone; .qad(k) (want_qad)
+        is capture k's slice of the demodulated signal on the device, .retry(k) runs a truncated capture again with the rows it needs.
+        ASK and FSK; PSK, auto_center, auto_noise, msg_records and dc_correction are not options of a batch (ValueError says what to call)."""
+        from .batch import iq_to_bits_batch
+        return iq_to_bits_batch(self, captures, p, want_qad, cap_rows, long_from, **options)
+
     def iq_to_bits_checked(self, iq, p: DemodParams, want_qad=True, msg_records=False, message_length_divisor=1) -> BitsResult:
         """iq_to_bits with the output capacities verified (one 40-byte read-back) and, if the default capacities were
         too small -- a capture that is mostly noise produces far more pulse-table rows than 4 per symbol --, one more
