@@ -1119,9 +1119,17 @@ int urhgpu_shard_msg_records_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_lo
  *            capture's blob in d_blob; d_dir[k] = the used part.  At d_dir[i] lies capture i's STANDARD compact result blob (above):
  *            header flags 0, int8 row_state, int32 row_len, bits packed most significant first, no position section (positions are
  *            a function of the rows: the host derives them).  A capture that outgrows its region stops storing and keeps counting:
- *            truncated bit 0 is set, rows_needed is exact, the blob holds what fitted; a wavefront never writes outside its region
- *            (truncated bit 3: the capture's start / end or its plan entry do not lie inside the buffers given -- nothing of it is
- *            read or stored).  k = 0 and captures of length 0 are accepted.
+ *            truncated bit 0 is set, rows_needed is exact, the blob holds what fitted -- the FIRST row-capacity rows of the table, and
+ *            the bits, msg_off and pauses that _ppseq_to_bits gives for exactly those rows as if the table ended there (the last stored
+ *            row closes the last message): the result of a shorter table, not a prefix of the full result's bits.  The demodulated
+ *            signal does not depend on the capacity.  A wavefront never writes outside its region.
+ *            truncated bit 3, a capture the pass refuses, in two forms.  Its start or end does not lie inside the buffer (a negative
+ *            start, start[i] > start[i + 1], start[i + 1] > total, more than 2^31 - 1 samples): nothing of it is read or stored,
+ *            rows_needed is 0 and truncated is 8.  Its plan entry alone is bad (a negative region offset or one that is no multiple of
+ *            16, a region that ends beyond work_bytes, a negative row capacity): its samples are valid, so it IS demodulated and
+ *            walked -- its slice of d_qad is written and rows_needed is exact -- but nothing is stored in the work buffer, and bit 0 is
+ *            set beside bit 3 when it needed any row.  In both forms rows, messages and bits are 0 and the blob is a well-formed empty
+ *            one (header, msg_off[0] = 0); the other captures are not affected.  k = 0 and captures of length 0 are accepted.
  *   Fetch    urhgpu_batch_fetch: the directory (one read of 8 (k + 1) bytes into h_dir), then ONE copy of d_dir[k] bytes into h_blob
  *            (pinned memory: at PCIe speed); synchronous.  *total_bytes = d_dir[k] (also on URHGPU_ERR_CAPACITY: cap_host too small).
  *   urhgpu_batch_step: samples a wavefront takes per step.  urhgpu_batch_launches: out2 = {kernel launches, copies} the two calls

@@ -145,6 +145,10 @@ def _pinned(torch, pool, key, nbytes):
 
 _META_ALIGN = 256
 
+# the pinned host buffer the blobs are first fetched into; a batch whose blobs are larger is told so by the fetch (which has read the
+# directory by then), grows the buffer to what the directory says and fetches once more
+FIRST_BLOB_BUFFER_BYTES = 8 << 20
+
 
 def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq=None, device_starts=None):
     """the short captures of a batch through the three launches.  caps: numpy arrays (packed and uploaded here, one copy), or device_iq (a
@@ -188,7 +192,7 @@ def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq
                                                C.c_void_p(qad.data_ptr()) if qad is not None else None, C.c_void_p(work.data_ptr()), work_bytes,
                                                C.c_void_p(counts.data_ptr()), C.c_void_p(d_dir.data_ptr()), C.c_void_p(blob.data_ptr()), blob_cap))
     h_dir = _pinned(torch, pool, "batch_dir", 8 * (k + 1))
-    h_blob = _pinned(torch, pool, "batch_blob", min(blob_cap, 8 << 20))
+    h_blob = _pinned(torch, pool, "batch_blob", min(blob_cap, FIRST_BLOB_BUFFER_BYTES))
     got = C.c_int64(0)
 
     def fetch():
