@@ -13,6 +13,7 @@ from dataclasses import replace
 import numpy as np
 
 from . import _lib
+from .host_bits import HostBits
 from .signal_functions import mod_code
 
 # a capture of this many samples or more goes through an ordinary pass: the capture length at which a batch's wavefront per capture stops
@@ -153,7 +154,6 @@ FIRST_BLOB_BUFFER_BYTES = 8 << 20
 def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq=None, device_starts=None):
     """the short captures of a batch through the three launches.  caps: numpy arrays (packed and uploaded here, one copy), or device_iq (a
     device tensor that holds them back to back) with device_starts.  Returns (HostBits list, qad tensor or None, device input, starts)."""
-    from .pipeline import HostBits
     torch, lib = pipe.torch, _lib.load()
     k = len(lengths)
     lengths = np.asarray(lengths, dtype=np.int64)

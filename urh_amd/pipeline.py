@@ -10,11 +10,12 @@ Parameter names/defaults follow the reference's Signal object
 """
 import array
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import numpy as np
 
 from . import _lib
+from .host_bits import HostBits, LazyDigitized, positions_from_rows  # noqa: F401  (also this module's exports)
 from .signal_functions import dtype_code, mod_code
 
 
@@ -35,7 +36,6 @@ class DemodParams:
         """demod_only: for afp_demod alone -- the slicing parameters (tolerance, samples_per_symbol, bits_per_symbol as a symbol
         width) play no part there and must not make it fail (the reference's qad depends on the demodulation parameters only)."""
         if demod_only:
-            from dataclasses import replace
             return replace(self, tolerance=0, samples_per_symbol=1, bits_per_symbol=max(1, int(self.bits_per_symbol))).to_c(dtype)
         mod, sentinel = mod_code(self.modulation_type)
         # the reference's own failures for these inputs: `uint16 tolerance` (signal_functions.pyx:392) raises
@@ -77,16 +77,42 @@ def _torch_dtype(t):
     return np.dtype(m[t.dtype])
 
 
-class BitsResult:
+class PassResult:
+    """The device buffers of one pass and its counts on the host: what BitsResult and a sharded pass's ShardResult share."""
+
+    def __init__(self, qad, rows, bits, msg_off, pauses, pos, pos_off, counts, params, ctx=None):
+        self.qad, self.rows_buf, self.bits_buf = qad, rows, bits
+        self.msg_off_buf, self.pauses_buf, self.pos_buf, self.pos_off_buf = msg_off, pauses, pos, pos_off
+        self.counts, self.params = counts, params
+        self._host_counts = None
+        self._ctx = ctx
+
+    def host_counts(self):
+        """(n_rows, n_msg, n_bits, n_pos): one 40-byte D2H copy (synchronises)."""
+        return self._read_counts()
+
+    def _read_counts(self):
+        if self._host_counts is None:
+            if self._ctx is not None:
+                self._ctx.join()          # pipelined mode: the current stream waits for the tail of the pass
+            c = self.counts.cpu().numpy()
+            self._host_counts = tuple(int(x) for x in c[:4])
+            self._rows_needed = int(c[4])
+        return self._host_counts
+
+    def check_capacity(self):
+        n_rows, n_msg, n_bits, n_pos = self.host_counts()
+        if self._rows_needed > self.rows_buf.shape[0] or n_msg > self.pauses_buf.shape[0] or n_bits > self.bits_buf.shape[0] \
+                or (self.pos_buf is not None and n_pos > self.pos_buf.shape[0]):
+            raise _lib.UrhGpuError(_lib.ERR_CAPACITY, f"output capacity too small: rows={self._rows_needed} msgs={n_msg} "
+                                                      f"bits={n_bits} pos={n_pos}")
+
+
+class BitsResult(PassResult):
     """Device-resident outputs of one IQ->bits pass (torch tensors) + lazy host views."""
 
     def __init__(self, qad, rows, bits, msg_off, pauses, pos, pos_off, counts, params, ctx=None, pipe=None, outputs=None):
-        self.qad, self.rows_buf, self.bits_buf = qad, rows, bits
-        self.msg_off_buf, self.pauses_buf, self.pos_buf, self.pos_off_buf = msg_off, pauses, pos, pos_off
-        self.counts = counts
-        self.params = params
-        self._host_counts = None
-        self._ctx = ctx
+        super().__init__(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, params, ctx)
         self._pipe, self._outputs = pipe, outputs          # the pipeline and the C descriptor of the pass: host() packs through them
         self._outputs_pos, self._pos_dev = outputs, pos    # msg_records passes that ship no positions: the descriptor WITH the positions the pass computed
         self._hostbits = None
@@ -124,12 +150,23 @@ class BitsResult:
         flat = self._flat(True)
         return messages_from_records(flat, rec, self.params, sample_rate, timestamp)
 
-    def _requeue_records(self, again):
-        """a pass that was sliced again on the host's decision (auto_center flag 2 / 3, auto_noise flag 2): its records again, for the new slicing"""
-        if self._rec is None:
-            return
-        _, _, iq, divisor, slot = self._rec
-        self._rec = self._pipe._queue_records(iq, self.params, again._outputs_pos, divisor, slot) + (iq, divisor, slot)
+    def queue_records(self, iq, divisor, slot, of=None):
+        """queue the message records of the capture iq behind the pass (DevicePipeline._queue_records), nothing waited for: .records and
+        .message_data() hand them out.  of: the result whose tables the records read -- this pass sliced again --, default this one"""
+        o = (self if of is None else of)._outputs_pos
+        self._rec = self._pipe._queue_records(iq, self.params, o, divisor, slot) + (iq, int(divisor), slot)
+
+    def _slice_again(self, signal, params, slot, adopt_qad=False):
+        """the host's decision (auto_center flag 2 / 3, auto_noise flag 2): slice `signal` with `params` into the slot's second set of
+        tables, the records again for the new slicing, and this result becomes that one -- its demodulated signal too where adopt_qad"""
+        again = self._pipe.qad_to_bits(signal, params, slot=slot, compute_pos=self._rec is not None)
+        if self._rec is not None:
+            self.queue_records(self._rec[2], self._rec[3], slot, of=again)
+        again.check_capacity()
+        for name in (("qad",) if adopt_qad else ()) + ("rows_buf", "bits_buf", "msg_off_buf", "pauses_buf", "pos_buf", "pos_off_buf", "counts", "_host_counts",
+                                                       "_rows_needed", "_ctx", "_outputs", "_outputs_pos", "_pos_dev"):
+            setattr(self, name, getattr(again, name))
+        self._hostbits = None
 
     @property
     def noise_flag(self):
@@ -184,14 +221,7 @@ class BitsResult:
             if self._noise_flag == 2:
                 self._auto = None                            # (no demodulated signal: nothing to find a center on)
                 torch = self._pipe.torch
-                again = self._pipe.qad_to_bits(torch.zeros(2, dtype=torch.float32, device=self._pipe.device), self.params, slot=slot,
-                                               compute_pos=self._rec is not None)
-                self._requeue_records(again)
-                again.check_capacity()
-                for name in ("qad", "rows_buf", "bits_buf", "msg_off_buf", "pauses_buf", "pos_buf", "pos_off_buf", "counts", "_host_counts", "_rows_needed",
-                             "_ctx", "_outputs", "_outputs_pos", "_pos_dev"):
-                    setattr(self, name, getattr(again, name))
-                self._hostbits = None
+                self._slice_again(torch.zeros(2, dtype=torch.float32, device=self._pipe.device), self.params, slot, adopt_qad=True)
         if self._auto is None:
             return
         (block, max_size, slot), self._auto = self._auto, None
@@ -200,14 +230,7 @@ class BitsResult:
         self._center_flag = flag
         self._center = center
         if flag in (2, 3) and center is not None:
-            from dataclasses import replace
-            again = self._pipe.qad_to_bits(self.qad, replace(self.params, center=center), slot=slot, compute_pos=self._rec is not None)
-            self._requeue_records(again)
-            again.check_capacity()
-            for name in ("rows_buf", "bits_buf", "msg_off_buf", "pauses_buf", "pos_buf", "pos_off_buf", "counts", "_host_counts", "_rows_needed", "_ctx",
-                         "_outputs", "_outputs_pos", "_pos_dev"):
-                setattr(self, name, getattr(again, name))
-            self._hostbits = None
+            self._slice_again(self.qad, replace(self.params, center=center), slot)
 
     def host(self, pool=None) -> "HostBits":
         """The results ON THE HOST through the compact blob (include/urhgpu.h): one more kernel packs them (5 B per pulse-table row, one bit
@@ -255,25 +278,9 @@ class BitsResult:
         return h
 
     def host_counts(self):
-        """(n_rows, n_msg, n_bits, n_pos): one 32-byte D2H copy (synchronises)."""
+        """the counts of the pass as it is handed out: settled first"""
         self._settle()
         return self._read_counts()
-
-    def _read_counts(self):
-        if self._host_counts is None:
-            if self._ctx is not None:
-                self._ctx.join()          # pipelined mode: the current stream waits for the tail of the pass
-            c = self.counts.cpu().numpy()
-            self._host_counts = tuple(int(x) for x in c[:4])
-            self._rows_needed = int(c[4])
-        return self._host_counts
-
-    def check_capacity(self):
-        n_rows, n_msg, n_bits, n_pos = self.host_counts()
-        if self._rows_needed > self.rows_buf.shape[0] or n_msg > self.pauses_buf.shape[0] or n_bits > self.bits_buf.shape[0] \
-                or (self.pos_buf is not None and n_pos > self.pos_buf.shape[0]):
-            raise _lib.UrhGpuError(_lib.ERR_CAPACITY, f"output capacity too small: rows={self._rows_needed} msgs={n_msg} "
-                                                      f"bits={n_bits} pos={n_pos}")
 
     def _through_blob(self):
         """Do the host accessors go through the compact blob?  Not for a result the pipeline did not make, and not when the pack kernel found
@@ -355,262 +362,6 @@ class BitsResult:
         return ["".join(map(str, d)) for d in data]
 
 
-class LazyDigitized:
-    """(ppseq, bits, msg_off, pauses, pos, pos_off) of one digitisation as a sequence whose members are widened to the reference's
-    types when somebody looks: what crossed PCIe is the compact blob (a HostBits over pinned memory), and a caller that only wants
-    the bits never pays for the int64 pulse table.  materialize() widens everything and lets go of the pinned buffer."""
-
-    def __init__(self, host: "HostBits", want_pos: bool = True):
-        self._h = host.check()
-        self._want_pos = want_pos
-        self._v = [None] * 6
-
-    def _get(self, i):
-        if self._v[i] is None:
-            h = self._h
-            if i == 0:
-                self._v[0] = h.ppseq()
-            elif i == 1:
-                self._v[1] = h.bits()
-            elif i == 2:
-                self._v[2] = h.msg_off.copy()
-            elif i == 3:
-                self._v[3] = h.pauses.copy()
-            elif i == 4:
-                self._v[4] = h.bit_sample_pos() if self._want_pos else np.zeros(0, np.int64)
-            else:
-                self._v[5] = h.pos_offsets() if self._want_pos else h.pos_off.copy()
-        return self._v[i]
-
-    def materialize(self):
-        if self._h is not None:
-            for i in range(6):
-                self._get(i)
-            self._h = None
-        return self
-
-    def __len__(self):
-        return 6
-
-    def __getitem__(self, k):
-        if isinstance(k, slice):
-            return tuple(self._get(i) for i in range(*k.indices(6)))
-        return self._get(range(6)[k])
-
-    def __iter__(self):
-        return (self._get(i) for i in range(6))
-
-
-class HostBits:
-    """One pass's results ON THE HOST, from the compact blob (include/urhgpu.h "compact result blob"): numpy views of pinned memory
-    owned by the stream -- valid until three pushes later; copy what has to live longer.  The accessors widen to the reference's own
-    shapes and types: ppseq() is grab_pulse_lens' int64 (P, 2), bits() one byte per bit, bit_sample_pos() int64."""
-
-    def __init__(self, r: "_lib.HostResult", params):
-        self.seq, self.n_samples = int(r.seq), int(r.n_samples)
-        self.n_rows, self.n_msg, self.n_bits, self.n_pos = int(r.n_rows), int(r.n_msg), int(r.n_bits), int(r.n_pos)
-        self.rows_needed, self.truncated, self.blob_bytes = int(r.rows_needed), int(r.truncated), int(r.blob_bytes)
-        self.params = params
-        self.d_qad_ptr = r.d_qad
-        # the views are made when somebody looks (a push per 0.3 ms must not allocate a dozen objects each)
-        self._len16 = (r.row_len16, r.esc, int(r.n_esc)) if r.row_len16 else None      # 16-bit lengths + escape list (URHGPU_BLOB_LEN16)
-        self._row16 = (r.row16, r.esc, int(r.n_esc)) if getattr(r, "row16", None) else None      # state | length words + escape list (URHGPU_BLOB_ROW16)
-        self._ptr = dict(row_len=(r.row_len, self.n_rows, np.int32), row_state=(r.row_state, self.n_rows, np.int8),
-                         bits_packed=(r.bits_packed, (self.n_bits + 7) // 8, np.uint8), msg_off=(r.msg_off, self.n_msg + 1, np.int64),
-                         pauses=(r.pauses, self.n_msg, np.int64), pos_off=(r.pos_off, self.n_msg + 1, np.int64),
-                         pos32=(r.pos32, self.n_pos, np.uint32) if r.pos32 else None)
-
-    def __getattr__(self, name):
-        spec = self.__dict__.get("_ptr", {}).get(name, False)
-        if spec is False:
-            raise AttributeError(name)
-        if name in ("row_len", "row_state") and self.__dict__.get("_row16") is not None:
-            # one uint16 per row: (state + 1) << 13 | length; a length field of 0x1FFF = look the row up in the escape list
-            p16, pesc, n_esc = self._row16
-            if self.n_rows <= 0:
-                state, value = np.zeros(0, np.int8), np.zeros(0, np.int32)
-            else:
-                w = np.frombuffer((C.c_ubyte * (2 * self.n_rows)).from_address(p16), dtype=np.uint16, count=self.n_rows)
-                state = ((w >> 13).astype(np.int16) - 1).astype(np.int8)
-                value = (w & 0x1FFF).astype(np.int32)
-                marked = value == 0x1FFF
-                rows = np.zeros(0, np.int64)
-                if n_esc > 0:
-                    e = np.frombuffer((C.c_ubyte * (8 * n_esc)).from_address(pesc), dtype=np.uint32, count=2 * n_esc).reshape(-1, 2)
-                    rows = e[:, 0].astype(np.int64)
-                if int(marked.sum()) != n_esc or (n_esc and (rows.max() >= self.n_rows or not marked[rows].all() or len(np.unique(rows)) != n_esc)):
-                    raise _lib.UrhGpuError(_lib.ERR_UNSUPPORTED, "compact blob: the packed rows and their escape list do not match")
-                if n_esc > 0:
-                    value[rows] = e[:, 1].copy().view(np.int32)
-            self.__dict__["row_len"], self.__dict__["row_state"] = value, state
-            return self.__dict__[name]
-        if name == "row_len" and self.__dict__.get("_len16") is not None:
-            # widen the shipped uint16 lengths; 0xFFFF = look the row up in the escape list ({uint32 row, int32 length} pairs)
-            p16, pesc, n_esc = self._len16
-            if self.n_rows <= 0:
-                value = np.zeros(0, np.int32)
-            else:
-                value = np.frombuffer((C.c_ubyte * (2 * self.n_rows)).from_address(p16), dtype=np.uint16, count=self.n_rows).astype(np.int32)
-                marked = value == 0xFFFF
-                rows = np.zeros(0, np.int64)
-                if n_esc > 0:
-                    e = np.frombuffer((C.c_ubyte * (8 * n_esc)).from_address(pesc), dtype=np.uint32, count=2 * n_esc).reshape(-1, 2)
-                    rows = e[:, 0].astype(np.int64)
-                # every 0xFFFF has its entry and every entry its 0xFFFF (a true length of 65535 is an entry too)
-                if int(marked.sum()) != n_esc or (n_esc and (rows.max() >= self.n_rows or not marked[rows].all() or len(np.unique(rows)) != n_esc)):
-                    raise _lib.UrhGpuError(_lib.ERR_UNSUPPORTED, "compact blob: the 16-bit row lengths and their escape list do not match")
-                if n_esc > 0:
-                    value[rows] = e[:, 1].copy().view(np.int32)
-            self.__dict__[name] = value
-            return value
-        if spec is None:
-            value = None
-        else:
-            ptr, count, dtype = spec
-            if not ptr or count <= 0:
-                value = np.zeros(0, dtype)
-            else:
-                nbytes = count * np.dtype(dtype).itemsize
-                value = np.frombuffer((C.c_ubyte * nbytes).from_address(ptr), dtype=dtype, count=count)
-        self.__dict__[name] = value
-        return value
-
-    @classmethod
-    def from_blob(cls, host_ptr: int, params, seq: int = 0, n_samples: int = 0, d_qad: int = 0):
-        """the same object from a compact blob that lies in host memory at host_ptr (header first; include/urhgpu.h): what
-        urhgpu_stream_* hands out for a single-GPU stream, made here for blobs copied by other means (sharded passes)"""
-        hdr = np.frombuffer((C.c_ubyte * 128).from_address(host_ptr), dtype=np.int64, count=16)
-        if int(hdr[0]) != _lib.BLOB_MAGIC:
-            raise ValueError("not a result blob")
-        r = _lib.HostResult()
-        r.seq, r.n_samples = seq, n_samples
-        r.n_rows, r.n_msg, r.n_bits, r.n_pos, r.rows_needed = (int(hdr[k]) for k in (1, 2, 3, 4, 5))
-        r.blob_bytes = abs(int(hdr[6]))
-        r.truncated = int(hdr[15])
-        r.pauses, r.msg_off, r.pos_off = host_ptr + int(hdr[8]), host_ptr + int(hdr[9]), host_ptr + int(hdr[10])
-        r.row_state, r.bits_packed, r.row_len = host_ptr + int(hdr[11]), host_ptr + int(hdr[12]), host_ptr + int(hdr[13])
-        if int(hdr[7]) & _lib.BLOB_ROW16:
-            n_esc = int(np.frombuffer((C.c_ubyte * 8).from_address(host_ptr + int(hdr[11])), dtype=np.int64, count=1)[0])
-            r.row16, r.row_len, r.row_state, r.esc, r.n_esc = r.row_len, None, None, host_ptr + int(hdr[11]) + 8, abs(n_esc)
-        elif int(hdr[7]) & _lib.BLOB_LEN16:
-            off_esc = (int(hdr[12]) + (int(hdr[3]) + 7) // 8 + 15) & ~15
-            n_esc = int(np.frombuffer((C.c_ubyte * 8).from_address(host_ptr + off_esc), dtype=np.int64, count=1)[0])
-            r.row_len16, r.row_len, r.esc, r.n_esc = r.row_len, None, host_ptr + off_esc + 8, abs(n_esc)
-        r.pos32 = host_ptr + int(hdr[14]) if int(hdr[7]) & 1 else None
-        r.blob = host_ptr
-        r.d_qad = d_qad or None
-        return cls(r, params)
-
-    def check(self):
-        if self.truncated & 4:
-            raise _lib.UrhGpuError(_lib.ERR_UNSUPPORTED, "a row length, position or state does not fit the compact blob's narrow types "
-                                                         "(take the wide device outputs)")
-        if self.truncated:
-            raise _lib.UrhGpuError(_lib.ERR_CAPACITY, f"output capacity too small: the pulse table needs {self.rows_needed} rows")
-        return self
-
-    def ppseq(self) -> np.ndarray:
-        out = np.empty((self.n_rows, 2), np.int64)
-        out[:, 0] = self.row_state
-        out[:, 1] = self.row_len
-        if self.n_rows and self.row_state[0] == -128:        # a sharded ASK piece whose first row was merged into the previous rank's last
-            return out[1:]                                   # row (URHGPU_ROW_ABSORBED): not a row of this piece, as ShardResult.piece() has it
-        return out
-
-    def bits(self) -> np.ndarray:
-        return np.unpackbits(self.bits_packed, count=self.n_bits) if self.n_bits else np.zeros(0, np.uint8)
-
-    def bit_sample_pos(self) -> np.ndarray:
-        """All messages' bit_sample_pos back to back (int64; message m: [pos_offsets()[m], pos_offsets()[m + 1])).  With positions shipped
-        (want_pos) they are the device's; without, they are derived HERE from the pulse table that was shipped -- they are a function
-        of it (ProtocolAnalyzer.py:346-401 computes them from ppseq too), so not shipping them costs no information, only host time
-        when somebody asks."""
-        if self.pos32 is not None:
-            return self.pos32.astype(np.int64)
-        return self._derived_positions()[0]
-
-    def pos_offsets(self) -> np.ndarray:
-        return self.pos_off.copy() if self.pos32 is not None else self._derived_positions()[1]
-
-    def _derived_positions(self):
-        if self.__dict__.get("sharded_piece"):
-            raise ValueError("a rank's piece of a sharded capture does not start at sample 0 of the capture: its positions are not derivable "
-                             "from its rows alone -- run the pass with write_bit_sample_pos=True to have them shipped")
-        if getattr(self, "_derived", None) is None:
-            self._derived = positions_from_rows(self.row_state, self.row_len, self.params)
-        return self._derived
-
-    def flat(self):
-        """(bits u8, msg_off i64, pauses i64, pos i64, pos_off i64): what BitsResult.flat() gives"""
-        return self.bits(), self.msg_off.copy(), self.pauses.copy(), self.bit_sample_pos(), self.pos_offsets()
-
-    def message_data(self, sample_rate=1e6, timestamp=0.0):
-        """results of a stream with msg_records: the list of protocol.MessageData ProtocolAnalyzer.get_protocol_from_signal builds its Message
-        objects from -- bits, pause and positions padded where the pass's record says so, RSSI and timestamp from the record.  Without
-        shipped positions (want_pos=False) bit_sample_pos is derived here from the pulse table."""
-        from .protocol import messages_from_records
-        rec = self.__dict__.get("records")
-        if rec is None:
-            raise ValueError("this result carries no message records (CaptureStream(msg_records=True))")
-        self.check()
-        if len(rec) != self.n_msg or not (rec["flag"] == 1).all():
-            raise _lib.UrhGpuError(_lib.ERR_CAPACITY, "output capacity too small: a message's record is missing")
-        return messages_from_records(self.flat(), rec, self.params, sample_rate, timestamp)
-
-
-def positions_from_rows(row_state, row_len, p):
-    """bit_sample_pos of every message from the pulse table, as ProtocolAnalyzer._ppseq_to_bits builds them (:346-411), on whole arrays:
-    (positions int64, back to back; offsets int64[n_msg + 1]).  A message's entries: one position per bit (total_samples + k *
-    samples_per_bit), then [start, end] of the long pause that closed it -- or the capture's total_samples for the trailing message."""
-    st = np.asarray(row_state, dtype=np.int64)
-    ln = np.asarray(row_len, dtype=np.int64)
-    n = len(st)
-    sps, bps, pt = int(p.samples_per_symbol), int(p.bits_per_symbol), int(p.pause_threshold)
-    spb = int(sps / bps)
-    if n == 0:
-        return np.zeros(0, np.int64), np.zeros(1, np.int64)
-    ts = np.concatenate([[0], np.cumsum(ln)[:-1]])              # total_samples before each row
-    q = ln // sps
-    nsym = q + (2 * (ln - q * sps) > sps)                         # int(x) + (fraction > 0.5): exact for these integers
-    pause = st == -1
-    long_pause = pause & (nsym > pt) & (pt != 0)
-    nbits = np.where(long_pause, 0, nsym * bps)
-    data = ~pause & (nsym > 0)
-    if pause[0]:                                                  # "Starts with Pause": only seeds total_samples
-        nbits[0] = 0
-        long_pause[0] = False
-    grp = np.cumsum(long_pause) - long_pause                      # group of each row (a long pause closes its own group)
-    n_grp = int(grp[-1]) + 1
-    has_data = np.bincount(grp[data], minlength=n_grp) > 0
-    # "elif not there_was_data": a long pause after a group without data drops what was gathered; such a group is no message
-    closed = np.zeros(n_grp, dtype=bool)
-    closed[grp[long_pause]] = True
-    close_row = np.full(n_grp, -1, dtype=np.int64)
-    close_row[grp[long_pause]] = np.nonzero(long_pause)[0]
-    kept = has_data
-    row_kept = kept[grp] & (nbits > 0)
-    cnt = nbits[row_kept]
-    per_bit_base = np.repeat(ts[row_kept], cnt)
-    first = np.cumsum(cnt) - cnt
-    k = np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(first, cnt)
-    bit_pos = per_bit_base + k * spb
-    bits_per_group = np.bincount(grp[row_kept], weights=cnt, minlength=n_grp).astype(np.int64)
-    msgs = np.nonzero(kept)[0]
-    total_end = int(ts[-1] + ln[-1])
-    out, off = [], [0]
-    bit_cursor = np.concatenate([[0], np.cumsum(bits_per_group[msgs])])
-    for j, g in enumerate(msgs.tolist()):
-        out.append(bit_pos[bit_cursor[j]:bit_cursor[j + 1]])
-        if closed[g]:
-            r = int(close_row[g])
-            out.append(np.array([ts[r], ts[r] + ln[r]], dtype=np.int64))
-        else:
-            out.append(np.array([total_end], dtype=np.int64))
-        off.append(off[-1] + int(bits_per_group[g]) + (2 if closed[g] else 1))
-    pos = np.concatenate(out) if out else np.zeros(0, np.int64)
-    return pos.astype(np.int64), np.asarray(off, dtype=np.int64)
-
-
 def raise_noise_error(value: float):
     """what AutoInterpretation.detect_noise_level raises where urhgpu_noise_result's flag is 0: math.ceil of a NaN or of an infinity"""
     import math
@@ -623,21 +374,33 @@ def settle_center(pipe, block_ptr: int, qad, max_size):
     of a tied histogram): the device's center for flag 1, None for flag 0; flag 3 -- peaks_center on the shipped histogram, with the
     edges the device binned with --, flag 2 (or a tied histogram that was not shipped) -- the single-range estimator on the demodulated
     signal `qad` (device tensor)."""
-    from . import estimators
     r = _lib.CenterResult.from_address(block_ptr)
-    flag = int(r.flag)
+    flag, nb = int(r.flag), int(r.n_bins)
+    counts = _host_u32(block_ptr + C.sizeof(_lib.CenterResult), nb) if int(r.n_counts) == nb and nb > 0 else None
+    return flag, decide_center(flag, r.center, counts, r.e0, r.delta, pipe, qad, max_size)
+
+
+def _host_u32(ptr: int, n: int):
+    """n uint32 in host memory at ptr, as a numpy view"""
+    return np.frombuffer((C.c_ubyte * (4 * n)).from_address(ptr), dtype=np.uint32, count=n)
+
+
+def decide_center(flag, device_center, counts, e0, delta, pipe, qad, max_size):
+    """The center of an auto_center pass from what its device part reported (include/urhgpu.h: urhgpu_center_result), a Python float or
+    None.  flag 1: the device's center; 0: None; 3 with the tied histogram shipped (counts; None where it was not) -- peaks_center on it,
+    with the edges e0 + i * delta the device binned with; 2, or 3 without the histogram -- the single-range estimator on the demodulated
+    signal `qad` (device tensor)."""
     if flag == 1:
-        return flag, float(r.center)
+        return float(device_center)
     if flag == 0:
-        return flag, None
-    nb = int(r.n_bins)
-    if flag == 3 and int(r.n_counts) == nb and nb > 0:
-        counts = np.frombuffer((C.c_ubyte * (4 * nb)).from_address(block_ptr + C.sizeof(_lib.CenterResult)), dtype=np.uint32, count=nb).astype(np.int64)
-        edges = float(r.e0) + np.arange(nb + 1, dtype=np.float64) * float(r.delta)         # np.arange's fill: first + i * (second - first)
-        c = estimators.peaks_center(counts, edges)
+        return None
+    from . import estimators
+    if flag == 3 and counts is not None:
+        edges = float(e0) + np.arange(len(counts) + 1, dtype=np.float64) * float(delta)    # np.arange's fill: first + i * (second - first)
+        c = estimators.peaks_center(counts.astype(np.int64), edges)
     else:
         c = estimators.detect_center_dev(pipe, qad, max_size=max_size, _single=True)
-    return flag, (None if c is None else float(c))
+    return None if c is None else float(c)
 
 
 class CaptureStream:
@@ -766,32 +529,32 @@ class CaptureStream:
         center, flag, hist, nb, e0, delta = C.c_double(0.0), C.c_int64(0), C.c_void_p(), C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
         _lib.check(lib.urhgpu_stream_center(self._h, h.seq, C.byref(center), C.byref(flag), C.byref(hist), C.byref(nb), C.byref(e0), C.byref(delta)))
         h.center_flag = int(flag.value)
-        h.center = float(center.value) if h.center_flag == 1 else None
-        if h.center_flag not in (2, 3):
+        qad = None
+        if h.center_flag in (2, 3):
+            torch = pipe.torch
+            pipe.ctx.set_stream(torch.cuda.current_stream(pipe.device).cuda_stream)
+            qad = torch.empty(h.n_samples, dtype=torch.float32, device=pipe.device)
+            _lib.check(lib.urhgpu_memcpy_dtod(pipe.ctx.handle, C.c_void_p(qad.data_ptr()), C.c_void_p(h.d_qad_ptr), h.n_samples * 4))
+        h.center = decide_center(h.center_flag, center.value, _host_u32(hist.value, nb.value) if hist.value else None, e0.value, delta.value,
+                                 pipe, qad, self._center_max_size)
+        if qad is None or h.center is None:
             return h
-        from dataclasses import replace
-        from . import estimators
-        torch = pipe.torch
-        pipe.ctx.set_stream(torch.cuda.current_stream(pipe.device).cuda_stream)
-        qad = torch.empty(h.n_samples, dtype=torch.float32, device=pipe.device)
-        _lib.check(lib.urhgpu_memcpy_dtod(pipe.ctx.handle, C.c_void_p(qad.data_ptr()), C.c_void_p(h.d_qad_ptr), h.n_samples * 4))
-        if h.center_flag == 3 and hist.value:
-            counts = np.frombuffer((C.c_ubyte * (4 * nb.value)).from_address(hist.value), dtype=np.uint32, count=nb.value).astype(np.int64)
-            c = estimators.peaks_center(counts, e0.value + np.arange(nb.value + 1, dtype=np.float64) * delta.value)
-        else:
-            c = estimators.detect_center_dev(pipe, qad, max_size=self._center_max_size, _single=True)
-        if c is None:
-            return h
-        p = replace(self.params, center=float(c), write_bit_sample_pos=h.pos32 is not None)
-        again = pipe.qad_to_bits(qad, p, slot="stream", compute_pos=self._msg_records)
+        g = self._sliced_again(h, qad, center=h.center)
+        g.center, g.center_flag = h.center, h.center_flag
+        if self._auto_noise:
+            g.noise_threshold, g.noise_flag = h.noise_threshold, h.noise_flag
+        return g
+
+    def _sliced_again(self, h: "HostBits", qad, **changed):
+        """a pass sliced again at its hand-out (auto_center flag 2 / 3, auto_noise flag 2): the result of slicing `qad` with the stream's
+        parameters and what `changed` of them, in h's place in the stream, its records included"""
+        p = replace(self.params, write_bit_sample_pos=h.pos32 is not None, **changed)
+        again = self.pipe.qad_to_bits(qad, p, slot="stream", compute_pos=self._msg_records)
         again.check_capacity()
         g = again.host(pool={})                               # (a pinned buffer of its own: the result lives as long as the caller keeps it)
         g.seq, g.n_samples, g.d_qad_ptr, g.params = h.seq, h.n_samples, h.d_qad_ptr, self.params
         if self._msg_records:
             g = self._records_again(g, again, p)
-        g.center, g.center_flag = float(c), h.center_flag
-        if self._auto_noise:
-            g.noise_threshold, g.noise_flag = h.noise_threshold, h.noise_flag
         return g
 
     def _final_noise(self, h: "HostBits"):
@@ -805,16 +568,9 @@ class CaptureStream:
             raise_noise_error(h.noise_threshold)
         if h.noise_flag != 2:
             return h
-        from dataclasses import replace
         torch = pipe.torch
         pipe.ctx.set_stream(torch.cuda.current_stream(pipe.device).cuda_stream)
-        p = replace(self.params, write_bit_sample_pos=h.pos32 is not None)
-        again = pipe.qad_to_bits(torch.zeros(2, dtype=torch.float32, device=pipe.device), p, slot="stream", compute_pos=self._msg_records)
-        again.check_capacity()
-        g = again.host(pool={})                               # (a pinned buffer of its own: the result lives as long as the caller keeps it)
-        g.seq, g.n_samples, g.d_qad_ptr, g.params = h.seq, h.n_samples, h.d_qad_ptr, self.params
-        if self._msg_records:
-            g = self._records_again(g, again, p)
+        g = self._sliced_again(h, torch.zeros(2, dtype=torch.float32, device=pipe.device))
         g.noise_threshold, g.noise_flag = h.noise_threshold, 2
         if self._auto_center:
             g.center, g.center_flag = None, 0
@@ -934,6 +690,71 @@ class DevicePipeline:
             self._bufs[name] = t
         return t[:need].view(*shape)
 
+    def _pinned_block(self, key, nbytes):
+        """the zeroed pinned host block kept under `key`, made anew where there is none yet or it is shorter than nbytes"""
+        block = self._pinned.get(key)
+        if block is None or block.numel() < nbytes:
+            block = self.torch.zeros(nbytes, dtype=self.torch.uint8).pin_memory()
+            self._pinned[key] = block
+        return block
+
+    @staticmethod
+    def _outputs(qad, rows, bits, msg_off, pauses, pos, pos_off, counts):
+        """the C descriptor of a result's buffers, the capacities being their lengths"""
+        o = _lib.Outputs()
+        o.qad = qad.data_ptr() if qad is not None else None
+        o.rows = rows.data_ptr(); o.cap_rows = int(rows.shape[0])
+        o.bits = bits.data_ptr(); o.cap_bits = int(bits.shape[0])
+        o.msg_off = msg_off.data_ptr(); o.pauses = pauses.data_ptr(); o.cap_msg = int(pauses.shape[0])
+        o.pos = pos.data_ptr() if pos is not None else None
+        o.cap_pos = int(pos.shape[0]) if pos is not None else 0
+        o.pos_off = pos_off.data_ptr()
+        o.counts = counts.data_ptr()
+        return o
+
+    def _output_set(self, prefix, n_qad, capacities, want_pos):
+        """The output buffers of a pass, kept under `prefix` + their names, for the capacities (rows, bits, messages, positions) -- the
+        demodulated signal of n_qad samples (None: none), the positions only where want_pos -- and their C descriptor:
+        ((qad, rows, bits, msg_off, pauses, pos, pos_off, counts), descriptor)."""
+        torch = self.torch
+        cap_rows, cap_bits, cap_msg, cap_pos = capacities
+        bufs = (self._buf(prefix + "qad", (n_qad,), torch.float32) if n_qad is not None else None,
+                self._buf(prefix + "rows", (cap_rows, 2), torch.int64),
+                self._buf(prefix + "bits", (cap_bits,), torch.uint8),
+                self._buf(prefix + "msg_off", (cap_msg + 1,), torch.int64),
+                self._buf(prefix + "pauses", (cap_msg,), torch.int64),
+                self._buf(prefix + "pos", (cap_pos,), torch.int64) if want_pos else None,
+                self._buf(prefix + "pos_off", (cap_msg + 1,), torch.int64),
+                self._buf(prefix + "counts", (5,), torch.int64))
+        return bufs, self._outputs(*bufs)
+
+    def _result(self, bufs, o, p, ship_pos, ctx):
+        """the BitsResult of a pass over the buffers `bufs` with the descriptor o; a pass that computes positions only for its records hands
+        out a descriptor without them (nothing ships them) and keeps the full one for the records"""
+        if ship_pos or bufs[5] is None:
+            return BitsResult(*bufs, p, ctx, pipe=self, outputs=o)
+        o_ship = _lib.Outputs()
+        C.memmove(C.byref(o_ship), C.byref(o), C.sizeof(_lib.Outputs))
+        o_ship.pos, o_ship.cap_pos = None, 0
+        r = BitsResult(*bufs[:5], None, *bufs[6:], p, ctx, pipe=self, outputs=o_ship)
+        r._outputs_pos, r._pos_dev = o, bufs[5]
+        return r
+
+    def _center_blocks(self, prefix, slot):
+        """auto_center passes: (the center's result block on the device, its pinned mirror, the histogram capacity).  On a pipelined context
+        the slot's qad is read by its previous pass's tail (center chain, segmentation): a pass that REUSES a slot whose tail may still be
+        pending makes its demodulation wait for the tail; passes on slots of their own overlap"""
+        hist_cap = int(_lib.load().urhgpu_center_hist_cap(self.ctx.handle))
+        nbytes = C.sizeof(_lib.CenterResult) + 4 * hist_cap
+        d_res = self._buf(prefix + "center", (nbytes,), self.torch.uint8)
+        block = self._pinned_block(("center", slot), nbytes)
+        if self.tail_stream is not None:
+            if slot in self._auto_slots:
+                self.ctx.join()
+                self._auto_slots.clear()
+            self._auto_slots.add(slot)
+        return d_res, block, hist_cap
+
     def capacities(self, n: int, p: DemodParams, cap_rows=None):
         sps = max(int(p.samples_per_symbol), 1)
         if cap_rows is None:
@@ -965,10 +786,7 @@ class DevicePipeline:
         cap = int(o.cap_msg) if pt < 0 else min(int(o.cap_msg), (n // (pt * sps) if pt > 0 else 0) + 2)
         nbytes = max(cap, 1) * C.sizeof(_lib.MsgRecord)
         d_rec = self._buf(f"s{slot}:records", (nbytes,), torch.uint8)
-        block = self._pinned.get(("records", slot))
-        if block is None or block.numel() < nbytes:
-            block = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
-            self._pinned[("records", slot)] = block
+        block = self._pinned_block(("records", slot), nbytes)
         _lib.check(_lib.load().urhgpu_msg_records_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, C.byref(cp), C.byref(o), int(divisor),
                                                       C.c_void_p(d_rec.data_ptr()), cap, C.c_void_p(block.data_ptr())))
         return block, cap
@@ -1006,7 +824,7 @@ class DevicePipeline:
                 raise ValueError("message_length_divisor must be at least 1")
             if iq.dtype == self.torch.complex64:
                 iq = self.torch.view_as_real(iq)
-            res._rec = self._queue_records(iq, p, res._outputs_pos, message_length_divisor, slot) + (iq, int(message_length_divisor), slot)
+            res.queue_records(iq, message_length_divisor, slot)
         return res
 
     def _iq_to_bits(self, iq, p, want_qad, cap_rows, slot, auto_center, center_max_size, auto_noise, compute_pos) -> BitsResult:
@@ -1023,94 +841,33 @@ class DevicePipeline:
         ship_pos = bool(p.write_bit_sample_pos)
         if compute_pos:
             cp.write_bit_sample_pos = 1
-        cap_rows, cap_bits, cap_msg, cap_pos = self.capacities(n, p, cap_rows)
         sfx = f"s{slot}:" if slot else ""
-        qad = self._buf(sfx + "qad", (n,), torch.float32) if want_qad else None
-        rows = self._buf(sfx + "rows", (cap_rows, 2), torch.int64)
-        bits = self._buf(sfx + "bits", (cap_bits,), torch.uint8)
-        msg_off = self._buf(sfx + "msg_off", (cap_msg + 1,), torch.int64)
-        pauses = self._buf(sfx + "pauses", (cap_msg,), torch.int64)
-        pos_off = self._buf(sfx + "pos_off", (cap_msg + 1,), torch.int64)
-        pos = self._buf(sfx + "pos", (cap_pos,), torch.int64) if (ship_pos or compute_pos) else None
-        counts = self._buf(sfx + "counts", (5,), torch.int64)
-
-        def result():
-            """the pass's BitsResult; a pass that computes positions only for its records hands out a descriptor without them (nothing ships them)"""
-            if ship_pos or pos is None:
-                return BitsResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, self.ctx, pipe=self, outputs=o)
-            o_ship = _lib.Outputs()
-            C.memmove(C.byref(o_ship), C.byref(o), C.sizeof(_lib.Outputs))
-            o_ship.pos, o_ship.cap_pos = None, 0
-            r = BitsResult(qad, rows, bits, msg_off, pauses, None, pos_off, counts, p, self.ctx, pipe=self, outputs=o_ship)
-            r._outputs_pos, r._pos_dev = o, pos
-            return r
-        o = _lib.Outputs()
-        o.qad = qad.data_ptr() if qad is not None else None
-        o.rows = rows.data_ptr(); o.cap_rows = cap_rows
-        o.bits = bits.data_ptr(); o.cap_bits = cap_bits
-        o.msg_off = msg_off.data_ptr(); o.pauses = pauses.data_ptr(); o.cap_msg = cap_msg
-        o.pos = pos.data_ptr() if pos is not None else None
-        o.cap_pos = cap_pos if pos is not None else 0
-        o.pos_off = pos_off.data_ptr()
-        o.counts = counts.data_ptr()
+        bufs, o = self._output_set(sfx, n if want_qad else None, self.capacities(n, p, cap_rows), ship_pos or compute_pos)
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        lib, args = _lib.load(), (self.ctx.handle, C.c_void_p(iq.data_ptr()), n, C.byref(cp))
+        max_size = -1 if center_max_size is None else int(center_max_size)
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        nblock, (d_cres, cblock, hist_cap) = None, (None, None, 0)
         if auto_noise:
-            lib = _lib.load()
             nres = self._buf(sfx + "noise", (C.sizeof(_lib.NoiseResult),), torch.uint8)
-            nblock = self._pinned.get(("noise", slot))
-            if nblock is None:
-                nblock = torch.zeros(C.sizeof(_lib.NoiseResult), dtype=torch.uint8).pin_memory()
-                self._pinned[("noise", slot)] = nblock
-            d_cres, cblock, hist_cap = None, None, 0
-            if auto_center:
-                hist_cap = int(lib.urhgpu_center_hist_cap(self.ctx.handle))
-                nbytes = C.sizeof(_lib.CenterResult) + 4 * hist_cap
-                d_cres = self._buf(sfx + "center", (nbytes,), torch.uint8)
-                cblock = self._pinned.get(("center", slot))
-                if cblock is None or cblock.numel() < nbytes:
-                    cblock = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
-                    self._pinned[("center", slot)] = cblock
-            if self.tail_stream is not None and auto_center:
-                # (as below) a pass that REUSES a slot whose tail may still be pending -- the center chain reads the slot's qad -- waits for that
-                # tail; passes on slots of their own overlap
-                if slot in self._auto_slots:
-                    self.ctx.join()
-                    self._auto_slots.clear()
-                self._auto_slots.add(slot)
-            _lib.check(lib.urhgpu_iq_to_bits_auto_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, C.byref(cp), 1, 1 if auto_center else 0,
-                                                      -1 if center_max_size is None else int(center_max_size), C.byref(o),
-                                                      C.c_void_p(nres.data_ptr()), C.c_void_p(nblock.data_ptr()),
-                                                      C.c_void_p(d_cres.data_ptr()) if auto_center else None,
-                                                      C.c_void_p(cblock.data_ptr()) if auto_center else None, hist_cap))
-            res = result()
-            res._auto_noise = (nblock, slot)
-            if auto_center:
-                res._auto = (cblock, center_max_size, slot)
-            return res
+            nblock = self._pinned_block(("noise", slot), C.sizeof(_lib.NoiseResult))
         if auto_center:
-            lib = _lib.load()
-            hist_cap = int(lib.urhgpu_center_hist_cap(self.ctx.handle))
-            nbytes = C.sizeof(_lib.CenterResult) + 4 * hist_cap
-            d_res = self._buf(sfx + "center", (nbytes,), torch.uint8)
-            block = self._pinned.get(("center", slot))
-            if block is None or block.numel() < nbytes:
-                block = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
-                self._pinned[("center", slot)] = block
-            if self.tail_stream is not None:
-                # the slot's qad is read by its previous pass's tail (center chain, segmentation): a pass that REUSES a slot whose tail may still be
-                # pending makes its demodulation wait for the tail; passes on slots of their own overlap
-                if slot in self._auto_slots:
-                    self.ctx.join()
-                    self._auto_slots.clear()
-                self._auto_slots.add(slot)
-            _lib.check(lib.urhgpu_iq_to_bits_auto_center_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, C.byref(cp),
-                                                             -1 if center_max_size is None else int(center_max_size), C.byref(o),
-                                                             C.c_void_p(d_res.data_ptr()), C.c_void_p(block.data_ptr()), hist_cap))
-            res = result()
-            res._auto = (block, center_max_size, slot)
-            return res
-        _lib.check(_lib.load().urhgpu_iq_to_bits_dev(self.ctx.handle, C.c_void_p(iq.data_ptr()), n, C.byref(cp), C.byref(o)))
-        return result()
+            d_cres, cblock, hist_cap = self._center_blocks(sfx, slot)
+        if auto_noise:
+            _lib.check(lib.urhgpu_iq_to_bits_auto_dev(*args, 1, 1 if auto_center else 0, max_size, C.byref(o), ptr(nres), ptr(nblock), ptr(d_cres),
+                                                      ptr(cblock), hist_cap))
+        elif auto_center:
+            _lib.check(lib.urhgpu_iq_to_bits_auto_center_dev(*args, max_size, C.byref(o), ptr(d_cres), ptr(cblock), hist_cap))
+        else:
+            _lib.check(lib.urhgpu_iq_to_bits_dev(*args, C.byref(o)))
+        res = self._result(bufs, o, p, ship_pos, self.ctx)
+        if nblock is not None:
+            res._auto_noise = (nblock, slot)
+        if cblock is not None:
+            res._auto = (cblock, center_max_size, slot)
+        return res
 
     def iq_to_bits_batch(self, captures, p: DemodParams, want_qad=False, cap_rows=None, long_from=None, **options):
         """Many captures in one pass (urh_amd/batch.py; include/urhgpu.h "a batch of captures"): one upload, three launches whatever the
@@ -1159,43 +916,23 @@ class DevicePipeline:
             cp.write_bit_sample_pos = 1
         if cap_rows is None:
             cap_rows = n // (p.tolerance + 1) + 2            # exact bound: one pass, no retry (the table is sliced from a resident signal)
-        cap_rows, cap_bits, cap_msg, cap_pos = self.capacities(n, p, cap_rows)
         sfx = f"q{slot}:"
-        rows = self._buf(sfx + "rows", (cap_rows, 2), torch.int64)
+        bufs, o = self._output_set(sfx, None, self.capacities(n, p, cap_rows), ship_pos or compute_pos)
+        _, rows, _, msg_off, _, _, pos_off, counts = bufs
+        bufs = (qad,) + bufs[1:]                             # (the result's demodulated signal is the input; the descriptor names none)
         n_rows = self._buf(sfx + "n_rows", (1,), torch.int64)
-        bits = self._buf(sfx + "bits", (cap_bits,), torch.uint8)
-        msg_off = self._buf(sfx + "msg_off", (cap_msg + 1,), torch.int64)
-        pauses = self._buf(sfx + "pauses", (cap_msg,), torch.int64)
-        pos_off = self._buf(sfx + "pos_off", (cap_msg + 1,), torch.int64)
-        pos = self._buf(sfx + "pos", (cap_pos,), torch.int64) if (ship_pos or compute_pos) else None
-        counts = self._buf(sfx + "counts", (5,), torch.int64)
         lib = _lib.load()
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
         if n == 0:
             counts.zero_()
             msg_off[:1] = 0
             pos_off[:1] = 0
-            return BitsResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, None)
+            return BitsResult(*bufs, p, None)
         _lib.check(lib.urhgpu_grab_pulse_lens_dev(self.ctx.handle, C.c_void_p(qad.data_ptr()), n, C.byref(cp), C.c_void_p(rows.data_ptr()), cap_rows,
                                                   C.c_void_p(n_rows.data_ptr())))
-        o = _lib.Outputs()
-        o.qad = None
-        o.rows = rows.data_ptr(); o.cap_rows = cap_rows
-        o.bits = bits.data_ptr(); o.cap_bits = cap_bits
-        o.msg_off = msg_off.data_ptr(); o.pauses = pauses.data_ptr(); o.cap_msg = cap_msg
-        o.pos = pos.data_ptr() if pos is not None else None
-        o.cap_pos = cap_pos if pos is not None else 0
-        o.pos_off = pos_off.data_ptr(); o.counts = counts.data_ptr()
         _lib.check(lib.urhgpu_ppseq_to_bits_dev(self.ctx.handle, C.c_void_p(rows.data_ptr()), C.c_void_p(n_rows.data_ptr()), cap_rows, C.byref(cp),
                                                 C.byref(o)))
-        if ship_pos or pos is None:
-            return BitsResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, None, pipe=self, outputs=o)
-        o_ship = _lib.Outputs()
-        C.memmove(C.byref(o_ship), C.byref(o), C.sizeof(_lib.Outputs))
-        o_ship.pos, o_ship.cap_pos = None, 0
-        r = BitsResult(qad, rows, bits, msg_off, pauses, None, pos_off, counts, p, None, pipe=self, outputs=o_ship)
-        r._outputs_pos, r._pos_dev = o, pos
-        return r
+        return self._result(bufs, o, p, ship_pos, None)
 
     def afp_demod(self, iq, p: DemodParams):
         torch = self.torch

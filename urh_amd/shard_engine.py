@@ -6,35 +6,14 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .pipeline import DevicePipeline, _torch_dtype
+from .host_bits import HostBits
+from .pipeline import DevicePipeline, PassResult, _torch_dtype
 
 
-class ShardResult:
+class ShardResult(PassResult):
     """This rank's piece of a sharded result (device tensors) + host views for `sharding.stitch`."""
 
-    def __init__(self, qad, rows, bits, msg_off, pauses, pos, pos_off, counts, params, ctx=None):
-        self.qad, self.rows_buf, self.bits_buf = qad, rows, bits
-        self.msg_off_buf, self.pauses_buf, self.pos_buf, self.pos_off_buf = msg_off, pauses, pos, pos_off
-        self.counts, self.params = counts, params
-        self._host_counts = None
-        self._ctx = ctx
-        self._host = None
-
-    def host_counts(self):
-        if self._host_counts is None:
-            if self._ctx is not None:
-                self._ctx.join()
-            c = self.counts.cpu().numpy()
-            self._host_counts = tuple(int(x) for x in c[:4])
-            self._rows_needed = int(c[4])
-        return self._host_counts
-
-    def check_capacity(self):
-        n_rows, n_msg, n_bits, n_pos = self.host_counts()
-        if self._rows_needed > self.rows_buf.shape[0] or n_msg > self.pauses_buf.shape[0] or n_bits > self.bits_buf.shape[0] \
-                or (self.pos_buf is not None and n_pos > self.pos_buf.shape[0]):
-            raise _lib.UrhGpuError(_lib.ERR_CAPACITY, f"output capacity too small: rows={self._rows_needed} msgs={n_msg} "
-                                                      f"bits={n_bits} pos={n_pos}")
+    _host = None                                            # host results: (engine, blob slot, bytes copied, pass) until looked at, then the HostBits
 
     def piece(self):
         """dict(rows, bits, msg_end, pauses, pos, pos_end) of numpy arrays (see sharding.stitch)."""
@@ -52,7 +31,6 @@ class ShardResult:
         """This rank's piece ON THE HOST from the compact blob (GpuShardEngine(host_results=True): packed at the end of the pass, copied
         by the copy stream while later passes run): a pipeline.HostBits whose views are valid until three passes later.  Rows, bits,
         pauses and offsets are the rank's LOCAL piece, as in `piece()`."""
-        from .pipeline import HostBits
         if self._host is None:
             raise ValueError("the engine was not asked for host results (host_results=True)")
         if not isinstance(self._host, HostBits):
@@ -126,7 +104,6 @@ class GpuShardEngine(DevicePipeline):
         return n
 
     def _finish_host_copy(self, k, copied, params, qad, pass_no):
-        from .pipeline import HostBits
         if self._slot_pass[k] != pass_no:
             raise RuntimeError(f"ShardResult.host(): the blob slot of pass {pass_no} has been reused by pass {self._slot_pass[k]} (three blob slots "
                                f"rotate: look at a result before three later passes have been issued) or the slots were reallocated")
@@ -138,14 +115,10 @@ class GpuShardEngine(DevicePipeline):
             with self.torch.cuda.stream(self._copy_stream):
                 hblob[copied:total].copy_(dblob[copied:total], non_blocking=False)
         self._predicted = total + total // 8 + 65536
-        h = self._host_bits(HostBits, hblob, params, qad)
+        h = HostBits.from_blob(hblob.data_ptr(), params, n_samples=int(qad.shape[0]) if qad is not None else 0,
+                               d_qad=qad.data_ptr() if qad is not None else 0)
         h.sharded_piece = True
         return h
-
-    @staticmethod
-    def _host_bits(HostBits, hblob, params, qad):
-        return HostBits.from_blob(hblob.data_ptr(), params, n_samples=int(qad.shape[0]) if qad is not None else 0,
-                                  d_qad=qad.data_ptr() if qad is not None else 0)
 
     # ---- plumbing shared by the phases ----
     def _rows_view(self, t, what=None, own=True):
@@ -167,20 +140,6 @@ class GpuShardEngine(DevicePipeline):
             raise ValueError(f"{what}: the shard lies on {t.device}, the engine runs on {self.device}")
         if not t.is_contiguous():
             raise ValueError(f"{what}: the shard must be contiguous")
-
-    @staticmethod
-    def _outputs(qad, rows, bits, msg_off, pauses, pos, pos_off, counts):
-        """the C descriptor of a result's buffers, the capacities being their lengths"""
-        o = _lib.Outputs()
-        o.qad = qad.data_ptr() if qad is not None else None
-        o.rows = rows.data_ptr(); o.cap_rows = int(rows.shape[0])
-        o.bits = bits.data_ptr(); o.cap_bits = int(bits.shape[0])
-        o.msg_off = msg_off.data_ptr(); o.pauses = pauses.data_ptr(); o.cap_msg = int(pauses.shape[0])
-        o.pos = pos.data_ptr() if pos is not None else None
-        o.cap_pos = int(pos.shape[0]) if pos is not None else 0
-        o.pos_off = pos_off.data_ptr()
-        o.counts = counts.data_ptr()
-        return o
 
     def _call(self, fn_name, *args, set_stream=True):
         """one call into the library on this engine's context, its return code checked.  set_stream: the context works on the current torch
@@ -231,15 +190,8 @@ class GpuShardEngine(DevicePipeline):
         extra = (max(int(n_total) - n, 0) // max(int(p.samples_per_symbol), 1) + 1) * int(p.bits_per_symbol)
         cap_bits += extra
         cap_pos += extra
-        qad = self._buf("qad", (n,), torch.float32) if want_qad else None
-        rows = self._buf("rows", (cap_rows, 2), torch.int64)
-        bits = self._buf("bits", (cap_bits,), torch.uint8)
-        msg_off = self._buf("msg_off", (cap_msg + 1,), torch.int64)
-        pauses = self._buf("pauses", (cap_msg,), torch.int64)
-        pos_off = self._buf("pos_off", (cap_msg + 1,), torch.int64)
-        pos = self._buf("pos", (cap_pos,), torch.int64) if p.write_bit_sample_pos else None
-        counts = self._buf("counts", (5,), torch.int64)
-        o = self._outputs(qad, rows, bits, msg_off, pauses, pos, pos_off, counts)
+        bufs, o = self._output_set("", n if want_qad else None, (cap_rows, cap_bits, cap_msg, cap_pos), p.write_bit_sample_pos)
+        pos = bufs[5]
         self._hslot = None
         if self.host_results:
             k, cap = self._host_slot(cap_rows, cap_bits, cap_msg, cap_pos if pos is not None else 0, pos is not None)
@@ -248,7 +200,7 @@ class GpuShardEngine(DevicePipeline):
             (self.tail_stream if self.tail_stream is not None else torch.cuda.current_stream(self.device)).wait_event(done)
             o.blob = dblob.data_ptr(); o.cap_blob = cap
             self._hslot = k
-        self._res = ShardResult(qad, rows, bits, msg_off, pauses, pos, pos_off, counts, p, self.ctx)
+        self._res = ShardResult(*bufs, p, self.ctx)
         self._ask = p.modulation_type == "ASK"
         self._keep = (iq,)                                     # keep the inputs alive until the pass is over
         # here and not at every phase: the phases behind the hot launch run under tail_context, where the current stream is the tail stream
@@ -538,10 +490,7 @@ class GpuShardEngine(DevicePipeline):
         o, cp = self._records_outputs(res), p.to_c(npdt)
         cap = max(int(o.cap_msg), 1)
         d_rec = self._buf("shard_records", (cap * RECORD_DTYPE.itemsize,), torch.uint8)
-        block = self._pinned.get(("records", "shard"))
-        if block is None or block.numel() < cap * RECORD_DTYPE.itemsize:
-            block = torch.zeros(cap * RECORD_DTYPE.itemsize, dtype=torch.uint8).pin_memory()
-            self._pinned[("records", "shard")] = block
+        block = self._pinned_block(("records", "shard"), cap * RECORD_DTYPE.itemsize)
         first = np.ascontiguousarray(first, dtype=np.int64)
         if window is not None:
             window = window.contiguous()

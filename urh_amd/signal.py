@@ -536,7 +536,7 @@ class Signal:
             # one slicing pass over the cached demodulated signal with the records queued behind it (the capture is resident), one hand-out;
             # kept until a parameter or the samples change: a repeated call does no device work
             res = self.pipe.qad_to_bits(q, p, slot=7)
-            res._rec = self.pipe._queue_records(self._iq, p, res._outputs_pos, divisor, 7) + (self._iq, divisor, 7)
+            res.queue_records(self._iq, divisor, 7)
             rec = res.records.copy()
             res.check_capacity()
             self._records, self._records_key = (res._flat(True), rec), key
