@@ -1144,6 +1144,38 @@ int urhgpu_batch_fetch(urhgpu_ctx *ctx, const int64_t *d_dir, int64_t k, const v
                        int64_t *total_bytes);
 int urhgpu_batch_launches(urhgpu_ctx *ctx, int64_t *out2);
 
+/* ---- a batch of captures: automatic noise threshold per capture, on the device ----------------------------------------------------
+ * The reference opens every file of a recording session with noise_threshold = detect_noise_level(magnitudes) of THAT capture
+ * (Signal.py:97-103, AutoInterpretation.py:60-91), and the captures of a session differ in gain by tens of dB: no single threshold
+ * decodes them.  Here the K noise floors of a batch are decided by ONE launch and the batch's walk gates each capture with its own.
+ *   urhgpu_batch_noise_dev            d_iq, total, d_start, d_plan, k, p as for urhgpu_iq_to_bits_batch_dev (of the plan only the launch
+ *            order is followed; no work buffer is needed).  One launch, asynchronous on the context's stream, the caller owns all memory:
+ *            a workgroup per capture takes the per-chunk (sum, max) of the magnitudes -- chunks of max(1, n / 100) samples counted from
+ *            the END of that capture, at most 199; the sum in numpy's float64 pairwise order, so that sum / chunk IS np.mean(chunk) bit
+ *            for bit; no load leaves [start[c], start[c + 1]) -- and decides with the body of the single-capture chain (k_noise_decide).
+ *            d_noise: device urhgpu_noise_result[k], 8-byte aligned, block c = capture c's.  Flags per capture:
+ *              flag 1  noise = detect_noise_level's value, also the 0 it returns for n <= 3, close means, a NaN mean, an all-zero capture;
+ *                      and a capture whose start or end the batch refuses (truncated bit 3 above): nothing is read, noise = 0
+ *              flag 2  noise is the value, but it is not below Signal.max_magnitude of the sample type: the reference demodulates nothing
+ *                      and slices zeros(2) (Signal.py:474-484)
+ *              flag 0  the reference raises (math.ceil of a NaN: ValueError, of an infinity: OverflowError); noise holds that value
+ *            With flag 0 or 2 the block's noise_f32 / noise_sqrd are those of p->noise_threshold (as in a pass: "use_cfg").
+ *   urhgpu_iq_to_bits_batch_auto_dev  urhgpu_iq_to_bits_batch_dev's arguments plus d_noise: FOUR launches whatever k and the lengths are,
+ *            k = 0 included -- noise, bits, scan, pack.  The wavefront of capture c loads noise_sqrd and flag from d_noise[c] (uniform
+ *            loads).  Flag 1: every result is that of urhgpu_iq_to_bits_batch_dev with noise_threshold = (float)noise.  Flag 2: the
+ *            capture is walked as TWO samples, settled on the device -- two zeros are demodulated (only the first two entries of its slice
+ *            of d_qad are written) and sliced; the caller reports n_samples = 2.  Flag 0: walked with p->noise_threshold, so that the
+ *            pass stays well defined; the caller raises instead of handing the result out.
+ *   urhgpu_batch_noise_fetch          one copy of 64 k bytes into h_noise (pinned host memory), synchronous.  With urhgpu_batch_fetch: the
+ *            directory, the blob and the K result blocks in THREE copies whatever k >= 1 is.
+ * urhgpu_batch_launches counts these launches and copies too: 4 per automatic pass, 1 per urhgpu_batch_noise_dev, 1 per noise fetch. */
+int urhgpu_batch_noise_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k,
+                           const urhgpu_params *p, urhgpu_noise_result *d_noise);
+int urhgpu_iq_to_bits_batch_auto_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k,
+                                     const urhgpu_params *p, float *d_qad, void *d_work, int64_t work_bytes, int64_t *d_counts, int64_t *d_dir,
+                                     void *d_blob, int64_t cap_blob, urhgpu_noise_result *d_noise);
+int urhgpu_batch_noise_fetch(urhgpu_ctx *ctx, const urhgpu_noise_result *d_noise, int64_t k, urhgpu_noise_result *h_noise);
+
 #ifdef __cplusplus
 }
 #endif

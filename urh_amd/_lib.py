@@ -235,6 +235,9 @@ PROTOTYPES = {
     "urhgpu_iq_to_bits_batch_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _vp, _vp, _i64, _vp, _vp, _vp, _i64]),
     "urhgpu_batch_fetch": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
     "urhgpu_batch_launches": (_i, [_vp, C.POINTER(_i64)]),
+    "urhgpu_batch_noise_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _vp]),
+    "urhgpu_iq_to_bits_batch_auto_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "urhgpu_batch_noise_fetch": (_i, [_vp, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -19,6 +19,7 @@
 #include "common.hpp"
 #include "launchers.hpp"
 #include "magnitude.hpp"
+#include "noise_decide.hpp"
 
 namespace urh {
 
@@ -677,42 +678,7 @@ __global__ __launch_bounds__(256) void k_noise_decide(const double *sum, const d
     if (t < n_chunks) { s_mean[t] = (float)(sum[t] / (double)chunk); s_max[t] = mx[t]; }
     __syncthreads();
     if (t != 0) return;
-    urhgpu_noise_result r;
-    r.noise = 0.0; r.flag = 1; r.chunk = chunk; r.n_chunks = n_chunks; r.n_candidates = 0; r.min_mean = 0.0; r.max_mean = 0.0;
-    if (n_chunks > 0) {
-        float mn = s_mean[0], mxm = s_mean[0];
-        bool nan = mn != mn;
-        for (int k = 1; k < n_chunks; ++k) {
-            const float e = s_mean[k];
-            nan = nan || (e != e);
-            if (e > mxm) mxm = e;
-            if (e < mn) mn = e;
-        }
-        const double minimum = (double)mn, maximum = (double)mxm;
-        r.min_mean = minimum; r.max_mean = maximum;
-        if (!nan && !(maximum == 0.0 || minimum / maximum > 0.9)) {
-            const float lim = 1.1f * mn;
-            double result = 0.0;
-            bool res_nan = false;
-            int64_t cand = 0;
-            for (int k = 0; k < n_chunks; ++k) {
-                if (!(s_mean[k] <= lim)) continue;
-                const double m = s_max[k];
-                if (m != m) res_nan = true;
-                if (cand == 0 || m > result) result = m;
-                ++cand;
-            }
-            r.n_candidates = cand;
-            if (cand > 0) {
-                if (res_nan) result = __builtin_nan("");
-                if (result != result || result == __builtin_inf() || result == -__builtin_inf()) { r.noise = result; r.flag = 0; }
-                else r.noise = __builtin_ceil(result * 10000.0) / 10000.0;
-            }
-        }
-    }
-    if (r.flag == 1 && !(r.noise < max_mag)) r.flag = 2;
-    r.noise_f32 = (use_cfg && r.flag != 1) ? cfg_noise : (float)r.noise;
-    r.noise_sqrd = r.noise_f32 * r.noise_f32;
+    const urhgpu_noise_result r = noise_decide(s_mean, s_max, chunk, n_chunks, max_mag, cfg_noise, use_cfg);      // noise_decide.hpp: shared with k_batch_noise
     if (d_res) *d_res = r;
     if (h_res) *h_res = r;
 }

@@ -8,13 +8,18 @@
 
 #include "../../include/urhgpu.h"
 
+// the correctly rounded fp32 square root; a translation unit may define its own form first (demod_prims.hpp has the same default)
+#ifndef URH_FSQRT
+#define URH_FSQRT(x) __builtin_sqrtf(x)
+#endif
+
 namespace urh {
 
 template <int DT> struct MagLoad;
 template <> struct MagLoad<URHGPU_DT_F32> {
     static __device__ __forceinline__ double mag(const void *p, int64_t i) {
         const float2 v = ((const float2 *)p)[i];
-        return (double)__builtin_sqrtf(v.x * v.x + v.y * v.y);
+        return (double)URH_FSQRT(v.x * v.x + v.y * v.y);
     }
 };
 template <class T2> __device__ __forceinline__ double int_mag(int re, int im) {

@@ -882,9 +882,31 @@ class DevicePipeline:
         the result; default batch.LONG_FROM_DEFAULT, the measured crossover.
         Returns a batch.BatchBits: a sequence of HostBits, each equal to what iq_to_bits gives for that capture alone; .qad(k) (want_qad)
         is capture k's slice of the demodulated signal on the device, .retry(k) runs a truncated capture again with the rows it needs.
-        ASK and FSK; PSK, auto_center, auto_noise, msg_records and dc_correction are not options of a batch (ValueError says what to call)."""
+        ASK and FSK; PSK, auto_center, auto_noise, msg_records and dc_correction are not options of a batch (ValueError says what to call:
+        for a noise threshold per capture, iq_to_bits_batch_auto)."""
         from .batch import iq_to_bits_batch
         return iq_to_bits_batch(self, captures, p, want_qad, cap_rows, long_from, **options)
+
+    def iq_to_bits_batch_auto(self, captures, p: DemodParams, auto_noise=True, want_qad=False, cap_rows=None, long_from=None, **options):
+        """iq_to_bits_batch with the noise threshold of EVERY capture detected on the device (AutoInterpretation.detect_noise_level, the
+        reference's default_noise_threshold = "automatic" for each file it opens) and each capture gated with its own: four launches and
+        three read-backs whatever the number of captures (include/urhgpu.h "a batch of captures: automatic noise threshold per capture").
+        captures, want_qad, cap_rows, long_from: as for iq_to_bits_batch; a capture of long_from samples or more goes through
+        iq_to_bits(..., auto_noise=True).  auto_noise=False is iq_to_bits_batch.  p.noise_threshold is not used by a capture whose
+        detection succeeds.
+        Returns a batch.BatchBits that also carries .noise (detect_noise_level's value per capture, Python floats) and .noise_flags
+        (urhgpu_noise_result's flag per capture).  Flag 2 -- the value is not below the sample type's max_magnitude --: the capture's
+        HostBits is the reference's slicing of zeros(2), n_samples = 2.  Flag 0 -- the reference raises for that capture --: result[k],
+        iteration at k and .check() raise the same exception (ValueError for a NaN, OverflowError for an infinity); every other capture is
+        handed out.  .retry(k) runs a truncated capture again, alone, through this entry point: it detects the same threshold.
+        ASK and FSK; PSK, auto_center, msg_records and dc_correction are not options of a batch (ValueError says what to call)."""
+        from .batch import iq_to_bits_batch_auto
+        return iq_to_bits_batch_auto(self, captures, p, auto_noise, want_qad, cap_rows, long_from, **options)
+
+    def detect_noise_levels(self, captures):
+        """AutoInterpretation.detect_noise_level of every capture of a batch in ONE launch and one read (batch.detect_noise_levels)"""
+        from .batch import detect_noise_levels
+        return detect_noise_levels(self, captures)
 
     def iq_to_bits_checked(self, iq, p: DemodParams, want_qad=True, msg_records=False, message_length_divisor=1) -> BitsResult:
         """iq_to_bits with the output capacities verified (one 40-byte read-back) and, if the default capacities were
