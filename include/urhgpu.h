@@ -1102,6 +1102,9 @@ int urhgpu_shard_msg_records_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_lo
  * :392-495, ProtocolAnalyzer.py:323-414), one workgroup takes the prefix of the result sizes, one wavefront per capture packs its
  * results.  Every capture's results are those of urhgpu_iq_to_bits_dev for that capture alone, bit for bit.  The counterpart of
  * urhgpu_modulate_dev's batch of messages.  Long captures still belong to passes and streams: a wavefront walks its capture serially.
+ * These three calls gate every capture with p->noise_threshold and slice it with p->center; the estimators that give every capture its own
+ * are the two sections below: a noise threshold per capture (urhgpu_iq_to_bits_batch_auto_dev), a center per capture
+ * (urhgpu_iq_to_bits_batch_center_dev).
  *   Input    d_iq: (total, 2) interleaved samples of p->dtype (any of the five), 16-byte aligned; d_start: device int64[k + 1], the first
  *            sample of each capture (a capture may start at any sample; lengths 0 .. 2^31 - 1); one urhgpu_params for all.  ASK and FSK;
  *            PSK and URHGPU_MOD_OTHER: URHGPU_ERR_UNSUPPORTED.  Any tolerance (uint16), bits_per_symbol 1 .. 7.
@@ -1175,6 +1178,61 @@ int urhgpu_iq_to_bits_batch_auto_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t 
                                      const urhgpu_params *p, float *d_qad, void *d_work, int64_t work_bytes, int64_t *d_counts, int64_t *d_dir,
                                      void *d_blob, int64_t cap_blob, urhgpu_noise_result *d_noise);
 int urhgpu_batch_noise_fetch(urhgpu_ctx *ctx, const urhgpu_noise_result *d_noise, int64_t k, urhgpu_noise_result *h_noise);
+
+/* ---- a batch of captures: automatic center per capture, on the device ------------------------------------------------------------
+ * The reference detects the center of every signal it demodulates (AutoInterpretation.detect_center, AutoInterpretation.py:226-277), and
+ * for ASK the center follows the received amplitude: captures that differ in gain cannot share p->center.  Here the K captures of a batch
+ * are demodulated into one buffer, ONE chain of kernels runs detect_center on the K ranges (the chain of "automatic center inside a pass"
+ * above, over many ranges: urh_amd/csrc/msg_estimators.hip), and the batch's walk slices each capture with the thresholds of its own
+ * center.  Capture c's results are those of urhgpu_iq_to_bits_auto_center_dev (with automatic noise: urhgpu_iq_to_bits_auto_dev) on that
+ * capture alone, bit for bit, the flag protocol included: WITH FLAG 0, 2 OR 3 THE CAPTURE WAS SLICED WITH p->center, and a caller that wants
+ * the reference's result for flag 2 / 3 settles the center on the host and slices those captures again (urhgpu_qad_to_bits_batch_dev with
+ * thresholds of its own: one call for all of them).  The caller owns all memory; nothing is waited for but the fetch.
+ *   urhgpu_batch_center_plan   host arithmetic, works without a GPU: *scratch_bytes the chain needs for k captures in a buffer of `total`
+ *            samples (total < 0: the sum of lengths[k]; lengths may be NULL when total is given) with a pool of max_bins bins per capture
+ *            (urhgpu_center_hist_cap), *group = captures per group -- the captures are taken in groups whose histogram pool stays within
+ *            64 MiB, as urhgpu_msg_center_stats takes its messages: max(1, 64 MiB / (4 max_bins)) --, *n_groups = ceil(k / group).
+ *   urhgpu_batch_center_dev    the chain and the publish step alone on d_qad (device float32[total]; capture c = [d_start[c], d_start[c + 1])
+ *            by the batch's rules: a refused start or end is an empty range).  max_size as for urhgpu_detect_center_dev.  d_noise: NULL, or
+ *            the batch's urhgpu_noise_result[k] -- a capture with flag 2 has the range of its two zeros.  14 launches and one fill per
+ *            GROUP, whatever k and the lengths are: the launch count is a function of ceil(k / group) alone.  Outputs:
+ *              d_thr     NULL or float32[k][order - 1], cap_thr floats: capture c's slicing thresholds -- urhgpu_get_center_thresholds'
+ *                        arithmetic on (float)center for flag 1, on p->center otherwise
+ *              d_result  urhgpu_batch_center_result[k + 1], cap_result blocks: block c = capture c's urhgpu_center_result and the offset of
+ *                        its counts in the tie pool; the trailing block's counts_off = counts reserved in the pool (its cursor)
+ *              d_tie     NULL or uint32[cap_tie], the tie pool: for flag 3 alone the histogram's n_bins counts, appended in no particular
+ *                        order.  A capture whose counts do not fit gets n_counts = 0; nothing is stored beyond cap_tie.
+ *            d_scratch: 256-byte aligned, scratch_bytes >= the plan's.  A capacity that is too small: URHGPU_ERR_CAPACITY, nothing is
+ *            launched.  Starts that overlap can ask for more tiles than the scratch holds (total / 4096 + group + 1): the captures that
+ *            do not fit get no center (flag 0).
+ *   urhgpu_qad_to_bits_batch_dev   urhgpu_iq_to_bits_batch_dev on captures that are ALREADY demodulated: the walk reads d_qad (4-byte
+ *            aligned) as it lies there, then scan and pack: three launches.  d_thr: NULL -- every capture is sliced with p->center -- or
+ *            float32[k][order - 1] in device memory.  d_noise: NULL or the batch's result blocks (flag 2: two samples are walked).
+ *   urhgpu_iq_to_bits_batch_center_dev   the whole pass: urhgpu_batch_noise_dev's launch when auto_noise is not 0, the demodulation of all
+ *            captures into d_qad (required; a workgroup per capture), the chain and the publish step per group, the qad-input walk, scan,
+ *            pack: 4 (auto_noise: 5) + 14 n_groups launches.  Arguments as for urhgpu_iq_to_bits_batch_auto_dev and urhgpu_batch_center_dev.
+ *   urhgpu_batch_center_fetch  the k + 1 result blocks into h_result, then the used part of the tie pool -- min(cursor, cap_tie) counts,
+ *            *used -- into h_tie (cap_host counts): two copies at most, one when no capture tied; synchronous.
+ * urhgpu_batch_launches counts these launches and copies too. */
+typedef struct urhgpu_batch_center_result {
+    urhgpu_center_result r;      /* n_counts: n_bins when flag == 3 and the counts fitted the tie pool, else 0 */
+    int64_t counts_off;          /* first of the n_counts counts in the tie pool; trailing block: counts reserved in the pool */
+} urhgpu_batch_center_result;
+int urhgpu_batch_center_plan(const int64_t *lengths, int64_t k, int64_t total, int64_t max_bins, int64_t *scratch_bytes, int64_t *n_groups,
+                             int64_t *group);
+int urhgpu_batch_center_dev(urhgpu_ctx *ctx, const float *d_qad, int64_t total, const int64_t *d_start, int64_t k, const urhgpu_params *p,
+                            int64_t max_size, const urhgpu_noise_result *d_noise, void *d_scratch, int64_t scratch_bytes, float *d_thr,
+                            int64_t cap_thr, void *d_result, int64_t cap_result, uint32_t *d_tie, int64_t cap_tie);
+int urhgpu_qad_to_bits_batch_dev(urhgpu_ctx *ctx, const float *d_qad, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k,
+                                 const urhgpu_params *p, const float *d_thr, int64_t cap_thr, const urhgpu_noise_result *d_noise, void *d_work,
+                                 int64_t work_bytes, int64_t *d_counts, int64_t *d_dir, void *d_blob, int64_t cap_blob);
+int urhgpu_iq_to_bits_batch_center_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k,
+                                       const urhgpu_params *p, int auto_noise, int64_t max_size, float *d_qad, void *d_work, int64_t work_bytes,
+                                       int64_t *d_counts, int64_t *d_dir, void *d_blob, int64_t cap_blob, urhgpu_noise_result *d_noise,
+                                       void *d_scratch, int64_t scratch_bytes, float *d_thr, int64_t cap_thr, void *d_result, int64_t cap_result,
+                                       uint32_t *d_tie, int64_t cap_tie);
+int urhgpu_batch_center_fetch(urhgpu_ctx *ctx, const void *d_result, int64_t k, const uint32_t *d_tie, int64_t cap_tie, void *h_result,
+                              uint32_t *h_tie, int64_t cap_host, int64_t *used);
 
 #ifdef __cplusplus
 }

@@ -58,6 +58,11 @@ class CenterResult(C.Structure):
                 ("kept", C.c_int64), ("trimmed", C.c_int64), ("n_counts", C.c_int64)]
 
 
+class BatchCenterResult(C.Structure):
+    """struct urhgpu_batch_center_result (include/urhgpu.h): a capture's urhgpu_center_result and where its counts lie in the tie pool"""
+    _fields_ = [("r", CenterResult), ("counts_off", C.c_int64)]
+
+
 class NoiseResult(C.Structure):
     """struct urhgpu_noise_result (include/urhgpu.h)"""
     _fields_ = [("noise", C.c_double), ("noise_f32", C.c_float), ("noise_sqrd", C.c_float), ("flag", C.c_int64), ("chunk", C.c_int64),
@@ -238,6 +243,12 @@ PROTOTYPES = {
     "urhgpu_batch_noise_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _vp]),
     "urhgpu_iq_to_bits_batch_auto_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "urhgpu_batch_noise_fetch": (_i, [_vp, _vp, _i64, _vp]),
+    "urhgpu_batch_center_plan": (_i, [_vp, _i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "urhgpu_batch_center_dev": (_i, [_vp, _vp, _i64, _vp, _i64, C.POINTER(Params), _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
+    "urhgpu_qad_to_bits_batch_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64]),
+    "urhgpu_iq_to_bits_batch_center_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _i, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp,
+                                                _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
+    "urhgpu_batch_center_fetch": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, C.POINTER(_i64)]),
 }
 
 _lib = None

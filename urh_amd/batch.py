@@ -11,6 +11,12 @@ DevicePipeline.iq_to_bits_batch_auto opens the captures the way the reference op
 (k_batch_noise, urh_amd/csrc/batch_auto.hip) runs AutoInterpretation.detect_noise_level on every capture, and the walk gates each capture
 with its own threshold -- four launches and three read-backs whatever the number of captures.  detect_noise_levels is that first launch
 alone.
+
+DevicePipeline.iq_to_bits_batch_center also slices every capture with its OWN center (urh_amd/csrc/batch_center.hip): the captures are
+demodulated into one buffer, one chain of kernels runs AutoInterpretation.detect_center on all of them, and the walk classifies each
+capture through the thresholds of its center.  Where the device leaves a center to numpy (more bins than its pool holds, a tie between
+the second and the third peak) the host settles it and ALL those captures are sliced again by one more call.  detect_centers is the chain
+alone, qad_to_bits_batch the walk alone.
 """
 import ctypes as C
 from dataclasses import replace
@@ -27,7 +33,8 @@ from .signal_functions import mod_code
 LONG_FROM_DEFAULT = 196_608
 
 _NOT_IN_A_BATCH = {
-    "auto_center": "a batch slices every capture with p.center: call iq_to_bits(..., auto_center=True) per capture, or a CaptureStream(auto_center=True)",
+    "auto_center": "iq_to_bits_batch slices every capture with p.center: call iq_to_bits_batch_center(captures, p, auto_noise=False), which detects a center "
+                   "per capture (or call iq_to_bits(..., auto_center=True) per capture, or a CaptureStream(auto_center=True))",
     "auto_noise": "iq_to_bits_batch gates every capture with p.noise_threshold: call iq_to_bits_batch_auto(captures, p), which detects a threshold per capture",
     "msg_records": "a batch computes no message records: call iq_to_bits(..., msg_records=True) per capture, or a CaptureStream(msg_records=True)",
     "dc_correction": "a batch does not remove the captures' means: call iq_to_bits(..., dc_correction=True) per capture, or a CaptureStream(dc_correction=True)",
@@ -85,7 +92,7 @@ class BatchBits:
     bit_sample_pos(), pos_offsets(), flat(), truncated, rows_needed, check() as for a stream's results).  Views of pinned memory of the
     pipeline: valid until its next batch; copy what has to live longer."""
 
-    def __init__(self, items, params, lengths, qads=None, rerun=None, noise=None, noise_flags=None):
+    def __init__(self, items, params, lengths, qads=None, rerun=None, noise=None, noise_flags=None, centers=None, center_flags=None):
         self._items = list(items)
         self.params = params
         self.lengths = [int(n) for n in lengths]
@@ -96,6 +103,11 @@ class BatchBits:
         # did the batch (n_samples = 2); 0 the reference raises, and so does handing that capture out (the value is the NaN / infinity)
         self.noise = None if noise is None else [float(x) for x in noise]
         self.noise_flags = None if noise_flags is None else [int(f) for f in noise_flags]
+        # iq_to_bits_batch_center: detect_center's value per capture (a Python float, or None where it gives None: the capture was sliced
+        # with p.center) and urhgpu_center_result's flag per capture AS THE DEVICE REPORTED IT -- 1 decided on the device, 0 None, 2 / 3
+        # left to the host: settled before the method returned, the capture sliced again with the settled center
+        self.centers = None if centers is None else [None if c is None else float(c) for c in centers]
+        self.center_flags = None if center_flags is None else [int(f) for f in center_flags]
 
     def __len__(self):
         return len(self._items)
@@ -169,11 +181,151 @@ _META_ALIGN = 256
 FIRST_BLOB_BUFFER_BYTES = 8 << 20
 
 
-def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq=None, device_starts=None, auto_noise=False):
+# counts the tie pool of a batch holds per capture: a demodulated capture's histogram has a few dozen bins (medians of 45 - 81 on the gain
+# sweep of tests/batch_center_cases.py), and a tied capture that does not fit goes through the single-range estimator
+TIE_POOL_COUNTS_PER_CAPTURE = 128
+
+
+def batch_center_plan(lengths, total, max_bins):
+    """urhgpu_batch_center_plan: (scratch bytes, groups, captures per group) of the center chain over K captures in a buffer of `total`
+    samples (None: the sum of the lengths) with a pool of max_bins bins per capture.  Host arithmetic: works without a GPU."""
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    out = (C.c_int64(0), C.c_int64(0), C.c_int64(0))
+    _lib.check(_lib.load().urhgpu_batch_center_plan(lengths.ctypes.data_as(C.c_void_p), int(lengths.size), -1 if total is None else int(total), int(max_bins),
+                                                    C.byref(out[0]), C.byref(out[1]), C.byref(out[2])))
+    return tuple(int(x.value) for x in out)
+
+
+def center_thresholds(p, centers):
+    """float32 [K][order - 1]: urhgpu_get_center_thresholds' arithmetic -- fp32 multiply, then add / sub -- on (float)center per capture,
+    p.center where the entry is None: what k_batch_center_publish writes on the device"""
+    order = 1 << p.bits_per_symbol
+    half = order // 2
+    c = np.array([p.center if x is None else x for x in centers], dtype=np.float64).astype(np.float32).reshape(-1, 1)
+    i = np.arange(order - 1)
+    below = (i < half).reshape(1, -1)
+    mult = np.where(i < half, half - (i + 1), i + 1 - half).astype(np.float32).reshape(1, -1)
+    step = mult * np.float32(p.center_spacing)
+    return np.ascontiguousarray(np.where(below, c - step, c + step).astype(np.float32))
+
+
+def _center_buffers(pipe, k, total, order, cap_tie, max_bins=None):
+    """the device memory of the chain's scratch and outputs: (scratch, bytes, thr, cap_thr, res, tie, cap_tie)"""
+    torch = pipe.torch
+    max_bins = int(_lib.load().urhgpu_center_hist_cap(pipe.ctx.handle)) if max_bins is None else max_bins
+    scratch_bytes, _, _ = batch_center_plan(np.zeros(k, np.int64), total, max_bins)
+    cap_tie = TIE_POOL_COUNTS_PER_CAPTURE * max(k, 1) if cap_tie is None else int(cap_tie)
+    scratch = pipe._buf("batch:center_scratch", (max(scratch_bytes, 256),), torch.uint8)
+    cap_thr = max(k * (order - 1), 1)
+    thr = pipe._buf("batch:thr", (cap_thr,), torch.float32)
+    res = pipe._buf("batch:center_res", (C.sizeof(_lib.BatchCenterResult) * (k + 1),), torch.uint8)
+    tie = pipe._buf("batch:tie", (max(cap_tie, 1),), torch.int32)
+    return scratch, scratch_bytes, thr, cap_thr, res, tie, cap_tie
+
+
+def _fetch_centers(pipe, pool, res, k, tie, cap_tie):
+    """urhgpu_batch_center_fetch: (the K result blocks, the used part of the tie pool as uint32) -- two copies at most"""
+    torch, lib = pipe.torch, _lib.load()
+    h_res = _pinned(torch, pool, "batch_center_res", C.sizeof(_lib.BatchCenterResult) * (k + 1))
+    h_tie = _pinned(torch, pool, "batch_tie", 4 * max(cap_tie, 1))
+    used = C.c_int64(0)
+    _lib.check(lib.urhgpu_batch_center_fetch(pipe.ctx.handle, C.c_void_p(res.data_ptr()), k, C.c_void_p(tie.data_ptr()), cap_tie, C.c_void_p(h_res.data_ptr()),
+                                             C.c_void_p(h_tie.data_ptr()), cap_tie, C.byref(used)))
+    blocks = (_lib.BatchCenterResult * (k + 1)).from_address(h_res.data_ptr())
+    return blocks, h_tie.numpy()[:4 * int(used.value)].view(np.uint32)
+
+
+def _settle_centers(pipe, blocks, counts, k, qad, starts, n_of, max_size, skip=()):
+    """(centers, flags as the device reported them, indices whose center the HOST settled to a value) for the K result blocks: flag 1 -- the
+    device's center; 0 -- None; 3 with the histogram in the tie pool -- pipeline.decide_center on the shipped counts; 2, and a tie that did
+    not fit the pool -- the single-range estimator on the capture's slice of qad.  skip: captures that are not handed out (noise flag 0)."""
+    from .pipeline import decide_center
+    centers, flags, settled = [None] * k, [0] * k, []
+    for i in range(k):
+        r = blocks[i].r
+        flag = flags[i] = int(r.flag)
+        if i in skip or flag == 0:
+            continue
+        if flag == 1:
+            centers[i] = float(r.center)
+            continue
+        nb = int(r.n_bins)
+        shipped = counts[int(blocks[i].counts_off):int(blocks[i].counts_off) + nb] if (flag == 3 and nb > 0 and int(r.n_counts) == nb) else None
+        s0 = int(starts[i])
+        centers[i] = decide_center(flag, r.center, shipped, r.e0, r.delta, pipe, None if shipped is not None else qad[s0:s0 + n_of(i)], max_size)
+        if centers[i] is not None:
+            settled.append(i)
+    return centers, flags, settled
+
+
+def _walk_qad(pipe, pool, qad, starts, p, thresholds, cap_rows, tag=""):
+    """urhgpu_qad_to_bits_batch_dev and its fetch on the captures qad[starts[j]:starts[j + 1]] (a device float32 tensor): the walk, scan and
+    pack -- three launches --, one upload (starts, plan and the thresholds), two copies back.  thresholds: None (p.center for all) or
+    float32 [K][order - 1].  Returns the HostBits list; their views live in pinned memory named by `tag`."""
+    torch, lib = pipe.torch, _lib.load()
+    starts = np.asarray(starts, dtype=np.int64)
+    k = len(starts) - 1
+    lengths = np.diff(starts)
+    cp = p.to_c(np.float32)
+    cp.write_bit_sample_pos = 0
+    plan, work_bytes, blob_cap = batch_plan(lengths, cp, cap_rows)
+    n_thr = 0 if thresholds is None else int(thresholds.size)
+    meta_bytes = (8 * (4 * k + 1) + _META_ALIGN - 1) // _META_ALIGN * _META_ALIGN
+    stage = _pinned(torch, pool, "batch_stage" + tag, meta_bytes + 4 * n_thr)
+    view = stage.numpy()
+    meta = view[:8 * (4 * k + 1)].view(np.int64)
+    meta[:k + 1] = starts
+    meta[k + 1:] = plan
+    if n_thr:
+        view[meta_bytes:meta_bytes + 4 * n_thr].view(np.float32)[:] = thresholds.reshape(-1)
+    pipe.ctx.set_stream(torch.cuda.current_stream(pipe.device).cuda_stream)
+    dev_in = pipe._buf("batch:walk_in" + tag, (meta_bytes + 4 * n_thr,), torch.uint8)
+    dev_in.copy_(stage[:meta_bytes + 4 * n_thr], non_blocking=True)                  # THE upload: starts, plan and thresholds in one copy
+    work = pipe._buf("batch:work", (max(work_bytes, 16),), torch.uint8)
+    counts = pipe._buf("batch:counts", (8 * max(k, 1),), torch.int64)
+    d_dir = pipe._buf("batch:dir", (k + 1,), torch.int64)
+    blob = pipe._buf("batch:blob", (max(blob_cap, 16),), torch.uint8)
+    _lib.check(lib.urhgpu_qad_to_bits_batch_dev(pipe.ctx.handle, C.c_void_p(qad.data_ptr()), int(qad.shape[0]), C.c_void_p(dev_in.data_ptr()),
+                                                C.c_void_p(dev_in.data_ptr() + 8 * (k + 1)), k, C.byref(cp),
+                                                C.c_void_p(dev_in.data_ptr() + meta_bytes) if n_thr else None, n_thr, None, C.c_void_p(work.data_ptr()),
+                                                work_bytes, C.c_void_p(counts.data_ptr()), C.c_void_p(d_dir.data_ptr()), C.c_void_p(blob.data_ptr()), blob_cap))
+    h_dir, h_blob = _fetch_blobs(pipe, pool, d_dir, k, blob, blob_cap, tag)
+    offs = h_dir.numpy()[:8 * (k + 1)].view(np.int64)
+    items = []
+    for j in range(k):
+        h = HostBits.from_blob(h_blob.data_ptr() + int(offs[j]), p, seq=j, n_samples=int(lengths[j]), d_qad=qad.data_ptr() + 4 * int(starts[j]))
+        h._keep = (h_blob, qad)
+        items.append(h)
+    return items
+
+
+def _fetch_blobs(pipe, pool, d_dir, k, blob, blob_cap, tag=""):
+    """urhgpu_batch_fetch into pinned memory of the pool: (directory, blobs)"""
+    torch, lib = pipe.torch, _lib.load()
+    h_dir = _pinned(torch, pool, "batch_dir" + tag, 8 * (k + 1))
+    h_blob = _pinned(torch, pool, "batch_blob" + tag, min(blob_cap, FIRST_BLOB_BUFFER_BYTES))
+    got = C.c_int64(0)
+
+    def fetch():
+        return lib.urhgpu_batch_fetch(pipe.ctx.handle, C.c_void_p(d_dir.data_ptr()), k, C.c_void_p(blob.data_ptr()), C.c_void_p(h_dir.data_ptr()),
+                                      C.c_void_p(h_blob.data_ptr()), int(h_blob.numel()), C.byref(got))
+    st = fetch()
+    if st == _lib.ERR_CAPACITY and int(got.value) > h_blob.numel():
+        h_blob = _pinned(torch, pool, "batch_blob" + tag, int(got.value))          # larger than the buffer so far: grow to what it needs, fetch again
+        st = fetch()
+    _lib.check(st)
+    if int(got.value) > blob_cap:
+        raise _lib.UrhGpuError(_lib.ERR_CAPACITY, "the batch's blobs did not fit the planned capacity")
+    return h_dir, h_blob
+
+
+def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq=None, device_starts=None, auto_noise=False, center=None):
     """the short captures of a batch through the three launches.  caps: numpy arrays (packed and uploaded here, one copy), or device_iq (a
     device tensor that holds them back to back) with device_starts.  auto_noise: four launches -- every capture gated with the threshold
     detected for it (urhgpu_iq_to_bits_batch_auto_dev) -- and one more read, of the K result blocks; "only": that first launch and that
-    read alone.  Returns (HostBits list, qad tensor or None, device input, starts, (noise values, flags) or None)."""
+    read alone.  center: None, or {"max_size", "cap_tie"} -- every capture sliced with its own center (urhgpu_iq_to_bits_batch_center_dev),
+    the centers the device left to the host settled and those captures sliced again by ONE more call.
+    Returns (HostBits list, qad tensor or None, device input, starts, (noise values, flags) or None, (centers, flags) or None)."""
     torch, lib = pipe.torch, _lib.load()
     k = len(lengths)
     lengths = np.asarray(lengths, dtype=np.int64)
@@ -213,8 +365,8 @@ def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq
     if auto_noise == "only":
         _lib.check(lib.urhgpu_batch_noise_dev(pipe.ctx.handle, C.c_void_p(d_iq), total, C.c_void_p(d_start), C.c_void_p(d_plan), k, C.byref(cp),
                                               C.c_void_p(d_noise.data_ptr())))
-        return None, None, (dev_in, meta_bytes, device_iq), starts, fetch_noise()
-    qad = torch.empty(max(total, 1), dtype=torch.float32, device=pipe.device) if want_qad else None
+        return None, None, (dev_in, meta_bytes, device_iq), starts, fetch_noise(), None
+    qad = torch.empty(max(total, 1), dtype=torch.float32, device=pipe.device) if (want_qad or center is not None) else None
     work = pipe._buf("batch:work", (max(work_bytes, 16),), torch.uint8)
     counts = pipe._buf("batch:counts", (8 * max(k, 1),), torch.int64)
     d_dir = pipe._buf("batch:dir", (k + 1,), torch.int64)
@@ -222,24 +374,17 @@ def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq
     args = (pipe.ctx.handle, C.c_void_p(d_iq), total, C.c_void_p(d_start), C.c_void_p(d_plan), k, C.byref(cp),
             C.c_void_p(qad.data_ptr()) if qad is not None else None, C.c_void_p(work.data_ptr()), work_bytes,
             C.c_void_p(counts.data_ptr()), C.c_void_p(d_dir.data_ptr()), C.c_void_p(blob.data_ptr()), blob_cap)
-    if auto_noise:
+    if center is not None:
+        max_size = -1 if center["max_size"] is None else int(center["max_size"])
+        scratch, scratch_bytes, thr, cap_thr, res, tie, cap_tie = _center_buffers(pipe, k, total, 1 << p.bits_per_symbol, center.get("cap_tie"))
+        _lib.check(lib.urhgpu_iq_to_bits_batch_center_dev(
+            *args[:7], 1 if auto_noise else 0, max_size, *args[7:], C.c_void_p(d_noise.data_ptr()) if auto_noise else None, C.c_void_p(scratch.data_ptr()),
+            scratch_bytes, C.c_void_p(thr.data_ptr()), cap_thr, C.c_void_p(res.data_ptr()), k + 1, C.c_void_p(tie.data_ptr()), cap_tie))
+    elif auto_noise:
         _lib.check(lib.urhgpu_iq_to_bits_batch_auto_dev(*args, C.c_void_p(d_noise.data_ptr())))
     else:
         _lib.check(lib.urhgpu_iq_to_bits_batch_dev(*args))
-    h_dir = _pinned(torch, pool, "batch_dir", 8 * (k + 1))
-    h_blob = _pinned(torch, pool, "batch_blob", min(blob_cap, FIRST_BLOB_BUFFER_BYTES))
-    got = C.c_int64(0)
-
-    def fetch():
-        return lib.urhgpu_batch_fetch(pipe.ctx.handle, C.c_void_p(d_dir.data_ptr()), k, C.c_void_p(blob.data_ptr()), C.c_void_p(h_dir.data_ptr()),
-                                      C.c_void_p(h_blob.data_ptr()), int(h_blob.numel()), C.byref(got))
-    st = fetch()
-    if st == _lib.ERR_CAPACITY and int(got.value) > h_blob.numel():
-        h_blob = _pinned(torch, pool, "batch_blob", int(got.value))             # larger than the buffer so far: grow to what it needs, fetch again
-        st = fetch()
-    _lib.check(st)
-    if int(got.value) > blob_cap:
-        raise _lib.UrhGpuError(_lib.ERR_CAPACITY, "the batch's blobs did not fit the planned capacity")
+    h_dir, h_blob = _fetch_blobs(pipe, pool, d_dir, k, blob, blob_cap)
     noise = fetch_noise() if auto_noise else None
     offs = h_dir.numpy()[:8 * (k + 1)].view(np.int64)
     items = []
@@ -249,7 +394,24 @@ def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq
                                d_qad=(qad.data_ptr() + 4 * int(starts[i])) if qad is not None else 0)
         h._keep = (h_blob, qad)
         items.append(h)
-    return items, qad, (dev_in, meta_bytes, device_iq), starts, noise
+    found = None
+    if center is not None:
+        blocks, tie_counts = _fetch_centers(pipe, pool, res, k, tie, cap_tie)
+        n_of = lambda i: items[i].n_samples                                          # noqa: E731
+        skip = {i for i in range(k) if noise is not None and noise[1][i] == 0}      # (the reference raises for these: nothing is handed out)
+        centers, flags, settled = _settle_centers(pipe, blocks, tie_counts, k, qad, starts, n_of, center["max_size"], skip)
+        if settled:
+            # ALL the captures the host has settled a center for, sliced again by ONE call: their demodulated signals gathered back to back
+            # (one torch.cat), the thresholds of their centers uploaded with the starts and the plan
+            parts = [qad[int(starts[i]):int(starts[i]) + n_of(i)] for i in settled]
+            sub = torch.cat(parts) if len(parts) > 1 else parts[0]
+            sub_starts = np.concatenate([[0], np.cumsum([n_of(i) for i in settled])]).astype(np.int64)
+            again = _walk_qad(pipe, pool, sub.contiguous(), sub_starts, p, center_thresholds(p, [centers[i] for i in settled]), cap_rows, tag=":again")
+            for i, h in zip(settled, again):
+                h.seq = i
+                items[i] = h
+        found = (centers, flags)
+    return items, qad, (dev_in, meta_bytes, device_iq), starts, noise, found
 
 
 def iq_to_bits_batch(pipe, captures, p, want_qad=False, cap_rows=None, long_from=None, _pool=None, **options):
@@ -259,7 +421,8 @@ def iq_to_bits_batch(pipe, captures, p, want_qad=False, cap_rows=None, long_from
 
 
 _NOT_IN_A_BATCH_AUTO = {
-    "auto_center": "a batch slices every capture with p.center: call iq_to_bits(..., auto_noise=True, auto_center=True) per capture, or a CaptureStream",
+    "auto_center": "iq_to_bits_batch_auto slices every capture with p.center: call iq_to_bits_batch_center(captures, p), which detects a threshold and a "
+                   "center per capture (or call iq_to_bits(..., auto_noise=True, auto_center=True) per capture, or a CaptureStream)",
     "msg_records": "a batch computes no message records: call iq_to_bits(..., auto_noise=True, msg_records=True) per capture, or a CaptureStream",
     "dc_correction": "a batch does not remove the captures' means: call iq_to_bits(..., auto_noise=True, dc_correction=True) per capture, or a CaptureStream",
 }
@@ -297,8 +460,87 @@ def detect_noise_levels(pipe, captures):
     return noise
 
 
-def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise):
-    """iq_to_bits_batch and iq_to_bits_batch_auto: the input forms, the routing by length, the result sequence"""
+_NOT_IN_A_BATCH_CENTER = {
+    "msg_records": "a batch computes no message records: call iq_to_bits(..., auto_center=True, msg_records=True) per capture, or a CaptureStream",
+    "dc_correction": "a batch does not remove the captures' means: call iq_to_bits(..., auto_center=True, dc_correction=True) per capture, or a CaptureStream",
+}
+
+
+def check_batch_center_options(p, **options):
+    """what iq_to_bits_batch_center does not do raises ValueError with a sentence (host arithmetic: no GPU needed)"""
+    for name, value in options.items():
+        if name not in _NOT_IN_A_BATCH_CENTER:
+            raise TypeError(f"iq_to_bits_batch_center() got an unexpected keyword argument '{name}'")
+        if value:
+            raise ValueError(f"{name} is not an option of a batch: {_NOT_IN_A_BATCH_CENTER[name]}")
+    check_batch_options(p)
+
+
+def iq_to_bits_batch_center(pipe, captures, p, auto_noise=True, center_max_size=None, want_qad=False, cap_rows=None, long_from=None, _pool=None,
+                            _cap_tie=None, **options):
+    """DevicePipeline.iq_to_bits_batch_center (see there)"""
+    check_batch_center_options(p, **options)
+    return _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, bool(auto_noise), center={"max_size": center_max_size, "cap_tie": _cap_tie})
+
+
+def _qad_batch_input(pipe, captures):
+    """(qad_cat, starts) as a contiguous float32 device tensor and K + 1 ascending sample indices inside it"""
+    torch = pipe.torch
+    if not (isinstance(captures, tuple) and len(captures) == 2):
+        raise ValueError("the demodulated captures are given as (qad_cat, starts)")
+    cat, starts = captures
+    starts = np.asarray(starts, dtype=np.int64)
+    if not torch.is_tensor(cat):
+        cat = torch.from_numpy(np.ascontiguousarray(cat, dtype=np.float32)).to(pipe.device)
+    if cat.dim() != 1 or cat.dtype != torch.float32:
+        raise ValueError("qad_cat must be a float32 vector")
+    if starts.ndim != 1 or starts.size < 1 or (np.diff(starts) < 0).any() or starts[0] < 0 or starts[-1] > cat.shape[0]:
+        raise ValueError("starts must be K + 1 ascending sample indices inside qad_cat")
+    return cat.contiguous(), starts
+
+
+def detect_centers(pipe, captures, max_size=None, return_flags=False, _cap_tie=None, _pool=None):
+    """DevicePipeline.detect_centers (see there)"""
+    from .pipeline import DemodParams
+    torch, lib = pipe.torch, _lib.load()
+    qad, starts = _qad_batch_input(pipe, captures)
+    k = len(starts) - 1
+    pool = pipe._pinned if _pool is None else _pool
+    p = DemodParams("FSK", 1, 0.0, 0.0, 1.0, 5, 100, 0.1, 8, False)            # (the chain reads the demodulated signal alone)
+    cp = p.to_c(np.float32)
+    pipe.ctx.set_stream(torch.cuda.current_stream(pipe.device).cuda_stream)
+    d_start = pipe._buf("batch:center_starts", (k + 1,), torch.int64)
+    d_start.copy_(torch.from_numpy(starts), non_blocking=False)
+    total = int(qad.shape[0])
+    scratch, scratch_bytes, _, _, res, tie, cap_tie = _center_buffers(pipe, k, total, 2, _cap_tie)
+    _lib.check(lib.urhgpu_batch_center_dev(pipe.ctx.handle, C.c_void_p(qad.data_ptr()), total, C.c_void_p(d_start.data_ptr()), k, C.byref(cp),
+                                           -1 if max_size is None else int(max_size), None, C.c_void_p(scratch.data_ptr()), scratch_bytes, None, 0,
+                                           C.c_void_p(res.data_ptr()), k + 1, C.c_void_p(tie.data_ptr()), cap_tie))
+    blocks, counts = _fetch_centers(pipe, pool, res, k, tie, cap_tie)
+    lengths = np.diff(starts)
+    centers, flags, _ = _settle_centers(pipe, blocks, counts, k, qad, starts, lambda i: int(lengths[i]), max_size)
+    return (centers, flags) if return_flags else centers
+
+
+def qad_to_bits_batch(pipe, captures, p, centers=None, cap_rows=None, _pool=None):
+    """DevicePipeline.qad_to_bits_batch (see there)"""
+    check_batch_options(p)
+    qad, starts = _qad_batch_input(pipe, captures)
+    k = len(starts) - 1
+    if centers is not None and len(centers) != k:
+        raise ValueError("centers holds one entry per capture (a float, or None for p.center)")
+    pool = pipe._pinned if _pool is None else _pool
+    items = _walk_qad(pipe, pool, qad, starts, p, None if centers is None else center_thresholds(p, centers), cap_rows)
+    qads = [qad[int(a):int(b)] for a, b in zip(starts[:-1], starts[1:])]
+
+    def rerun(j, rows):
+        one = qad_to_bits_batch(pipe, (qads[j].contiguous(), [0, qads[j].shape[0]]), p, None if centers is None else [centers[j]], int(rows), _pool={})
+        return one[0], qads[j]
+    return BatchBits(items, p, np.diff(starts), qads, rerun, centers=None if centers is None else list(centers))
+
+
+def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, center=None):
+    """iq_to_bits_batch, iq_to_bits_batch_auto and iq_to_bits_batch_center: the input forms, the routing by length, the result sequence"""
     torch = pipe.torch
     long_from = LONG_FROM_DEFAULT if long_from is None else int(long_from)
     pool = pipe._pinned if _pool is None else _pool
@@ -335,6 +577,7 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise):
     items = [None] * len(caps)
     qads = [None] * len(caps) if want_qad else None
     noise, flags = ([0.0] * len(caps), [1] * len(caps)) if auto_noise else (None, None)
+    centers, cflags = ([None] * len(caps), [0] * len(caps)) if center is not None else (None, None)
 
     # the short ones: one batch
     sub = [caps[i] for i in short]
@@ -346,10 +589,10 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise):
             dev_cat = torch.cat(sub) if sub else torch.empty((0, 2), dtype=caps[0].dtype if caps else torch.float32, device=pipe.device)
             dev_starts = None
         dev_cat = dev_cat.contiguous()
-        got, qad, src, starts, found = _run_batch(pipe, None, sub_len, npdt, p, want_qad, cap_rows, pool, device_iq=dev_cat, device_starts=dev_starts,
-                                                  auto_noise=auto_noise)
+        got, qad, src, starts, found, cfound = _run_batch(pipe, None, sub_len, npdt, p, want_qad, cap_rows, pool, device_iq=dev_cat, device_starts=dev_starts,
+                                                          auto_noise=auto_noise, center=center)
     else:
-        got, qad, src, starts, found = _run_batch(pipe, sub, sub_len, npdt, p, want_qad, cap_rows, pool, auto_noise=auto_noise)
+        got, qad, src, starts, found, cfound = _run_batch(pipe, sub, sub_len, npdt, p, want_qad, cap_rows, pool, auto_noise=auto_noise, center=center)
     if auto_noise == "only":
         return found
     for j, i in enumerate(short):
@@ -357,6 +600,8 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise):
         items[i].seq = int(i)
         if auto_noise:
             noise[i], flags[i] = found[0][j], found[1][j]
+        if center is not None:
+            centers[i], cflags[i] = cfound[0][j], cfound[1][j]
         if want_qad:
             qads[i] = qad[int(starts[j]):int(starts[j]) + items[i].n_samples]     # (an auto_noise capture that is gated entirely: zeros(2))
 
@@ -365,13 +610,15 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise):
     for i in long_:
         c = caps[i]
         t = c if on_device else torch.from_numpy(c).to(pipe.device)
-        res = pipe.iq_to_bits(t.contiguous(), p_pass, want_qad=want_qad, cap_rows=cap_rows if isinstance(cap_rows, int) else None,
-                              auto_noise=bool(auto_noise))
+        res = pipe.iq_to_bits(t.contiguous(), p_pass, want_qad=want_qad or center is not None, cap_rows=cap_rows if isinstance(cap_rows, int) else None,
+                              auto_noise=bool(auto_noise), auto_center=center is not None, center_max_size=center["max_size"] if center else None)
         if auto_noise:
             flags[i] = res.noise_flag
             noise[i] = float(res._noise)
             if flags[i] == 0:                              # the reference raises for this capture: nothing to hand out
                 continue
+        if center is not None:
+            centers[i], cflags[i] = res.center, res.center_flag
         h = res.host(pool={})
         h.seq = int(i)
         items[i] = h
@@ -382,18 +629,22 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise):
         """capture k alone with `rows` rows of capacity, results in pinned memory of their own"""
         c = caps[k]
         t = c if on_device else torch.from_numpy(c).to(pipe.device)
-        if auto_noise:                                     # (alone through the same entry point: it detects the same threshold)
+        if center is not None:                             # (alone through the same entry point: it detects the same threshold and center)
+            one = iq_to_bits_batch_center(pipe, [t.contiguous()], p, auto_noise=bool(auto_noise), center_max_size=center["max_size"], want_qad=want_qad,
+                                          cap_rows=int(rows), long_from=long_from, _pool={}, _cap_tie=center.get("cap_tie"))
+        elif auto_noise:                                   # (alone through the same entry point: it detects the same threshold)
             one = iq_to_bits_batch_auto(pipe, [t.contiguous()], p, want_qad=want_qad, cap_rows=int(rows), long_from=long_from, _pool={})
         else:
             one = iq_to_bits_batch(pipe, [t.contiguous()], p, want_qad=want_qad, cap_rows=int(rows), long_from=long_from, _pool={})
         return one[0], (one.qad(0) if want_qad else None)
 
-    return BatchBits(items, p, lengths, qads, rerun, noise, flags)
+    return BatchBits(items, p, lengths, qads, rerun, noise, flags, centers, cflags)
 
 
 def launch_counts(pipe):
     """(kernel launches, copies) the batch entry points have issued on the pipeline's context so far: 3 and 2 per batch, 4 and 3 per batch
-    with automatic noise thresholds, 1 and 1 per detect_noise_levels"""
+    with automatic noise thresholds, 1 and 1 per detect_noise_levels; iq_to_bits_batch_center: 4 + 14 ceil(K / group) launches (5 + ... with
+    automatic noise) and 3 copies (4), plus -- whatever the number of tied captures -- 3 launches and 3 copies when any center was left to the host"""
     out = (C.c_int64 * 2)()
     _lib.check(_lib.load().urhgpu_batch_launches(pipe.ctx.handle, out))
     return int(out[0]), int(out[1])

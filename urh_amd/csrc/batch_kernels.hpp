@@ -1,7 +1,8 @@
 // batch_kernels.hpp -- the walk of a batch of captures (batch.hip: a WAVEFRONT PER CAPTURE), shared by the translation units that
-// instantiate it: batch.hip (every capture gated with p.noise_sqrd) and batch_auto.hip (DNOISE: every capture gated with the threshold
-// detected for it, k_batch_noise).  One definition of k_batch_bits, BatchArgs, batch_region, batch_capture and their helpers, so that the
-// two routes cannot drift apart.  A translation unit includes this header FIRST: it defines the URH_FDIV / URH_FSQRT forms that the
+// instantiate it: batch.hip (every capture gated with p.noise_sqrd), batch_auto.hip (DNOISE: every capture gated with the threshold
+// detected for it, k_batch_noise) and batch_center.hip (QIN: the captures are demodulated already and each is classified through the
+// thresholds of its own center).  One definition of k_batch_bits, BatchArgs, batch_region, batch_capture and their helpers, so that the
+// routes cannot drift apart.  A translation unit includes this header FIRST: it defines the URH_FDIV / URH_FSQRT forms that the
 // headers below it pick up.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -106,11 +107,24 @@ __device__ __forceinline__ uint32_t batch_shr1(uint32_t x, uint32_t lane0) {
 extern "C" __device__ int urh_llvm_writelane_i32(int value, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
 __device__ __forceinline__ int batch_lane(int x, int lane) { return __builtin_amdgcn_readlane(x, __builtin_amdgcn_readfirstlane(lane)); }
 
+// classify<ORDER2, true> with the thresholds at `t` instead of p.d_thr (the kernel's argument block cannot be pointed at a capture's own
+// thresholds; a copy of it with another d_thr would live in scratch memory): the same text, classify_thr (demod_prims.hpp); t == nullptr: p.thr
+template <bool ORDER2>
+__device__ __forceinline__ uint32_t classify_at(float q, const RunArgs &p, const float *t, bool check_noise = true) {
+    if (check_noise && q == p.noise_val) return kStPause;
+    return t ? classify_thr<ORDER2>(q, t, p.order) : classify<ORDER2>(q, p, false);
+}
+
 // DNOISE (batch_auto.hip): p.d_noise is the base of the batch's K urhgpu_noise_result blocks (k_batch_noise has written them on the same
 // stream) and capture c is gated with ITS block's noise_sqrd, loaded once (a uniform address).  Flag 2 -- the threshold is not below the
 // sample type's max_magnitude: the reference demodulates nothing and slices zeros(2) (Signal.py:474-484) -- is walked as a capture of two
 // samples, which the n <= 2 rule below turns into two zeros.  Without DNOISE the kernel reads p.noise_sqrd exactly where it always did.
-template <int DT, int MOD, bool ORDER2, bool DNOISE = false>
+// QIN (batch_center.hip): the captures are ALREADY demodulated -- b.qad is the input, q = qad[s0 + i] as it lies there (k_batch_demod has
+// applied the rules of sample 0 and of n <= 2; a caller's own signal is sliced as it is) -- and capture c is classified through ITS order - 1
+// thresholds at p.d_thr + c (order - 1) (classify_at, the device-threshold form of classify<ORDER2, true>: k_batch_center_publish has
+// written them on the same stream), or through p.thr where p.d_thr is null.  p.d_noise, where not null, still tells a flag-2 capture (two
+// samples).  DT is not used.
+template <int DT, int MOD, bool ORDER2, bool DNOISE = false, bool QIN = false>
 __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchArgs b) {
     const int lane = (int)threadIdx.x;
     if ((int64_t)blockIdx.x >= b.k) return;
@@ -124,10 +138,13 @@ __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchA
         nsq = r->noise_sqrd;
         two = r->flag == 2 && cap.n > 2;
     }
+    if (QIN && p.d_noise) two = ((const urhgpu_noise_result *)p.d_noise)[c].flag == 2 && cap.n > 2;
+    const float *thr_c = (QIN && p.d_thr) ? p.d_thr + c * (int64_t)(p.order - 1) : nullptr;      // (a uniform address)
     const uint32_t n = two ? 2u : (uint32_t)cap.n;             // < 2^31
     const uint32_t tol = (uint32_t)b.tol;
     const char *iq = (const char *)b.iq + cap.s0 * Iq<DT>::kBytes;
     float *qad = b.qad ? b.qad + cap.s0 : nullptr;
+    const float *qin = QIN ? b.qad + cap.s0 : nullptr;
     const uint32_t cap_rows = (uint32_t)cap.R.cap_rows;        // 0 without a region: nothing is stored
     int2 *rows = (int2 *)(b.work + (cap.ok ? cap.roff : 0) + cap.R.off_rows);
 
@@ -158,22 +175,28 @@ __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchA
 
     float c_b = 0.0f, d_b = 0.0f;                         // the step before (vector registers; its lane 63 is the seam)
     float c_n = 0.0f, d_n = 0.0f;
-    if ((uint32_t)lane < n) Iq<DT>::load1(iq, lane, c_n, d_n);
+    if (QIN) { if ((uint32_t)lane < n) c_n = qin[lane]; }
+    else if ((uint32_t)lane < n) Iq<DT>::load1(iq, lane, c_n, d_n);
     for (uint32_t base = 0; base < n; base += kBatchStep) {
         const float cc = c_n, dd = d_n;
         const uint32_t i = base + (uint32_t)lane;
         const bool valid = i < n;
         c_n = d_n = 0.0f;
-        if (i + kBatchStep < n) Iq<DT>::load1(iq, i + kBatchStep, c_n, d_n);       // the next step's samples are on their way during this one's walk
+        if (QIN) { if (i + kBatchStep < n) c_n = qin[i + kBatchStep]; }
+        else if (i + kBatchStep < n) Iq<DT>::load1(iq, i + kBatchStep, c_n, d_n);  // the next step's samples are on their way during this one's walk
         const float pc = batch_shr1(cc, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c_b), 63)));
         const float pd = batch_shr1(dd, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d_b), 63)));
-        float q = demod_one<MOD, DT, DNOISE>(pc, pd, cc, dd, p, nsq);                     // (every lane: selects below instead of two more levels of branches)
-        q = (i == 0) ? p.noise_val : q;                                            // :361 (no predecessor: never the neighbouring capture's sample)
-        q = (n <= 2) ? 0.0f : q;                                                   // :335-336
-        const uint32_t st = classify<ORDER2>(q, p);
-        if (qad && valid) qad[i] = q;
+        float q;
+        if (QIN) q = cc;
+        else {
+            q = demod_one<MOD, DT, DNOISE>(pc, pd, cc, dd, p, nsq);                       // (every lane: selects below instead of two more levels of branches)
+            q = (i == 0) ? p.noise_val : q;                                            // :361 (no predecessor: never the neighbouring capture's sample)
+            q = (n <= 2) ? 0.0f : q;                                                   // :335-336
+        }
+        const uint32_t st = QIN ? classify_at<ORDER2>(q, p, thr_c) : classify<ORDER2>(q, p);
+        if (!QIN && qad && valid) qad[i] = q;
         if (base == 0)      // :421-427: PAUSE when sample 0 is NOISE, else the state of the literal 0.0 (s is still 0 there)
-            cur_state = ((uint32_t)batch_lane((int)st, 0) == kStPause) ? kStPause : classify<ORDER2>(0.0f, p, false);
+            cur_state = ((uint32_t)batch_lane((int)st, 0) == kStPause) ? kStPause : (QIN ? classify_at<ORDER2>(0.0f, p, thr_c, false) : classify<ORDER2>(0.0f, p, false));
         const uint32_t before = batch_shr1(st, run_state);
         const uint64_t bm = __builtin_amdgcn_ballot_w64(valid && st != before);    // lanes that start a run
         const int cnt = (int)((n - base < kBatchStep) ? (n - base) : kBatchStep);

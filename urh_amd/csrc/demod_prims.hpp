@@ -160,18 +160,22 @@ __device__ __forceinline__ float atan2f_dev(float y, float x) {
     return (z - pi_lo) - pi;
 }
 
+// the state of a sample that is not NOISE from order - 1 thresholds in device memory at t: the ONE text of the device-threshold form, for
+// classify<.., true> (t = RunArgs::d_thr) and for a batch's walk, whose captures each have thresholds of their own (batch_kernels.hpp)
+template <bool ORDER2>
+__device__ __forceinline__ uint32_t classify_thr(float q, const float *t, int order) {
+    if (ORDER2) return (q <= t[0]) ? 1u : 2u;
+    int st = order - 1;
+    for (int k = 0; k < order - 1; ++k)
+        if (q <= t[k]) { st = k; break; }
+    return (uint32_t)st + 1u;
+}
+
 // DTHR (the qad-input instantiations): the thresholds may live in device memory (RunArgs::d_thr) -- plain loads of a uniform address
 template <bool ORDER2, bool DTHR = false>
 __device__ __forceinline__ uint32_t classify(float q, const RunArgs &p, bool check_noise = true) {
     if (check_noise && q == p.noise_val) return kStPause;
-    if (DTHR && p.d_thr) {
-        const float *t = p.d_thr;
-        if (ORDER2) return (q <= t[0]) ? 1u : 2u;
-        int st = p.order - 1;
-        for (int k = 0; k < p.order - 1; ++k)
-            if (q <= t[k]) { st = k; break; }
-        return (uint32_t)st + 1u;
-    }
+    if (DTHR && p.d_thr) return classify_thr<ORDER2>(q, p.d_thr, p.order);
     if (ORDER2) return (q <= p.thr[0]) ? 1u : 2u;
     int st = p.order - 1;
     for (int k = 0; k < p.order - 1; ++k)

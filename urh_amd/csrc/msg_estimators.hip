@@ -23,37 +23,17 @@
 
 #include "common.hpp"
 #include "launchers.hpp"
+#include "msg_state.hpp"
 #include "pass.hpp"
 
 namespace urh {
 
-constexpr int kMeTile = 4096;                 // samples per tile: 256 threads x 16 consecutive samples
-constexpr int kMeBlock = 256;
+constexpr int kMeBlock = 256;                 // (kMeTile, msg_state.hpp: 256 threads x 16 consecutive samples)
 constexpr int kMePer = kMeTile / kMeBlock;
 constexpr int kPwChunkM = 8192, kPwLeafM = 128, kLeavesPerTile = kMeTile / kPwLeafM;    // numpy's pairwise summation geometry
 
 struct MsgTile { int32_t msg; int32_t idx; };           // tile `idx` of message `msg`
 
-struct MsgState {            // one per message, device resident between the stages (host mirror: same layout)
-    int64_t start, end;      // sample range in the demodulated signal
-    int64_t first_tile;      // index of its first tile in the tile table
-    int64_t kept;            // samples > -4 (AutoInterpretation.py:227)
-    int64_t a, L;            // trimmed range [a, a + L) of the kept samples (:231)
-    float mn, mx;            // util.minmax of the trimmed samples (:236)
-    float mean, var;         // float32 np.mean / np.var (:240)
-    double e0, delta;        // bin edges e0 + i * delta (np.arange(min, max + step, step), :243)
-    int64_t n_edges;         // 0: no histogram (empty, zero / NaN variance, fewer than 2 edges); > max_bins + 1: too many for the pool
-    int64_t n_plateaus;      // urhgpu_msg_plateaus: plateaus found, -1: the window did not reach the 25 % mark
-    int64_t edge_cnt;        // boundaries found in the window
-    int64_t window;          // samples of the message searched for boundaries
-    double center;           // center handed to urhgpu_msg_plateaus (NaN: none)
-    double peak_center;      // urhgpu_msg_center_stats: center picked from the histogram (k_me_peaks)
-    int64_t peak_flag;       // 0 none, 1 peak_center valid, 2 more bins than the pool holds, 3 equally populated peaks compete for a slot
-    int64_t skip;            // 1: the message's first sample is filtered (x <= -4: afp_demod's result[0] = NOISE of FSK / PSK) -- k_me_first
-    int64_t pairs_base;      // urhgpu_msg_plateau_decisions: first (value, count) pair of the message's plateau lengths in the pool ...
-    int64_t pairs_n;         // ... and how many; -1: more distinct lengths than the table holds / the pool is full (the sequence decides)
-    int64_t cut;             // detect_center's max_size (AutoInterpretation.py:233-234): 0 none, else max_size + 1 -- the trimmed range keeps its first max_size samples
-};
 // the trimmed range's length after the cut (every place that derives L from the kept count goes through here)
 __host__ __device__ inline int64_t me_cut(const MsgState &m, int64_t L) { return (m.cut > 0 && L > m.cut - 1) ? m.cut - 1 : L; }
 // nothing filtered but (possibly) the first sample: the kept samples ARE x[start + skip : end], no compaction needed
@@ -1326,6 +1306,142 @@ int center_publish(const CenterChain &c, const urhgpu_params *p, void *d_result,
     return URHGPU_OK;
 }
 
+// The histogram pool holds max_bins counters per message and is cleared for every call: a capture cut into 10^5 .. 10^6 segments (a
+// bursty capture whose modulation is not OOK, so nothing was merged) would ask for gigabytes of it at once.  The messages are
+// therefore taken in batches whose pool stays below kCenterBatchBytes; the compacted samples (indexed by message start) are shared.
+constexpr size_t kCenterBatchBytes = size_t(64) << 20;
+
+// ---- the center chain over the captures of a batch: detect_center of K ranges, asynchronously ------------------------------------------------
+// center_stats_batch's launches for the captures [c0, c0 + kg) of a batch -- back to back in one demodulated buffer, start[k + 1] on the
+// device: ascending disjoint ranges --, with the states built ON the device (k_bc_init_states), no MsgState upload, no read-back and no
+// wait, as center_chain_async is for one range.  The host does not know how many tiles the ranges take (a capture whose noise flag is 2
+// has the range of its two zeros, a refused capture none), so the tile table has an upper bound of entries, total / kMeTile + kg + 1, and a
+// SPARE range behind the kg captures -- empty, first_tile = the tiles the captures really take -- owns the surplus: k_me_fill_tiles maps
+// every surplus tile to it, and a tile of an empty range is skipped by every stage (L = 0, no edges, clean).  Starts that overlap (malformed:
+// the lengths then sum to more than total) could ask for more tiles than the table has: a capture whose tiles do not fit gets the empty
+// range -- no center, flag 0.
+constexpr int kBcInitBlock = 1024;
+__global__ __launch_bounds__(kBcInitBlock) void k_bc_init_states(const int64_t *start, int64_t total, const urhgpu_noise_result *noise, int64_t c0, int kg,
+                                                                  int64_t cut, int64_t cap_tiles, MsgState *st) {
+    __shared__ int64_t s_a[kBcInitBlock / 64];
+    __shared__ int64_t s_used[kBcInitBlock / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int per = (kg + kBcInitBlock - 1) / kBcInitBlock;
+    const int lo = (tid * per < kg) ? tid * per : kg, hi = (lo + per < kg) ? lo + per : kg;
+    // capture c's range: [s0, s0 + n) -- the batch's rules (batch_kernels.hpp: batch_capture) --, two samples for a noise flag 2
+    auto range_of = [&](int m, int64_t &s0, int64_t &n) {
+        const int64_t c = c0 + m;
+        s0 = start[c];
+        const int64_t s1 = start[c + 1];
+        const bool ok = s0 >= 0 && s1 >= s0 && s1 <= total && s1 - s0 <= 0x7fffffffll;
+        n = ok ? s1 - s0 : 0;
+        if (!ok) s0 = 0;
+        if (noise && noise[c].flag == 2 && n > 2) n = 2;
+    };
+    int64_t a = 0;                                           // tiles of this thread's captures
+    for (int m = lo; m < hi; ++m) { int64_t s0, n; range_of(m, s0, n); a += me_tiles_of(n); }
+    int64_t ia = a;                                          // inclusive scan over the threads
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int64_t ua = __shfl_up(ia, o); if (lane >= o) ia += ua; }
+    if (lane == 63) s_a[wave] = ia;
+    __syncthreads();
+    int64_t fa = ia - a;
+    for (int w = 0; w < wave; ++w) fa += s_a[w];
+    int64_t used = 0;                                        // the tiles of the captures that fit: prefixes are monotone, so those are the first ones
+    for (int m = lo; m < hi; ++m) {
+        int64_t s0, n;
+        range_of(m, s0, n);
+        const int64_t nt = me_tiles_of(n);
+        MsgState z;
+        memset(&z, 0, sizeof(z));
+        z.center = __builtin_nan(""); z.cut = cut;
+        if (fa + nt <= cap_tiles) { z.start = s0; z.end = s0 + n; z.first_tile = fa; z.window = n; used = fa + nt; }
+        else { z.first_tile = -1; }                          // (settled below, once `used` is known)
+        st[m] = z;
+        fa += nt;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const int64_t u = __shfl_xor(used, o); used = u > used ? u : used; }
+    if (lane == 0) s_used[wave] = used;
+    __syncthreads();
+    for (int w = 0; w < kBcInitBlock / 64; ++w) used = s_used[w] > used ? s_used[w] : used;
+    for (int m = lo; m < hi; ++m) if (st[m].first_tile < 0) st[m].first_tile = used;
+    if (tid == 0) {                                          // the spare range
+        MsgState z;
+        memset(&z, 0, sizeof(z));
+        z.center = __builtin_nan(""); z.cut = cut; z.first_tile = used;
+        st[kg] = z;
+    }
+}
+
+BatchCenterScratch batch_center_scratch(int64_t k, int64_t total, int64_t max_bins) {
+    BatchCenterScratch L;
+    memset(&L, 0, sizeof(L));
+    const int64_t per = std::max<int64_t>(1, (int64_t)(kCenterBatchBytes / ((size_t)max_bins * 4)));
+    L.group = per;
+    L.n_groups = (k + per - 1) / per;
+    const int64_t kg = std::min<int64_t>(k, per), n = std::max<int64_t>(total, 0);
+    L.n_tiles = n / kMeTile + kg + 1;
+    const size_t nt = (size_t)L.n_tiles, nm = (size_t)kg + 1;
+    size_t o = 0;
+    auto put = [&](size_t bytes) { const size_t at = o; o = align256(o + bytes); return at; };
+    L.off_st = put(nm * sizeof(MsgState));
+    L.off_tiles = put(nt * sizeof(MsgTile));
+    L.off_pre = put((nt + 1) * 8);
+    L.off_mm = put(nt * 8);
+    L.off_half = put((nt + 1) * 4);
+    L.off_leaf = put(nt * kLeavesPerTile * 4);
+    L.off_kept = put((size_t)std::max<int64_t>(n, 1) * 4);
+    L.off_wide = put(nm * 4);
+    L.pool_bytes = align256(nm * (size_t)max_bins * 4 + 256);
+    L.off_hist = put(L.pool_bytes + nt * 4);
+    L.bytes = o;
+    return L;
+}
+
+int center_stats_batch_async(const float *d_x, int64_t total, const int64_t *d_start, int64_t k, const void *d_noise, int64_t c0, int64_t kg,
+                             int64_t max_size, int64_t max_bins, const BatchCenterScratch &L, char *w, hipStream_t s, MsgState **out_st,
+                             unsigned int **out_hist) {
+    if (kg < 1 || kg > L.group || c0 < 0 || c0 + kg > k || L.n_tiles > INT32_MAX) return URHGPU_ERR_ARG;
+    const int n_msgs = (int)kg + 1;                          // the captures and the spare range
+    const int64_t n_tiles = L.n_tiles;
+    MsgState *d_st = (MsgState *)(w + L.off_st);
+    MsgTile *d_tiles = (MsgTile *)(w + L.off_tiles);
+    int64_t *d_pre = (int64_t *)(w + L.off_pre);
+    float2 *d_mm = (float2 *)(w + L.off_mm);
+    float *d_half = (float *)(w + L.off_half);
+    float *d_leaf = (float *)(w + L.off_leaf);
+    float *d_kept = (float *)(w + L.off_kept);
+    int *d_wide = (int *)(w + L.off_wide);
+    unsigned int *d_hist = (unsigned int *)(w + L.off_hist);
+    unsigned int *d_any_wide = d_hist + (size_t)n_msgs * (size_t)max_bins, *d_any_dirty = d_any_wide + 1;
+    int32_t *d_cnt = (int32_t *)((char *)d_hist + L.pool_bytes);
+    *out_st = d_st; *out_hist = d_hist;
+    hipLaunchKernelGGL(k_bc_init_states, dim3(1), dim3(kBcInitBlock), 0, s, d_start, total, (const urhgpu_noise_result *)d_noise, c0, (int)kg,
+                       max_size < 0 ? (int64_t)0 : max_size + 1, n_tiles - 1, d_st);
+    // from here on: center_stats_batch's launches, in its order
+    hipLaunchKernelGGL(k_me_fill_tiles, dim3((unsigned)((n_tiles + 255) / 256)), dim3(256), 0, s, d_st, n_msgs, d_tiles, n_tiles);
+    URH_HIP(hipMemsetAsync(d_hist, 0, L.pool_bytes + (size_t)n_tiles * 4, s));
+    const unsigned gt = (unsigned)n_tiles, gm = (unsigned)((n_msgs + 63) / 64);
+    hipLaunchKernelGGL(k_me_first, dim3(gt), dim3(kMeBlock), 0, s, d_x, d_st, d_tiles, d_cnt, d_mm, d_half);
+    hipLaunchKernelGGL(k_me_tile_scan, dim3(1), dim3(kMeScanBlock), 0, s, d_cnt, n_tiles, d_pre, d_st, n_msgs, d_any_dirty);
+    hipLaunchKernelGGL(k_me_compact, dim3((unsigned)((n_tiles + kMeCompactGroup - 1) / kMeCompactGroup)), dim3(kMeBlock), 0, s, d_x, d_st, d_tiles, n_tiles,
+                       d_pre, d_kept, d_leaf, d_mm, d_any_dirty);
+    hipLaunchKernelGGL(k_me_dirty_trees, dim3((unsigned)((n_tiles + kMeBlock / 64 - 1) / (kMeBlock / 64))), dim3(kMeBlock), 0, s, d_kept, d_st, d_tiles,
+                       n_tiles, d_leaf, d_half, d_any_dirty);
+    hipLaunchKernelGGL(k_me_sum_fin, dim3((unsigned)n_msgs), dim3(kMeSumBlock), 0, s, d_x, d_kept, d_st, d_half, d_mm, 0);
+    hipLaunchKernelGGL(k_me_leaves, dim3(gt), dim3(kMeBlock), 0, s, d_x, d_kept, d_st, d_tiles, d_half);
+    hipLaunchKernelGGL(k_me_sum_fin, dim3((unsigned)n_msgs), dim3(kMeSumBlock), 0, s, d_x, d_kept, d_st, d_half, d_mm, 1);
+    hipLaunchKernelGGL(k_me_bins, dim3(gm), dim3(64), 0, s, d_st, n_msgs, max_bins, d_any_wide, d_wide);
+    hipLaunchKernelGGL((k_me_hist<kMeHistSmall>), dim3((unsigned)((n_tiles + kMeHistGroup - 1) / kMeHistGroup)), dim3(kMeBlock), 0, s, d_x, d_kept, d_st,
+                       d_tiles, n_tiles, max_bins, d_hist, d_any_wide, d_wide);
+    hipLaunchKernelGGL((k_me_hist<kMeHistLds>), dim3((unsigned)std::min<int64_t>((n_tiles + kMeHistGroup - 1) / kMeHistGroup, 1024)), dim3(kMeBlock), 0, s,
+                       d_x, d_kept, d_st, d_tiles, n_tiles, max_bins, d_hist, d_any_wide, d_wide);
+    hipLaunchKernelGGL(k_me_peaks, dim3((unsigned)n_msgs), dim3(kMeBlock), 0, s, d_st, d_hist, max_bins);
+    URH_HIP(hipGetLastError());
+    return URHGPU_OK;
+}
+
 }  // namespace urh
 
 using namespace urh;
@@ -1481,10 +1597,8 @@ static void center_stats_collect(const MsgBatch &b, int n_msgs, int64_t max_bins
     }
 }
 
-// The histogram pool holds max_bins counters per message and is cleared for every call: a capture cut into 10^5 .. 10^6 segments (a
-// bursty capture whose modulation is not OOK, so nothing was merged) would ask for gigabytes of it at once.  The messages are
-// therefore taken in batches whose pool stays below kCenterBatchBytes; the compacted samples (indexed by message start) are shared.
-constexpr size_t kCenterBatchBytes = size_t(64) << 20;
+// (kCenterBatchBytes, above: the messages are taken in batches whose histogram pool stays below it; the compacted samples -- indexed by
+// message start -- are shared)
 
 int urhgpu_msg_center_stats(urhgpu_ctx *ctx, const float *d_x, int64_t n, const int64_t *ranges, int n_msgs, int64_t max_bins,
                             double *out_stats, int64_t *out_hist, double *out_center, int32_t *out_flag) {

@@ -903,6 +903,42 @@ class DevicePipeline:
         from .batch import iq_to_bits_batch_auto
         return iq_to_bits_batch_auto(self, captures, p, auto_noise, want_qad, cap_rows, long_from, **options)
 
+    def iq_to_bits_batch_center(self, captures, p: DemodParams, auto_noise=True, center_max_size=None, want_qad=False, cap_rows=None, long_from=None,
+                                **options):
+        """iq_to_bits_batch_auto with the CENTER of every capture detected on the device too (AutoInterpretation.detect_center on the capture's
+        own demodulated signal, max_size=center_max_size) and each capture sliced with its own: capture k is, bit for bit, what
+        iq_to_bits(capture_k, p, auto_noise=auto_noise, auto_center=True, center_max_size=center_max_size) gives on that capture alone.  The
+        number of launches and copies does not depend on the number of captures but through ceil(K / group), the groups the center chain
+        takes them in (include/urhgpu.h "a batch of captures: automatic center per capture"; DESIGN.md 7.7g has the figures).
+        captures, want_qad, cap_rows, long_from: as for iq_to_bits_batch; a capture of long_from samples or more goes through
+        iq_to_bits(..., auto_noise=auto_noise, auto_center=True, center_max_size=center_max_size).  auto_noise=False gates every capture with
+        p.noise_threshold.
+        Returns a batch.BatchBits that also carries .centers (a Python float per capture, None where detect_center gives None: that capture
+        is sliced with p.center) and .center_flags (urhgpu_center_result's flag as the device reported it: 1 decided on the device, 0 None,
+        2 more bins than the pool holds, 3 a tie between the second and the third peak).  Flag 2 and 3 are settled before the method
+        returns -- tied histograms with numpy on the counts the device shipped, the others by the single-range estimator -- and ALL captures
+        settled to a center are sliced again by one more call; their HostBits replace the first ones.  With auto_noise, .noise and
+        .noise_flags as for iq_to_bits_batch_auto: a noise flag 2 gives center None, center flag 0 and the slicing of two zeros with p.center;
+        a noise flag 0 raises the reference's exception where that capture is handed out.
+        ASK and FSK; PSK, msg_records and dc_correction are not options of a batch (ValueError says what to call)."""
+        from .batch import iq_to_bits_batch_center
+        return iq_to_bits_batch_center(self, captures, p, auto_noise, center_max_size, want_qad, cap_rows, long_from, **options)
+
+    def detect_centers(self, captures, max_size=None):
+        """AutoInterpretation.detect_center of every capture of a batch of DEMODULATED signals, captures = (qad_cat, starts) with capture k =
+        qad_cat[starts[k]:starts[k + 1]] (a float32 device tensor or numpy array): one chain of kernels whose launch count does not depend on
+        the number of captures but through ceil(K / group), and two read-backs at most -- the batch counterpart of
+        estimators.detect_center_dev.  Returns a list of Python floats, None where detect_center gives None (batch.detect_centers)."""
+        from .batch import detect_centers
+        return detect_centers(self, captures, max_size)
+
+    def qad_to_bits_batch(self, captures, p: DemodParams, centers=None, cap_rows=None):
+        """The walk of a batch alone on captures that are already demodulated, captures = (qad_cat, starts): three launches, one upload, two
+        copies back.  centers: None -- every capture is sliced with p.center -- or one entry per capture, a float or None (p.center).
+        Returns a batch.BatchBits, each HostBits equal to what qad_to_bits gives for that capture's signal alone."""
+        from .batch import qad_to_bits_batch
+        return qad_to_bits_batch(self, captures, p, centers, cap_rows)
+
     def detect_noise_levels(self, captures):
         """AutoInterpretation.detect_noise_level of every capture of a batch in ONE launch and one read (batch.detect_noise_levels)"""
         from .batch import detect_noise_levels
