@@ -1234,6 +1234,49 @@ int urhgpu_iq_to_bits_batch_center_dev(urhgpu_ctx *ctx, const void *d_iq, int64_
 int urhgpu_batch_center_fetch(urhgpu_ctx *ctx, const void *d_result, int64_t k, const uint32_t *d_tie, int64_t cap_tie, void *h_result,
                               uint32_t *h_tie, int64_t cap_host, int64_t *used);
 
+/* ---- a batch of captures: message records per capture, on the device --------------------------------------------------------------
+ * What a user wants from a recording session is its messages: ProtocolAnalyzer.get_protocol_from_signal gives every Message of every file an
+ * RSSI, a timestamp and, for ASK, the padding to message_length_divisor ("message records inside a pass" above has the arithmetic and the
+ * record).  Here that step is queued behind the walk of a batch -- urhgpu_iq_to_bits_batch_dev, _batch_auto_dev, _batch_center_dev or
+ * urhgpu_qad_to_bits_batch_dev -- for all K captures at once.  Capture c's records are those of urhgpu_msg_records_dev behind
+ * urhgpu_iq_to_bits_dev on that capture alone, bit for bit, the RSSI included.
+ *   urhgpu_batch_msg_records_dev   asynchronous on the context's stream, the caller owns all memory, nothing is copied or waited for.
+ *            Queued behind the batch pass that filled d_work and d_counts, before anything rewrites them.  d_iq, total, d_plan, k, p, d_work,
+ *            work_bytes, d_counts: that pass's (of the qad-input walk: the samples the captures were demodulated from).  THREE launches
+ *            whatever k, the lengths and the number of messages are:
+ *              directory   d_rec_dir: int64[k + 1], the exclusive prefix of the captures' stored messages (d_counts[8 c + 1]): capture c's
+ *                          records are d_rec[d_rec_dir[c] .. d_rec_dir[c + 1]), d_rec_dir[k] = M, the messages of the whole batch.  The host
+ *                          knows M without reading it: the sum of the blob headers' n_msg.
+ *              positions   a batch ships no positions (they are a function of the pulse table); a wavefront per capture derives the three
+ *                          entries a record needs -- the first bit's, the entry np - 2 and the middle bit's -- from the capture's stored rows
+ *                          in d_work, with _ppseq_to_bits' control flow and arithmetic (ProtocolAnalyzer.py:346-411)
+ *              RSSI        a workgroup per message over a bounded grid; the window [mid_pos, mid_pos + samples_per_symbol) is Python's slice
+ *                          of THE CAPTURE: clipped at its length n_c = d_start[c + 1] - d_start[c], whatever its noise flag -- the next
+ *                          capture lies directly behind it.  No load leaves [d_start[c], d_start[c + 1]).
+ *            d_start: int64[k_all + 1], the captures' first samples in d_iq.  d_map: NULL (then k_all == k, capture j's samples are capture
+ *            j's), or int64[k]: capture j of this call -- its plan entry, region and counts -- takes its samples from capture d_map[j] of
+ *            d_start, whose length is the length its region was planned for.  That serves captures sliced a second time from a gathered
+ *            demodulated buffer (urhgpu_qad_to_bits_batch_dev after a center the host settled): their rows lie in the second call's regions,
+ *            their samples where they were.  An index outside [0, k_all) is a refused capture.  d_noise: NULL, or the batch's
+ *            urhgpu_noise_result[k]; a capture's region is laid out from its true length also where its flag is 2 and two samples were
+ *            walked, and its window is clipped at the true length, so the blocks are accepted and not read.
+ *            d_rec: urhgpu_msg_record[cap_rec], 16-byte aligned; d_rec_capture: int32[cap_rec], for record i the capture of d_start its
+ *            samples lie in.  A message beyond cap_rec is not stored; the sum of the plan's row capacities / 2 + 1 holds every batch.
+ *            Flags as for urhgpu_msg_record; every stored message of a capture whose results were truncated or refused (bits 0 and 3 of
+ *            `truncated`) gets flag 0 and a NaN RSSI: repeat that capture with the rows it needs.
+ *            Rejected before anything is launched (and without a GPU, in this order): parameters a batch refuses -- PSK and
+ *            URHGPU_MOD_OTHER: URHGPU_ERR_UNSUPPORTED; a sample type: URHGPU_ERR_DTYPE --, a message_length_divisor outside 1 .. 2^30,
+ *            cap_rec < 0, a misaligned pointer, a missing context or buffer: URHGPU_ERR_ARG.
+ *   urhgpu_batch_records_fetch     ONE copy of the first n_rec records into h_rec (pinned host memory, 16-byte aligned); synchronous.  None
+ *            for n_rec = 0.  n_rec > cap_rec: URHGPU_ERR_CAPACITY.
+ * urhgpu_batch_launches counts these too: 3 launches per urhgpu_batch_msg_records_dev and 1 copy per urhgpu_batch_records_fetch of at least
+ * one record, whatever k, the lengths and M are. */
+int urhgpu_batch_msg_records_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, int64_t k_all, const int64_t *d_map,
+                                 const int64_t *d_plan, int64_t k, const urhgpu_params *p, const urhgpu_noise_result *d_noise,
+                                 int64_t message_length_divisor, const void *d_work, int64_t work_bytes, const int64_t *d_counts,
+                                 int64_t *d_rec_dir, void *d_rec, int64_t cap_rec, int32_t *d_rec_capture);
+int urhgpu_batch_records_fetch(urhgpu_ctx *ctx, const void *d_rec, int64_t n_rec, int64_t cap_rec, void *h_rec);
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,8 @@ PROTOTYPES = {
     "urhgpu_iq_to_bits_batch_center_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _i, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp,
                                                 _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
     "urhgpu_batch_center_fetch": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, C.POINTER(_i64)]),
+    "urhgpu_batch_msg_records_dev": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "urhgpu_batch_records_fetch": (_i, [_vp, _vp, _i64, _i64, _vp]),
 }
 
 _lib = None

@@ -17,6 +17,10 @@ demodulated into one buffer, one chain of kernels runs AutoInterpretation.detect
 capture through the thresholds of its center.  Where the device leaves a center to numpy (more bins than its pool holds, a tie between
 the second and the third peak) the host settles it and ALL those captures are sliced again by one more call.  detect_centers is the chain
 alone, qad_to_bits_batch the walk alone.
+
+DevicePipeline.iq_to_bits_batch_records ends any of the three with the session's MESSAGES: one record per message (RSSI, first position,
+ASK padding) queued behind the walk for all captures at once (urh_amd/csrc/batch_records.hip) -- three more launches and one more copy,
+whatever the number of captures and of messages.  BatchBits.messages() is then what ProtocolAnalyzer.get_protocol_from_signal builds per file.
 """
 import ctypes as C
 from dataclasses import replace
@@ -36,7 +40,8 @@ _NOT_IN_A_BATCH = {
     "auto_center": "iq_to_bits_batch slices every capture with p.center: call iq_to_bits_batch_center(captures, p, auto_noise=False), which detects a center "
                    "per capture (or call iq_to_bits(..., auto_center=True) per capture, or a CaptureStream(auto_center=True))",
     "auto_noise": "iq_to_bits_batch gates every capture with p.noise_threshold: call iq_to_bits_batch_auto(captures, p), which detects a threshold per capture",
-    "msg_records": "a batch computes no message records: call iq_to_bits(..., msg_records=True) per capture, or a CaptureStream(msg_records=True)",
+    "msg_records": "iq_to_bits_batch computes no message records: call iq_to_bits_batch_records(captures, p), which queues them behind the batch (or call "
+                   "iq_to_bits(..., msg_records=True) per capture, or a CaptureStream(msg_records=True))",
     "dc_correction": "a batch does not remove the captures' means: call iq_to_bits(..., dc_correction=True) per capture, or a CaptureStream(dc_correction=True)",
 }
 
@@ -142,8 +147,21 @@ class BatchBits:
             raise ValueError("the batch did not keep the demodulated signal (want_qad=True)")
         return self._qads[k]
 
+    def message_data(self, k, sample_rate=1e6, timestamp=0.0):
+        """iq_to_bits_batch_records: capture k's list of protocol.MessageData (HostBits.message_data); a truncated capture raises the
+        capacity error -- retry(k) runs it again, records included"""
+        return self[k].message_data(sample_rate, timestamp)
+
+    def messages(self, sample_rate=1e6, timestamps=None):
+        """iq_to_bits_batch_records: the session's messages, a list of MessageData per capture in the order given.  timestamps: one per
+        capture (Signal.timestamp of that file), default 0.0 for all"""
+        if timestamps is not None and len(timestamps) != len(self._items):
+            raise ValueError("timestamps holds one entry per capture")
+        return [self.message_data(k, sample_rate, 0.0 if timestamps is None else timestamps[k]) for k in range(len(self._items))]
+
     def retry(self, k):
-        """a truncated capture once more, alone, with the row capacity its first run reported; the result takes its place"""
+        """a truncated capture once more, alone, with the row capacity its first run reported; the result (with its records, where the
+        batch computed them) takes its place"""
         if self._rerun is None:
             raise ValueError("this result cannot run a capture again")
         h = self._items[k]
@@ -258,10 +276,53 @@ def _settle_centers(pipe, blocks, counts, k, qad, starts, n_of, max_size, skip=(
     return centers, flags, settled
 
 
-def _walk_qad(pipe, pool, qad, starts, p, thresholds, cap_rows, tag=""):
+def record_capacity(plan):
+    """records a batch with this plan can need at most: a region holds cap_rows / 2 + 1 messages (host arithmetic)"""
+    k = len(plan) // 3
+    return int((np.asarray(plan[k:2 * k], dtype=np.int64) // 2 + 1).sum())
+
+
+def _queue_records(pipe, src, d_map, d_plan, k, plan, divisor, d_noise, work, work_bytes, counts, tag=""):
+    """urhgpu_batch_msg_records_dev behind the batch pass that has just filled work and counts: three launches, nothing waited for.
+    src: where the samples lie -- (d_iq, total, d_start, k_all, the parameters with the sample type).  Returns (device records, capacity)."""
+    torch = pipe.torch
+    d_iq, total, d_start, k_all, cp = src
+    cap_rec = record_capacity(plan)
+    d_rec = pipe._buf("batch:rec" + tag, (C.sizeof(_lib.MsgRecord) * max(cap_rec, 1),), torch.uint8)
+    d_cap = pipe._buf("batch:rec_capture" + tag, (max(cap_rec, 1),), torch.int32)
+    d_dir = pipe._buf("batch:rec_dir" + tag, (k + 1,), torch.int64)
+    _lib.check(_lib.load().urhgpu_batch_msg_records_dev(
+        pipe.ctx.handle, C.c_void_p(d_iq), total, C.c_void_p(d_start), k_all, C.c_void_p(d_map) if d_map else None, C.c_void_p(d_plan), k, C.byref(cp),
+        C.c_void_p(d_noise.data_ptr()) if d_noise is not None else None, int(divisor), C.c_void_p(work.data_ptr()), work_bytes, C.c_void_p(counts.data_ptr()),
+        C.c_void_p(d_dir.data_ptr()), C.c_void_p(d_rec.data_ptr()), cap_rec, C.c_void_p(d_cap.data_ptr())))
+    return d_rec, cap_rec
+
+
+def _fetch_records(pipe, pool, queued, items, tag=""):
+    """urhgpu_batch_records_fetch: ONE copy of the 32 M bytes in use -- M is the sum of the blob headers' n_msg, the records lie compacted in
+    the captures' order -- and every HostBits gets its slice as .records (a view of pinned memory, valid as long as the blobs)"""
+    from .protocol import RECORD_DTYPE
+    torch = pipe.torch
+    d_rec, cap_rec = queued
+    n_msg = [int(h.n_msg) for h in items]
+    total = sum(n_msg)
+    h_rec = _pinned(torch, pool, "batch_rec" + tag, RECORD_DTYPE.itemsize * max(total, 1))
+    _lib.check(_lib.load().urhgpu_batch_records_fetch(pipe.ctx.handle, C.c_void_p(d_rec.data_ptr()), total, cap_rec, C.c_void_p(h_rec.data_ptr())))
+    rec = h_rec.numpy()[:RECORD_DTYPE.itemsize * total].view(RECORD_DTYPE)
+    at = 0
+    for h, n in zip(items, n_msg):
+        h.records = rec[at:at + n]
+        h._keep = (h._keep, h_rec)
+        at += n
+
+
+def _walk_qad(pipe, pool, qad, starts, p, thresholds, cap_rows, tag="", records=None):
     """urhgpu_qad_to_bits_batch_dev and its fetch on the captures qad[starts[j]:starts[j + 1]] (a device float32 tensor): the walk, scan and
     pack -- three launches --, one upload (starts, plan and the thresholds), two copies back.  thresholds: None (p.center for all) or
-    float32 [K][order - 1].  Returns the HostBits list; their views live in pinned memory named by `tag`."""
+    float32 [K][order - 1].  records: None, or (message_length_divisor, where the samples lie -- _queue_records' src --, int64[K]: the capture
+    of that buffer each of these was demodulated from): the records of this slicing are queued behind the walk and fetched, the map
+    uploaded with the starts -- three more launches and one more copy.  Returns the HostBits list; their views live in pinned memory named
+    by `tag`."""
     torch, lib = pipe.torch, _lib.load()
     starts = np.asarray(starts, dtype=np.int64)
     k = len(starts) - 1
@@ -270,12 +331,15 @@ def _walk_qad(pipe, pool, qad, starts, p, thresholds, cap_rows, tag=""):
     cp.write_bit_sample_pos = 0
     plan, work_bytes, blob_cap = batch_plan(lengths, cp, cap_rows)
     n_thr = 0 if thresholds is None else int(thresholds.size)
-    meta_bytes = (8 * (4 * k + 1) + _META_ALIGN - 1) // _META_ALIGN * _META_ALIGN
+    n_meta = 4 * k + 1 + (k if records is not None else 0)                     # starts, plan and -- with records -- the map
+    meta_bytes = (8 * n_meta + _META_ALIGN - 1) // _META_ALIGN * _META_ALIGN
     stage = _pinned(torch, pool, "batch_stage" + tag, meta_bytes + 4 * n_thr)
     view = stage.numpy()
-    meta = view[:8 * (4 * k + 1)].view(np.int64)
+    meta = view[:8 * n_meta].view(np.int64)
     meta[:k + 1] = starts
-    meta[k + 1:] = plan
+    meta[k + 1:4 * k + 1] = plan
+    if records is not None:
+        meta[4 * k + 1:] = records[2]
     if n_thr:
         view[meta_bytes:meta_bytes + 4 * n_thr].view(np.float32)[:] = thresholds.reshape(-1)
     pipe.ctx.set_stream(torch.cuda.current_stream(pipe.device).cuda_stream)
@@ -289,6 +353,10 @@ def _walk_qad(pipe, pool, qad, starts, p, thresholds, cap_rows, tag=""):
                                                 C.c_void_p(dev_in.data_ptr() + 8 * (k + 1)), k, C.byref(cp),
                                                 C.c_void_p(dev_in.data_ptr() + meta_bytes) if n_thr else None, n_thr, None, C.c_void_p(work.data_ptr()),
                                                 work_bytes, C.c_void_p(counts.data_ptr()), C.c_void_p(d_dir.data_ptr()), C.c_void_p(blob.data_ptr()), blob_cap))
+    queued = None
+    if records is not None:
+        queued = _queue_records(pipe, records[1], dev_in.data_ptr() + 8 * (4 * k + 1), dev_in.data_ptr() + 8 * (k + 1), k, plan, records[0], None, work,
+                                work_bytes, counts, tag)
     h_dir, h_blob = _fetch_blobs(pipe, pool, d_dir, k, blob, blob_cap, tag)
     offs = h_dir.numpy()[:8 * (k + 1)].view(np.int64)
     items = []
@@ -296,6 +364,8 @@ def _walk_qad(pipe, pool, qad, starts, p, thresholds, cap_rows, tag=""):
         h = HostBits.from_blob(h_blob.data_ptr() + int(offs[j]), p, seq=j, n_samples=int(lengths[j]), d_qad=qad.data_ptr() + 4 * int(starts[j]))
         h._keep = (h_blob, qad)
         items.append(h)
+    if queued is not None:
+        _fetch_records(pipe, pool, queued, items, tag)
     return items
 
 
@@ -319,12 +389,14 @@ def _fetch_blobs(pipe, pool, d_dir, k, blob, blob_cap, tag=""):
     return h_dir, h_blob
 
 
-def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq=None, device_starts=None, auto_noise=False, center=None):
+def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq=None, device_starts=None, auto_noise=False, center=None, records=None):
     """the short captures of a batch through the three launches.  caps: numpy arrays (packed and uploaded here, one copy), or device_iq (a
     device tensor that holds them back to back) with device_starts.  auto_noise: four launches -- every capture gated with the threshold
     detected for it (urhgpu_iq_to_bits_batch_auto_dev) -- and one more read, of the K result blocks; "only": that first launch and that
     read alone.  center: None, or {"max_size", "cap_tie"} -- every capture sliced with its own center (urhgpu_iq_to_bits_batch_center_dev),
-    the centers the device left to the host settled and those captures sliced again by ONE more call.
+    the centers the device left to the host settled and those captures sliced again by ONE more call.  records: None, or the
+    message_length_divisor -- the records of all captures are queued behind the walk (urhgpu_batch_msg_records_dev: before anything reuses
+    the work buffer) and fetched with one copy; the captures sliced again get the records of their second slicing the same way.
     Returns (HostBits list, qad tensor or None, device input, starts, (noise values, flags) or None, (centers, flags) or None)."""
     torch, lib = pipe.torch, _lib.load()
     k = len(lengths)
@@ -384,6 +456,8 @@ def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq
         _lib.check(lib.urhgpu_iq_to_bits_batch_auto_dev(*args, C.c_void_p(d_noise.data_ptr())))
     else:
         _lib.check(lib.urhgpu_iq_to_bits_batch_dev(*args))
+    rec_src = (d_iq, total, d_start, k, cp)
+    queued = None if records is None else _queue_records(pipe, rec_src, None, d_plan, k, plan, records, d_noise, work, work_bytes, counts)
     h_dir, h_blob = _fetch_blobs(pipe, pool, d_dir, k, blob, blob_cap)
     noise = fetch_noise() if auto_noise else None
     offs = h_dir.numpy()[:8 * (k + 1)].view(np.int64)
@@ -394,6 +468,8 @@ def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq
                                d_qad=(qad.data_ptr() + 4 * int(starts[i])) if qad is not None else 0)
         h._keep = (h_blob, qad)
         items.append(h)
+    if queued is not None:
+        _fetch_records(pipe, pool, queued, items)
     found = None
     if center is not None:
         blocks, tie_counts = _fetch_centers(pipe, pool, res, k, tie, cap_tie)
@@ -406,7 +482,8 @@ def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq
             parts = [qad[int(starts[i]):int(starts[i]) + n_of(i)] for i in settled]
             sub = torch.cat(parts) if len(parts) > 1 else parts[0]
             sub_starts = np.concatenate([[0], np.cumsum([n_of(i) for i in settled])]).astype(np.int64)
-            again = _walk_qad(pipe, pool, sub.contiguous(), sub_starts, p, center_thresholds(p, [centers[i] for i in settled]), cap_rows, tag=":again")
+            again = _walk_qad(pipe, pool, sub.contiguous(), sub_starts, p, center_thresholds(p, [centers[i] for i in settled]), cap_rows, tag=":again",
+                              records=None if records is None else (records, rec_src, np.asarray(settled, dtype=np.int64)))
             for i, h in zip(settled, again):
                 h.seq = i
                 items[i] = h
@@ -423,7 +500,8 @@ def iq_to_bits_batch(pipe, captures, p, want_qad=False, cap_rows=None, long_from
 _NOT_IN_A_BATCH_AUTO = {
     "auto_center": "iq_to_bits_batch_auto slices every capture with p.center: call iq_to_bits_batch_center(captures, p), which detects a threshold and a "
                    "center per capture (or call iq_to_bits(..., auto_noise=True, auto_center=True) per capture, or a CaptureStream)",
-    "msg_records": "a batch computes no message records: call iq_to_bits(..., auto_noise=True, msg_records=True) per capture, or a CaptureStream",
+    "msg_records": "iq_to_bits_batch_auto computes no message records: call iq_to_bits_batch_records(captures, p, auto_noise=True), which queues them behind "
+                   "the batch (or call iq_to_bits(..., auto_noise=True, msg_records=True) per capture, or a CaptureStream)",
     "dc_correction": "a batch does not remove the captures' means: call iq_to_bits(..., auto_noise=True, dc_correction=True) per capture, or a CaptureStream",
 }
 
@@ -461,7 +539,8 @@ def detect_noise_levels(pipe, captures):
 
 
 _NOT_IN_A_BATCH_CENTER = {
-    "msg_records": "a batch computes no message records: call iq_to_bits(..., auto_center=True, msg_records=True) per capture, or a CaptureStream",
+    "msg_records": "iq_to_bits_batch_center computes no message records: call iq_to_bits_batch_records(captures, p, auto_noise=..., auto_center=True), which "
+                   "queues them behind the batch (or call iq_to_bits(..., auto_center=True, msg_records=True) per capture, or a CaptureStream)",
     "dc_correction": "a batch does not remove the captures' means: call iq_to_bits(..., auto_center=True, dc_correction=True) per capture, or a CaptureStream",
 }
 
@@ -481,6 +560,31 @@ def iq_to_bits_batch_center(pipe, captures, p, auto_noise=True, center_max_size=
     """DevicePipeline.iq_to_bits_batch_center (see there)"""
     check_batch_center_options(p, **options)
     return _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, bool(auto_noise), center={"max_size": center_max_size, "cap_tie": _cap_tie})
+
+
+_NOT_IN_A_BATCH_RECORDS = {
+    "dc_correction": "a batch does not remove the captures' means: call iq_to_bits(..., msg_records=True, dc_correction=True) per capture, or a CaptureStream",
+}
+
+
+def check_batch_records_options(p, message_length_divisor=1, **options):
+    """what iq_to_bits_batch_records does not do raises ValueError with a sentence (host arithmetic: no GPU needed)"""
+    for name, value in options.items():
+        if name not in _NOT_IN_A_BATCH_RECORDS:
+            raise TypeError(f"iq_to_bits_batch_records() got an unexpected keyword argument '{name}'")
+        if value:
+            raise ValueError(f"{name} is not an option of a batch: {_NOT_IN_A_BATCH_RECORDS[name]}")
+    check_batch_options(p)
+    if not 1 <= int(message_length_divisor) <= 1 << 30:
+        raise ValueError("message_length_divisor must be at least 1 (and at most 2 ** 30)")
+
+
+def iq_to_bits_batch_records(pipe, captures, p, message_length_divisor=1, auto_noise=False, auto_center=False, center_max_size=None, want_qad=False,
+                             cap_rows=None, long_from=None, _pool=None, _cap_tie=None, **options):
+    """DevicePipeline.iq_to_bits_batch_records (see there)"""
+    check_batch_records_options(p, message_length_divisor, **options)
+    center = {"max_size": center_max_size, "cap_tie": _cap_tie} if auto_center else None
+    return _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, bool(auto_noise), center=center, records=int(message_length_divisor))
 
 
 def _qad_batch_input(pipe, captures):
@@ -539,8 +643,9 @@ def qad_to_bits_batch(pipe, captures, p, centers=None, cap_rows=None, _pool=None
     return BatchBits(items, p, np.diff(starts), qads, rerun, centers=None if centers is None else list(centers))
 
 
-def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, center=None):
-    """iq_to_bits_batch, iq_to_bits_batch_auto and iq_to_bits_batch_center: the input forms, the routing by length, the result sequence"""
+def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, center=None, records=None):
+    """iq_to_bits_batch, iq_to_bits_batch_auto, iq_to_bits_batch_center and iq_to_bits_batch_records (records: the message_length_divisor):
+    the input forms, the routing by length, the result sequence"""
     torch = pipe.torch
     long_from = LONG_FROM_DEFAULT if long_from is None else int(long_from)
     pool = pipe._pinned if _pool is None else _pool
@@ -590,9 +695,10 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, 
             dev_starts = None
         dev_cat = dev_cat.contiguous()
         got, qad, src, starts, found, cfound = _run_batch(pipe, None, sub_len, npdt, p, want_qad, cap_rows, pool, device_iq=dev_cat, device_starts=dev_starts,
-                                                          auto_noise=auto_noise, center=center)
+                                                          auto_noise=auto_noise, center=center, records=records)
     else:
-        got, qad, src, starts, found, cfound = _run_batch(pipe, sub, sub_len, npdt, p, want_qad, cap_rows, pool, auto_noise=auto_noise, center=center)
+        got, qad, src, starts, found, cfound = _run_batch(pipe, sub, sub_len, npdt, p, want_qad, cap_rows, pool, auto_noise=auto_noise, center=center,
+                                                          records=records)
     if auto_noise == "only":
         return found
     for j, i in enumerate(short):
@@ -611,7 +717,8 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, 
         c = caps[i]
         t = c if on_device else torch.from_numpy(c).to(pipe.device)
         res = pipe.iq_to_bits(t.contiguous(), p_pass, want_qad=want_qad or center is not None, cap_rows=cap_rows if isinstance(cap_rows, int) else None,
-                              auto_noise=bool(auto_noise), auto_center=center is not None, center_max_size=center["max_size"] if center else None)
+                              auto_noise=bool(auto_noise), auto_center=center is not None, center_max_size=center["max_size"] if center else None,
+                              msg_records=records is not None, message_length_divisor=records or 1)
         if auto_noise:
             flags[i] = res.noise_flag
             noise[i] = float(res._noise)
@@ -621,6 +728,12 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, 
             centers[i], cflags[i] = res.center, res.center_flag
         h = res.host(pool={})
         h.seq = int(i)
+        if records is not None:                            # a copy of the pass's records: its pinned block belongs to the slot
+            from .protocol import RECORD_DTYPE
+            try:
+                h.records = res.records.copy()
+            except _lib.UrhGpuError:                       # (a capacity was exceeded: message_data() says so, retry(k) repeats the capture)
+                h.records = np.zeros(0, RECORD_DTYPE)
         items[i] = h
         if want_qad:
             qads[i] = res.qad.clone()
@@ -629,7 +742,10 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, 
         """capture k alone with `rows` rows of capacity, results in pinned memory of their own"""
         c = caps[k]
         t = c if on_device else torch.from_numpy(c).to(pipe.device)
-        if center is not None:                             # (alone through the same entry point: it detects the same threshold and center)
+        if records is not None:                            # (alone through the same entry point, records included)
+            one = iq_to_bits_batch_records(pipe, [t.contiguous()], p, records, bool(auto_noise), center is not None, center["max_size"] if center else None,
+                                           want_qad, int(rows), long_from, _pool={}, _cap_tie=center.get("cap_tie") if center else None)
+        elif center is not None:                           # (alone through the same entry point: it detects the same threshold and center)
             one = iq_to_bits_batch_center(pipe, [t.contiguous()], p, auto_noise=bool(auto_noise), center_max_size=center["max_size"], want_qad=want_qad,
                                           cap_rows=int(rows), long_from=long_from, _pool={}, _cap_tie=center.get("cap_tie"))
         elif auto_noise:                                   # (alone through the same entry point: it detects the same threshold)
@@ -644,7 +760,8 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, 
 def launch_counts(pipe):
     """(kernel launches, copies) the batch entry points have issued on the pipeline's context so far: 3 and 2 per batch, 4 and 3 per batch
     with automatic noise thresholds, 1 and 1 per detect_noise_levels; iq_to_bits_batch_center: 4 + 14 ceil(K / group) launches (5 + ... with
-    automatic noise) and 3 copies (4), plus -- whatever the number of tied captures -- 3 launches and 3 copies when any center was left to the host"""
+    automatic noise) and 3 copies (4), plus -- whatever the number of tied captures -- 3 launches and 3 copies when any center was left to the host;
+    iq_to_bits_batch_records adds 3 launches and 1 copy to its batch, and as many to the second slicing of the captures left to the host"""
     out = (C.c_int64 * 2)()
     _lib.check(_lib.load().urhgpu_batch_launches(pipe.ctx.handle, out))
     return int(out[0]), int(out[1])

@@ -186,13 +186,13 @@ class HostBits:
         return self.bits(), self.msg_off.copy(), self.pauses.copy(), self.bit_sample_pos(), self.pos_offsets()
 
     def message_data(self, sample_rate=1e6, timestamp=0.0):
-        """results of a stream with msg_records: the list of protocol.MessageData ProtocolAnalyzer.get_protocol_from_signal builds its Message
-        objects from -- bits, pause and positions padded where the pass's record says so, RSSI and timestamp from the record.  Without
+        """results of a stream with msg_records, or of DevicePipeline.iq_to_bits_batch_records: the list of protocol.MessageData
+        ProtocolAnalyzer.get_protocol_from_signal builds its Message objects from -- bits, pause and positions padded where the pass's record says so, RSSI and timestamp from the record.  Without
         shipped positions (want_pos=False) bit_sample_pos is derived here from the pulse table."""
         from .protocol import messages_from_records
         rec = self.__dict__.get("records")
         if rec is None:
-            raise ValueError("this result carries no message records (CaptureStream(msg_records=True))")
+            raise ValueError("this result carries no message records (CaptureStream(msg_records=True), or iq_to_bits_batch_records for a batch)")
         self.check()
         if len(rec) != self.n_msg or not (rec["flag"] == 1).all():
             raise _lib.UrhGpuError(_lib.ERR_CAPACITY, "output capacity too small: a message's record is missing")

@@ -883,7 +883,7 @@ class DevicePipeline:
         Returns a batch.BatchBits: a sequence of HostBits, each equal to what iq_to_bits gives for that capture alone; .qad(k) (want_qad)
         is capture k's slice of the demodulated signal on the device, .retry(k) runs a truncated capture again with the rows it needs.
         ASK and FSK; PSK, auto_center, auto_noise, msg_records and dc_correction are not options of a batch (ValueError says what to call:
-        for a noise threshold per capture, iq_to_bits_batch_auto)."""
+        for a noise threshold per capture, iq_to_bits_batch_auto; for the messages' records, iq_to_bits_batch_records)."""
         from .batch import iq_to_bits_batch
         return iq_to_bits_batch(self, captures, p, want_qad, cap_rows, long_from, **options)
 
@@ -923,6 +923,26 @@ class DevicePipeline:
         ASK and FSK; PSK, msg_records and dc_correction are not options of a batch (ValueError says what to call)."""
         from .batch import iq_to_bits_batch_center
         return iq_to_bits_batch_center(self, captures, p, auto_noise, center_max_size, want_qad, cap_rows, long_from, **options)
+
+    def iq_to_bits_batch_records(self, captures, p: DemodParams, message_length_divisor=1, auto_noise=False, auto_center=False, center_max_size=None,
+                                 want_qad=False, cap_rows=None, long_from=None, **options):
+        """A batch that ends with its MESSAGES, as iq_to_bits(..., msg_records=True) ends a pass: the matching batch -- iq_to_bits_batch,
+        iq_to_bits_batch_auto (auto_noise) or iq_to_bits_batch_center (auto_center, with or without auto_noise) -- and, queued behind its
+        walk, one record per message of every capture (include/urhgpu.h "a batch of captures: message records per capture"): the ASK padding
+        to message_length_divisor, the first and the middle bit's position derived from the pulse table on the device, and the RSSI over one
+        symbol at the middle bit, its window clipped at the end of its OWN capture.  Three launches and one copy more than the batch,
+        whatever the number of captures and of messages; as many again when centers left to the host make a second slicing.
+        captures, want_qad, cap_rows, long_from, center_max_size: as for those methods; a capture of long_from samples or more goes through
+        iq_to_bits(..., msg_records=True, message_length_divisor=...).
+        Returns a batch.BatchBits whose HostBits carry .records (protocol.RECORD_DTYPE) and answer .message_data(sample_rate, timestamp);
+        BatchBits.message_data(k, ...) and .messages(sample_rate, timestamps) hand out the lists of protocol.MessageData.  Capture k equals,
+        record for record, iq_to_bits(capture_k, p, auto_noise=..., auto_center=..., msg_records=True, message_length_divisor=...) on it
+        alone; the RSSI bit for bit.  A truncated capture's message_data() raises the capacity error; .retry(k) runs it again with records.
+        A noise flag 2 capture is sliced as two zeros and its records, if any, read the real capture; noise flag 0 raises where the capture
+        is handed out.  ASK and FSK; PSK and dc_correction are not options of a batch (ValueError says what to call)."""
+        from .batch import iq_to_bits_batch_records
+        return iq_to_bits_batch_records(self, captures, p, message_length_divisor, auto_noise, auto_center, center_max_size, want_qad, cap_rows, long_from,
+                                        **options)
 
     def detect_centers(self, captures, max_size=None):
         """AutoInterpretation.detect_center of every capture of a batch of DEMODULATED signals, captures = (qad_cat, starts) with capture k =

@@ -129,6 +129,19 @@ def get_protocol_from_signal_dev(pipe, iq, p, message_length_divisor=1, sample_r
     return res.message_data(sample_rate, timestamp)
 
 
+def get_protocols_from_signals_dev(pipe, captures, p, message_length_divisor=1, sample_rate=1e6, timestamps=None, auto_noise=False, auto_center=False,
+                                   center_max_size=None, cap_rows=None, long_from=None):
+    """get_protocol_from_signal_dev for a recording session: captures as DevicePipeline.iq_to_bits_batch takes them (a list of numpy arrays
+    or device tensors, or (iq_cat, starts)), one parameter set for all.  One batch with its records queued behind it
+    (DevicePipeline.iq_to_bits_batch_records); a capture whose pulse table outgrew its capacity is run once more with the rows it needs.
+    timestamps: one per capture, default 0.0.  Returns a list of MessageData lists, one per capture in the order given."""
+    res = pipe.iq_to_bits_batch_records(captures, p, message_length_divisor, auto_noise=auto_noise, auto_center=auto_center, center_max_size=center_max_size,
+                                        cap_rows=cap_rows, long_from=long_from)
+    for k in res.truncated:
+        res.retry(k)
+    return res.messages(sample_rate, timestamps)
+
+
 def messages_from_bits(pipe, iq, p, bit_data, pauses, bit_sample_pos, message_length_divisor=1, sample_rate=1e6, timestamp=0.0):
     """The per-message part of get_protocol_from_signal (:256-283) for bits that are already on the host."""
     torch = pipe.torch
