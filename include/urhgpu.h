@@ -1277,6 +1277,46 @@ int urhgpu_batch_msg_records_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t tota
                                  int64_t *d_rec_dir, void *d_rec, int64_t cap_rec, int32_t *d_rec_capture);
 int urhgpu_batch_records_fetch(urhgpu_ctx *ctx, const void *d_rec, int64_t n_rec, int64_t cap_rec, void *h_rec);
 
+/* ---- a batch of captures: message ranges per capture ------------------------------------------------------------------------------
+ * Every batch entry point above takes finished parameters.  The reference learns modulation, samples per symbol and tolerance when it opens
+ * a file (AutoInterpretation.estimate, AutoInterpretation.py:373-470), and that starts with the capture's message ranges:
+ * auto_interpretation.segment_messages_from_magnitudes (auto_interpretation.pyx:55-111).  Here the ranges of all K captures of a batch come
+ * out of three launches; capture c's pairs are those of urhgpu_message_ranges_dev (merge off) on that capture alone with ITS threshold.
+ *   urhgpu_batch_segments_dev      asynchronous on the context's stream, the caller owns all memory, nothing is copied or waited for.
+ *            d_iq, total, d_start, d_plan, k: as for urhgpu_iq_to_bits_batch_dev (of the plan only the launch order is read).  dtype: the
+ *            sample type.  d_thr: float[k], capture c's noise threshold; a sample is above the noise where double(magnitude) > double(thr)
+ *            -- the magnitude as util.get_magnitudes gives it for the sample type --, so a NaN threshold yields no segment.
+ *            THREE launches whatever k and the lengths are:
+ *              segments    a wavefront per capture, a step of urhgpu_batch_step() samples; the state of sample 0, conseq_above and
+ *                          conseq_below with outlier_tolerance = 10, a segment opened at i - conseq_above and closed at i - conseq_below,
+ *                          the trailing rule state == 1 and start < N - conseq_below -- followed over the runs of the step's above-noise
+ *                          mask.  Capture c's (start, end) int64 pairs, relative to its first sample, go to ITS region
+ *                          d_seg[2 d_region[c] ..) of urhgpu_batch_segments_capacity(n_c) = n_c / 20 + 1 pairs (a segment needs ten samples
+ *                          to open and ten to close: the capacity cannot truncate); d_counts[c] = the exact number of its segments.  Every
+ *                          store is bounded by the capacity; a region that does not lie inside [0, cap_seg) pairs stores nothing.  No load
+ *                          leaves [d_start[c], d_start[c + 1]); a refused start or end (outside [0, total], descending) is an empty capture.
+ *              directory   d_dir: int64[k + 1], the exclusive prefix of the captures' stored segments; d_dir[k] = M
+ *              compaction  d_out: the stored pairs of all captures in capture order, capture c's at d_out[2 d_dir[c] ..); pairs beyond cap_out
+ *                          are not written
+ *            d_seg, d_out: 16-byte aligned.  Rejected before anything is launched (and without a GPU): a sample type: URHGPU_ERR_DTYPE; a
+ *            negative size, a misaligned pointer, a missing context or buffer: URHGPU_ERR_ARG.
+ *   urhgpu_batch_segments_fetch    synchronous: ONE copy of the directory into h_dir, then ONE copy of the M pairs into h_out (none for
+ *            M = 0).  *n_segments = M.  M > cap_host (pairs): URHGPU_ERR_CAPACITY, the directory has been read.
+ *   urhgpu_batch_demod_dev         the demodulation launch of urhgpu_iq_to_bits_batch_center_dev alone: afp_demod of every capture into
+ *            d_qad[total] (the rules of sample 0 and of n <= 2 per capture; a sample's predecessor is never the neighbouring capture's).
+ *            d_noise: NULL -- every capture gated with p->noise_threshold --, or urhgpu_noise_result[k]: capture c gated with block c's
+ *            noise_sqrd; a block with flag 2 writes two zeros and nothing else, as in that pass.  ONE launch.
+ * urhgpu_batch_launches counts these too: 3 launches per urhgpu_batch_segments_dev, 1 per urhgpu_batch_demod_dev, and 2 copies per
+ * urhgpu_batch_segments_fetch (1 when M = 0), whatever k, the lengths and M are. */
+int64_t urhgpu_batch_segments_capacity(int64_t n);
+int urhgpu_batch_segments_dev(urhgpu_ctx *ctx, const void *d_iq, int dtype, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k,
+                              const float *d_thr, const int64_t *d_region, int64_t *d_seg, int64_t cap_seg, int64_t *d_counts, int64_t *d_dir,
+                              int64_t *d_out, int64_t cap_out);
+int urhgpu_batch_segments_fetch(urhgpu_ctx *ctx, const int64_t *d_dir, int64_t k, const int64_t *d_out, int64_t *h_dir, int64_t *h_out,
+                                int64_t cap_host, int64_t *n_segments);
+int urhgpu_batch_demod_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k,
+                           const urhgpu_params *p, const urhgpu_noise_result *d_noise, float *d_qad);
+
 #ifdef __cplusplus
 }
 #endif

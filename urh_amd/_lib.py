@@ -251,6 +251,10 @@ PROTOTYPES = {
     "urhgpu_batch_center_fetch": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, C.POINTER(_i64)]),
     "urhgpu_batch_msg_records_dev": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "urhgpu_batch_records_fetch": (_i, [_vp, _vp, _i64, _i64, _vp]),
+    "urhgpu_batch_segments_capacity": (_i64, [_i64]),
+    "urhgpu_batch_segments_dev": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64]),
+    "urhgpu_batch_segments_fetch": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
+    "urhgpu_batch_demod_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _vp, _vp]),
 }
 
 _lib = None

@@ -21,6 +21,11 @@ alone, qad_to_bits_batch the walk alone.
 DevicePipeline.iq_to_bits_batch_records ends any of the three with the session's MESSAGES: one record per message (RSSI, first position,
 ASK padding) queued behind the walk for all captures at once (urh_amd/csrc/batch_records.hip) -- three more launches and one more copy,
 whatever the number of captures and of messages.  BatchBits.messages() is then what ProtocolAnalyzer.get_protocol_from_signal builds per file.
+
+DevicePipeline.estimate_batch stands in front of all of them: AutoInterpretation.estimate of every capture -- modulation, samples per symbol,
+center, tolerance, noise --, with the captures' message ranges from three launches (urh_amd/csrc/batch_estimate.hip: a wavefront per capture
+follows segment_messages_from_magnitudes) and the messages of all captures pooled through the native calls estimators.estimate_dev makes for one
+capture.  segment_messages_batch is the segmentation alone.
 """
 import ctypes as C
 from dataclasses import replace
@@ -643,13 +648,12 @@ def qad_to_bits_batch(pipe, captures, p, centers=None, cap_rows=None, _pool=None
     return BatchBits(items, p, np.diff(starts), qads, rerun, centers=None if centers is None else list(centers))
 
 
-def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, center=None, records=None):
-    """iq_to_bits_batch, iq_to_bits_batch_auto, iq_to_bits_batch_center and iq_to_bits_batch_records (records: the message_length_divisor):
-    the input forms, the routing by length, the result sequence"""
+def _batch_input(pipe, captures):
+    """the three input forms of a batch -- a list of (N, 2) / complex64 numpy arrays, a list of device tensors, (iq_cat, starts) with a numpy
+    array or a device tensor -- as (captures, on the device?, given packed?, iq_cat, starts, numpy sample type, lengths)"""
     torch = pipe.torch
-    long_from = LONG_FROM_DEFAULT if long_from is None else int(long_from)
-    pool = pipe._pinned if _pool is None else _pool
     from .pipeline import _torch_dtype
+    cat = starts_in = None
     packed = isinstance(captures, tuple) and len(captures) == 2 and not isinstance(captures[0], (list, tuple))
     if packed:
         cat, starts_in = captures
@@ -678,6 +682,16 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, 
         raise ValueError("the captures of a batch share one sample type")
     npdt = np.dtype(dts.pop()) if dts else np.dtype(np.float32)
     lengths = [int(c.shape[0]) for c in caps]
+    return caps, on_device, packed, cat, starts_in, npdt, lengths
+
+
+def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, center=None, records=None):
+    """iq_to_bits_batch, iq_to_bits_batch_auto, iq_to_bits_batch_center and iq_to_bits_batch_records (records: the message_length_divisor):
+    the input forms, the routing by length, the result sequence"""
+    torch = pipe.torch
+    long_from = LONG_FROM_DEFAULT if long_from is None else int(long_from)
+    pool = pipe._pinned if _pool is None else _pool
+    caps, on_device, packed, cat, starts_in, npdt, lengths = _batch_input(pipe, captures)
     short, long_ = route(lengths, long_from)
     items = [None] * len(caps)
     qads = [None] * len(caps) if want_qad else None
@@ -765,3 +779,289 @@ def launch_counts(pipe):
     out = (C.c_int64 * 2)()
     _lib.check(_lib.load().urhgpu_batch_launches(pipe.ctx.handle, out))
     return int(out[0]), int(out[1])
+
+
+# ---- the estimate of a session: every capture's parameters (include/urhgpu.h "a batch of captures: message ranges per capture") ------------
+# messages whose centers and plateau decisions go through one native call: urhgpu_msg_estimate refuses (URHGPU_ERR_UNSUPPORTED) more than
+# 64 MiB of histogram pool, 4096 counters of 4 bytes per message
+MSG_GROUP = 4096
+
+_ESTIMATE_MODULATIONS = ("OOK", "ASK", "FSK", "PSK")
+# estimators.estimate_dev agrees with the reference on these sample types here (tests/test_gpu_parity.py); uint8 and uint16 are not covered
+# by such a test, so a session of them is refused instead of estimated unchecked
+ESTIMATE_SAMPLE_TYPES = (np.float32, np.int8, np.int16)
+
+
+def per_capture(value, k, name, check=None):
+    """an option given once for all captures or once per capture, as a list of k entries (host arithmetic)"""
+    if value is None or isinstance(value, (str, int, float, np.floating, np.integer)):
+        out = [value] * k
+    else:
+        out = list(value)
+        if len(out) != k:
+            raise ValueError(f"{name} holds one entry per capture ({k}), or is one value for all")
+    if check is not None:
+        for v in out:
+            check(v)
+    return out
+
+
+def check_estimate_options(k, npdt, noise, modulation):
+    """(noise per capture, modulation per capture) of estimate_batch, or ValueError with a sentence (host arithmetic: no GPU needed)"""
+    if np.dtype(npdt) not in [np.dtype(t) for t in ESTIMATE_SAMPLE_TYPES]:
+        raise ValueError(f"estimate_batch takes float32, int8 and int16 captures, not {np.dtype(npdt).name}: estimate_dev is not verified against the "
+                         "reference on that sample type")
+
+    def check_mod(m):
+        if m is not None and m not in _ESTIMATE_MODULATIONS:
+            raise ValueError("Unsupported Modulation")           # (what the reference raises, AutoInterpretation.py:394)
+    mods = per_capture(modulation, k, "modulation", check_mod)
+    noises = [None if v is None else float(v) for v in per_capture(noise, k, "noise")]
+    return noises, mods
+
+
+class BatchEstimates:
+    """The results of estimate_batch: a sequence with one entry per capture in the order given -- the dict estimators.estimate_dev returns
+    (modulation_type, bit_length, center, tolerance, noise), or None.  A capture for which the reference raises (detect_noise_level on a
+    capture whose magnitudes hold a NaN or an infinity) raises the same exception where it is handed out, as BatchBits does; the others are
+    handed out."""
+
+    def __init__(self, items, errors, lengths):
+        self._items, self._errors = list(items), list(errors)
+        self.lengths = [int(n) for n in lengths]
+
+    def __len__(self):
+        return len(self._items)
+
+    def _hand_out(self, k):
+        if self._errors[k] is not None:
+            raise self._errors[k]
+        return self._items[k]
+
+    def __getitem__(self, k):
+        if isinstance(k, slice):
+            return [self._hand_out(i) for i in range(*k.indices(len(self._items)))]
+        return self._hand_out(range(len(self._items))[k])
+
+    def __iter__(self):
+        return (self._hand_out(k) for k in range(len(self._items)))
+
+
+class _Session:
+    """the short captures of a session on the device: the samples back to back, their starts, the plan's launch order and the regions of
+    the segmentation, uploaded with ONE copy"""
+
+    def __init__(self, pipe, pool, caps, lengths, npdt, device_iq=None, device_starts=None):
+        torch = self.torch = pipe.torch
+        from .pipeline import DemodParams
+        self.pipe, self.pool, self.npdt = pipe, pool, np.dtype(npdt)
+        k = self.k = len(lengths)
+        self.lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        p = DemodParams("FSK", 1, 0.0, 0.0, 1.0, 5, 100, 0.1, 8, False)            # (of the plan only the launch order is read)
+        plan, _, _ = batch_plan(self.lengths, p.to_c(self.npdt))
+        starts = np.zeros(k + 1, np.int64)
+        np.cumsum(self.lengths, out=starts[1:])
+        if device_starts is not None:
+            starts = np.asarray(device_starts, dtype=np.int64)
+        self.starts = starts
+        self.total = int(starts[-1]) if device_iq is None else int(device_iq.shape[0])
+        self.seg_caps = self.lengths // 20 + 1                                      # urhgpu_batch_segments_capacity
+        regions = np.zeros(k + 1, np.int64)
+        np.cumsum(self.seg_caps, out=regions[1:])
+        self.cap_seg = int(regions[-1])
+        item = 2 * self.npdt.itemsize
+        n_meta = 5 * k + 1
+        self.meta_bytes = (8 * n_meta + _META_ALIGN - 1) // _META_ALIGN * _META_ALIGN
+        in_bytes = self.meta_bytes + (self.total * item if device_iq is None else 0)
+        stage = _pinned(torch, pool, "estimate_stage", in_bytes)
+        view = stage.numpy()
+        meta = view[:8 * n_meta].view(np.int64)
+        meta[:k + 1] = starts
+        meta[k + 1:4 * k + 1] = plan
+        meta[4 * k + 1:] = regions[:-1]
+        if device_iq is None:
+            for a, s in zip(caps, starts[:-1]):
+                if len(a):
+                    view[self.meta_bytes + int(s) * item: self.meta_bytes + (int(s) + len(a)) * item] = a.reshape(-1).view(np.uint8)
+        pipe.ctx.set_stream(torch.cuda.current_stream(pipe.device).cuda_stream)
+        self.dev_in = pipe._buf("estimate:in", (max(in_bytes, 16),), torch.uint8)
+        self.dev_in[:in_bytes].copy_(stage[:in_bytes], non_blocking=True)          # THE upload: starts, plan, regions and every sample in one copy
+        self.d_start = self.dev_in.data_ptr()
+        self.d_plan = self.d_start + 8 * (k + 1)
+        self.d_region = self.d_start + 8 * (4 * k + 1)
+        if device_iq is None:
+            from .iq_array import _torch_dtype_for
+            self.iq = self.dev_in[self.meta_bytes:self.meta_bytes + self.total * item].view(_torch_dtype_for(self.npdt)).reshape(self.total, 2)
+        else:
+            self.iq = device_iq
+        self.cp = p.to_c(self.npdt)
+
+    def upload_noise(self, noise):
+        """the captures' thresholds as the kernels read them, ONE copy: float[k] for the segmentation ((float)noise, afp_demod's and
+        segment_messages_from_magnitudes' `float` argument) and urhgpu_noise_result[k] for the demodulation -- flag 1 and the DETECTED value
+        whatever Signal.max_magnitude says: the estimate never asks (k_batch_noise's own blocks carry the configured threshold for flag 2)"""
+        torch, k = self.torch, self.k
+        thr_bytes = (4 * k + 15) // 16 * 16
+        nbytes = thr_bytes + C.sizeof(_lib.NoiseResult) * max(k, 1)
+        stage = _pinned(torch, self.pool, "estimate_noise_stage", nbytes)
+        view = stage.numpy()
+        view[:nbytes] = 0
+        thr = view[:4 * k].view(np.float32)
+        with np.errstate(all="ignore"):
+            thr[:] = np.asarray(noise, dtype=np.float64).astype(np.float32)
+            sq = thr * thr                                                          # an fp32 multiply
+        blocks = (_lib.NoiseResult * max(k, 1)).from_address(stage.data_ptr() + thr_bytes)
+        for i in range(k):
+            blocks[i].noise, blocks[i].noise_f32, blocks[i].noise_sqrd, blocks[i].flag = float(noise[i]), float(thr[i]), float(sq[i]), 1
+        dev = self.pipe._buf("estimate:noise_in", (nbytes,), torch.uint8)
+        dev.copy_(stage[:nbytes], non_blocking=True)
+        self.d_thr, self.d_noise_blocks = dev.data_ptr(), dev.data_ptr() + thr_bytes
+
+    def detect_noise(self):
+        """AutoInterpretation.detect_noise_level of every capture: k_batch_noise and one read of the K blocks -> (values, flags)"""
+        torch, k, lib = self.torch, self.k, _lib.load()
+        d_noise = self.pipe._buf("batch:noise", (C.sizeof(_lib.NoiseResult) * max(k, 1),), torch.uint8)
+        _lib.check(lib.urhgpu_batch_noise_dev(self.pipe.ctx.handle, C.c_void_p(self.iq.data_ptr()), self.total, C.c_void_p(self.d_start), C.c_void_p(self.d_plan),
+                                              k, C.byref(self.cp), C.c_void_p(d_noise.data_ptr())))
+        h = _pinned(torch, self.pool, "batch_noise", C.sizeof(_lib.NoiseResult) * max(k, 1))
+        _lib.check(lib.urhgpu_batch_noise_fetch(self.pipe.ctx.handle, C.c_void_p(d_noise.data_ptr()), k, C.c_void_p(h.data_ptr())))
+        blocks = (_lib.NoiseResult * k).from_address(h.data_ptr())
+        return [float(r.noise) for r in blocks], [int(r.flag) for r in blocks]
+
+    def segments(self):
+        """urhgpu_batch_segments_dev and its fetch with the thresholds uploaded last: three launches and two copies -> one int64 (n, 2) array
+        per capture, relative to the capture's first sample"""
+        torch, k, lib, pipe = self.torch, self.k, _lib.load(), self.pipe
+        cap = max(self.cap_seg, 1)
+        seg = pipe._buf("estimate:seg", (2 * cap,), torch.int64)
+        out = pipe._buf("estimate:seg_out", (2 * cap,), torch.int64)
+        counts = pipe._buf("estimate:seg_counts", (max(k, 1),), torch.int64)
+        d_dir = pipe._buf("estimate:seg_dir", (k + 1,), torch.int64)
+        from .signal_functions import dtype_code
+        _lib.check(lib.urhgpu_batch_segments_dev(pipe.ctx.handle, C.c_void_p(self.iq.data_ptr()), dtype_code(self.npdt), self.total, C.c_void_p(self.d_start),
+                                                 C.c_void_p(self.d_plan), k, C.c_void_p(self.d_thr), C.c_void_p(self.d_region), C.c_void_p(seg.data_ptr()),
+                                                 self.cap_seg, C.c_void_p(counts.data_ptr()), C.c_void_p(d_dir.data_ptr()), C.c_void_p(out.data_ptr()), self.cap_seg))
+        h_dir = _pinned(torch, self.pool, "estimate_seg_dir", 8 * (k + 1))
+        h_out = _pinned(torch, self.pool, "estimate_seg_out", 16 * cap)
+        m = C.c_int64(0)
+        _lib.check(lib.urhgpu_batch_segments_fetch(pipe.ctx.handle, C.c_void_p(d_dir.data_ptr()), k, C.c_void_p(out.data_ptr()), C.c_void_p(h_dir.data_ptr()),
+                                                   C.c_void_p(h_out.data_ptr()), cap, C.byref(m)))
+        offs = h_dir.numpy()[:8 * (k + 1)].view(np.int64)
+        pairs = h_out.numpy()[:16 * int(m.value)].view(np.int64).reshape(-1, 2).copy()
+        return [pairs[int(offs[i]):int(offs[i + 1])] for i in range(k)]
+
+    def demod(self, mod):
+        """urhgpu_batch_demod_dev: afp_demod(capture, its noise, mod) of every capture into one float32 device tensor -- one launch"""
+        from .pipeline import DemodParams
+        torch, pipe = self.torch, self.pipe
+        cp = DemodParams(mod, 1, 0.0, 0.0, 1.0, 5, 100, 0.1, 8, False).to_c(self.npdt)
+        qad = pipe._buf("estimate:qad_" + mod, (max(self.total, 1),), torch.float32)
+        _lib.check(_lib.load().urhgpu_batch_demod_dev(pipe.ctx.handle, C.c_void_p(self.iq.data_ptr()), self.total, C.c_void_p(self.d_start), C.c_void_p(self.d_plan),
+                                                      self.k, C.byref(cp), C.c_void_p(self.d_noise_blocks), C.c_void_p(qad.data_ptr())))
+        return qad
+
+
+def _session(pipe, pool, caps, lengths, npdt, on_device, packed, cat, starts_in, whole):
+    """the captures `caps` as a _Session; a packed device tensor that is taken whole is read where it lies"""
+    torch = pipe.torch
+    if not on_device:
+        return _Session(pipe, pool, caps, lengths, npdt)
+    if packed and whole and cat.is_contiguous():
+        return _Session(pipe, pool, None, lengths, npdt, device_iq=cat, device_starts=starts_in)
+    from .iq_array import _torch_dtype_for
+    dev_cat = torch.cat(caps) if caps else torch.empty((0, 2), dtype=_torch_dtype_for(npdt), device=pipe.device)
+    return _Session(pipe, pool, None, lengths, npdt, device_iq=dev_cat.contiguous())
+
+
+def segment_messages_batch(pipe, captures, noise, _pool=None):
+    """DevicePipeline.segment_messages_batch (see there)"""
+    pool = pipe._pinned if _pool is None else _pool
+    caps, on_device, packed, cat, starts_in, npdt, lengths = _batch_input(pipe, captures)
+    noises = [float(v) for v in per_capture(noise, len(caps), "noise")]
+    s = _session(pipe, pool, caps, lengths, npdt, on_device, packed, cat, starts_in, True)
+    s.upload_noise(noises)
+    return s.segments()
+
+
+def estimate_batch(pipe, captures, noise=None, modulation=None, long_from=None, _pool=None):
+    """DevicePipeline.estimate_batch (see there)"""
+    from . import estimators as E
+    from .pipeline import raise_noise_error
+    torch = pipe.torch
+    pool = pipe._pinned if _pool is None else _pool
+    long_from = LONG_FROM_DEFAULT if long_from is None else int(long_from)
+    caps, on_device, packed, cat, starts_in, npdt, lengths = _batch_input(pipe, captures)
+    k_all = len(caps)
+    noises, mods = check_estimate_options(k_all, npdt, noise, modulation)
+    items, errors = [None] * k_all, [None] * k_all
+
+    def alone(i):
+        """capture i through estimate_dev: a long capture, or PSK -- a batch has no Costas loop"""
+        c = caps[i]
+        t = c if on_device else torch.from_numpy(c).to(pipe.device)
+        try:
+            items[i] = E.estimate_dev(pipe, t.contiguous(), noise=noises[i], modulation=mods[i])
+        except (ValueError, OverflowError) as e:              # what the reference raises for this capture: raised where it is handed out
+            errors[i] = e
+
+    by_length, long_ = route(lengths, long_from)
+    short = [int(i) for i in by_length if mods[i] != "PSK"]
+    for i in sorted([int(i) for i in long_] + [int(i) for i in by_length if mods[i] == "PSK"]):
+        alone(i)
+    k = len(short)
+    if k == 0:
+        return BatchEstimates(items, errors, lengths)
+    s = _session(pipe, pool, [caps[i] for i in short], [lengths[i] for i in short], npdt, on_device, packed, cat, starts_in, k == k_all)
+
+    # 1. noise: detected per capture (one launch, one read), or given
+    value = [noises[i] for i in short]
+    if any(v is None for v in value):
+        found, flags = s.detect_noise()
+        for j in range(k):
+            if value[j] is None:
+                value[j] = found[j]
+                if flags[j] == 0:                                 # math.ceil of a NaN / an infinity: the reference raises
+                    try:
+                        raise_noise_error(found[j])
+                    except (ValueError, OverflowError) as e:
+                        errors[short[j]] = e
+                    value[j] = float("nan")                       # (nothing is above a NaN: no segment, no message)
+    s.upload_noise(value)
+
+    # 2. segmentation; 3. the OOK merge per capture on the host (a short capture has a few dozen pulses)
+    segs = s.segments()
+    live = [j for j in range(k) if errors[short[j]] is None and len(segs[j])]
+
+    # 4. the modulation vote: ONE call over the first 100 ranges of every capture that needs it
+    mod_of = [mods[i] for i in short]
+    need = [j for j in live if mod_of[j] is None]
+    if need:
+        ranges = np.concatenate([segs[j][:100] + s.starts[j] for j in need])
+        labels = E.detect_modulation_dev(pipe, s.iq, ranges)      # (an integer session: iq_array.convert_to once, inside)
+        at = 0
+        for j in need:
+            n = min(len(segs[j]), 100)
+            mod_of[j] = E.most_common_label(labels[at:at + n])
+            at += n
+    for j in live:
+        if mod_of[j] == "PSK":                                    # detected: alone, as estimate_dev detects and estimates it
+            alone(short[j])
+    msgs = {j: (E.merge_message_segments_for_ook(segs[j]) if mod_of[j] == "OOK" else segs[j]) for j in live if mod_of[j] in ("OOK", "ASK", "FSK")}
+
+    # 5. demodulation, once per modulation group present; 6. the decisions of ALL messages of a group, pooled as global ranges, in chunks
+    # that fit the histogram pool; then the votes per capture
+    for group in (("OOK", "ASK"), ("FSK",)):
+        members = [j for j in sorted(msgs) if mod_of[j] in group]
+        if not members:
+            continue
+        qad = s.demod("ASK" if group[0] == "OOK" else "FSK")
+        pooled = np.concatenate([msgs[j] + s.starts[j] for j in members]).astype(np.int64)
+        parts = [E.message_decisions(pipe, qad, pooled[a:a + MSG_GROUP]) for a in range(0, len(pooled), MSG_GROUP)]
+        center_of, tol_of, len_of = (np.concatenate([p[i] for p in parts]) for i in range(3))
+        at = 0
+        for j in members:
+            n = len(msgs[j])
+            noise_j = noises[short[j]] if noises[short[j]] is not None else value[j]
+            items[short[j]] = E.vote_on_messages(mod_of[j], noise_j, center_of[at:at + n], tol_of[at:at + n], len_of[at:at + n])
+            at += n
+    return BatchEstimates(items, errors, lengths)

@@ -138,17 +138,8 @@ int batch_check_params(const urhgpu_params *p) {
     return URHGPU_OK;
 }
 
-// the argument checks of urhgpu_iq_to_bits_batch_dev and the two argument blocks of its launches (shared with batch_auto.hip)
-int batch_setup(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k, const urhgpu_params *p,
-                float *d_qad, void *d_work, int64_t work_bytes, int64_t *d_counts, int64_t *d_dir, void *d_blob, int64_t cap_blob, RunArgs &a, BatchArgs &b) {
-    if (!ctx || k < 0 || k > INT32_MAX || total < 0 || work_bytes < 0 || cap_blob < 0 || !d_dir) return URHGPU_ERR_ARG;
-    URH_TRY(batch_check_params(p));
-    if (k > 0 && (!d_start || !d_plan || !d_counts)) return URHGPU_ERR_ARG;
-    if ((total > 0 && !d_iq) || (work_bytes > 0 && !d_work) || (cap_blob > 0 && !d_blob)) return URHGPU_ERR_ARG;
-    if (((uintptr_t)d_iq & 15) || ((uintptr_t)d_work & 15) || ((uintptr_t)d_blob & 15) || ((uintptr_t)d_qad & 3)) return URHGPU_ERR_ARG;
-    if (((uintptr_t)d_start & 7) || ((uintptr_t)d_plan & 7) || ((uintptr_t)d_counts & 7) || ((uintptr_t)d_dir & 7)) return URHGPU_ERR_ARG;
-    URH_HIP(hipSetDevice(ctx->device));
-    URH_TRY(join_tail(ctx));
+// the demodulation's argument block from the parameters of a batch (p has passed batch_check_params)
+void batch_run_args(const urhgpu_params *p, RunArgs &a) {
     memset(&a, 0, sizeof(a));
     a.order = 1 << p->bits_per_symbol;
     urhgpu_get_center_thresholds(p->center, p->center_spacing, a.order, a.thr);
@@ -162,6 +153,20 @@ int batch_setup(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t 
         case URHGPU_DT_U16: a.max_magnitude = (float)sqrt(4294836225.0); break;
         default: a.max_magnitude = (float)sqrt(2.0); break;
     }
+}
+
+// the argument checks of urhgpu_iq_to_bits_batch_dev and the two argument blocks of its launches (shared with batch_auto.hip)
+int batch_setup(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k, const urhgpu_params *p,
+                float *d_qad, void *d_work, int64_t work_bytes, int64_t *d_counts, int64_t *d_dir, void *d_blob, int64_t cap_blob, RunArgs &a, BatchArgs &b) {
+    if (!ctx || k < 0 || k > INT32_MAX || total < 0 || work_bytes < 0 || cap_blob < 0 || !d_dir) return URHGPU_ERR_ARG;
+    URH_TRY(batch_check_params(p));
+    if (k > 0 && (!d_start || !d_plan || !d_counts)) return URHGPU_ERR_ARG;
+    if ((total > 0 && !d_iq) || (work_bytes > 0 && !d_work) || (cap_blob > 0 && !d_blob)) return URHGPU_ERR_ARG;
+    if (((uintptr_t)d_iq & 15) || ((uintptr_t)d_work & 15) || ((uintptr_t)d_blob & 15) || ((uintptr_t)d_qad & 3)) return URHGPU_ERR_ARG;
+    if (((uintptr_t)d_start & 7) || ((uintptr_t)d_plan & 7) || ((uintptr_t)d_counts & 7) || ((uintptr_t)d_dir & 7)) return URHGPU_ERR_ARG;
+    URH_HIP(hipSetDevice(ctx->device));
+    URH_TRY(join_tail(ctx));
+    batch_run_args(p, a);
     b.iq = d_iq; b.start = d_start; b.plan = d_plan; b.k = k; b.total = total; b.qad = d_qad;
     b.work = (char *)d_work; b.work_bytes = work_bytes; b.counts = d_counts; b.dir = d_dir; b.blob = (char *)d_blob; b.cap_blob = cap_blob;
     b.pause_threshold = p->pause_threshold; b.sps = p->samples_per_symbol; b.bps = p->bits_per_symbol; b.tol = p->tolerance;

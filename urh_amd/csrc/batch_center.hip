@@ -261,6 +261,28 @@ int urhgpu_iq_to_bits_batch_center_dev(urhgpu_ctx *ctx, const void *d_iq, int64_
     return URHGPU_OK;
 }
 
+int urhgpu_batch_demod_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k,
+                           const urhgpu_params *p, const urhgpu_noise_result *d_noise, float *d_qad) {
+    if (!ctx || k < 0 || k > INT32_MAX || total < 0) return URHGPU_ERR_ARG;
+    URH_TRY(batch_check_params(p));
+    if (k > 0 && (!d_start || !d_plan)) return URHGPU_ERR_ARG;
+    if ((total > 0 && (!d_iq || !d_qad)) || ((uintptr_t)d_iq & 15) || ((uintptr_t)d_qad & 3)) return URHGPU_ERR_ARG;
+    if (((uintptr_t)d_start & 7) || ((uintptr_t)d_plan & 7) || ((uintptr_t)d_noise & 7)) return URHGPU_ERR_ARG;
+    URH_HIP(hipSetDevice(ctx->device));
+    URH_TRY(join_tail(ctx));
+    RunArgs a;
+    BatchArgs b;
+    batch_run_args(p, a);
+    memset(&b, 0, sizeof(b));                              // no work buffer: batch_capture then vouches for the samples alone
+    b.iq = d_iq; b.start = d_start; b.plan = d_plan; b.k = k; b.total = total; b.qad = d_qad;
+    b.sps = p->samples_per_symbol; b.bps = p->bits_per_symbol; b.tol = p->tolerance;
+    a.d_noise = (const float *)d_noise;
+    URH_TRY(launch_batch_demod(a, b, p->dtype, p->mod, d_noise != nullptr, (unsigned)std::max<int64_t>(k, 1), ctx->stream));
+    ctx->batch_launches += 1;
+    URH_HIP(hipGetLastError());
+    return URHGPU_OK;
+}
+
 int urhgpu_batch_center_fetch(urhgpu_ctx *ctx, const void *d_result, int64_t k, const uint32_t *d_tie, int64_t cap_tie, void *h_result, uint32_t *h_tie,
                               int64_t cap_host, int64_t *used) {
     if (!ctx || k < 0 || !d_result || !h_result || cap_tie < 0 || cap_host < 0 || !used) return URHGPU_ERR_ARG;

@@ -323,6 +323,8 @@ __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchA
 // ---- host side, defined in batch.hip and shared with batch_auto.hip ----
 // the parameters a batch accepts (every entry point): ASK / FSK, the ranges of the other passes
 int batch_check_params(const urhgpu_params *p);
+// the demodulation's argument block from the parameters of a batch (p has passed batch_check_params)
+void batch_run_args(const urhgpu_params *p, RunArgs &a);
 // the argument checks of urhgpu_iq_to_bits_batch_dev and the two argument blocks of its launches
 int batch_setup(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k, const urhgpu_params *p,
                 float *d_qad, void *d_work, int64_t work_bytes, int64_t *d_counts, int64_t *d_dir, void *d_blob, int64_t cap_blob, RunArgs &a, BatchArgs &b);

@@ -393,7 +393,13 @@ def detect_modulation_for_messages_dev(iq, message_indices: list, pipe=None):
     if pipe is None:
         from .pipeline import DevicePipeline
         pipe = DevicePipeline(iq.device.index)
-    labels = [m for m in detect_modulation_dev(pipe, iq, list(message_indices[0:100])) if m is not None]
+    return most_common_label(detect_modulation_dev(pipe, iq, list(message_indices[0:100])))
+
+
+def most_common_label(labels):
+    """the vote of detect_modulation_for_messages (:208-223) over its messages' labels: the most common one that is not None; among equally
+    common labels the one that occurs first wins, as max() over the list does in the reference (:50-57).  None without a label."""
+    labels = [m for m in labels if m is not None]
     if not labels:
         return None
     votes = {}
@@ -603,6 +609,65 @@ def bit_lengths_batched(all_plateaus):
     return _bit_lengths_raw(lens, off, lambda m: all_plateaus[m])
 
 
+def message_decisions(pipe, data, message_indices):
+    """The middle of estimate_dev -- and of batch.estimate_batch, which hands it the messages of MANY captures as ranges into their
+    concatenated demodulated signal: (center float64 with NaN = none, tolerance int64 with -1 = none, bit length int64 with -1 = none) of
+    every message.  Centers and plateau decisions come from ONE native call (centers_and_decisions; round 5: two until then, with the
+    centers crossing PCIe twice in between); a message whose first plateau outlasts the search window (-3) sends all messages through the
+    per-message path, one whose decision hangs on numpy's order of equal histogram counts (-2) is decided by numpy."""
+    ranges = np.ascontiguousarray(message_indices, dtype=np.int64).reshape(-1, 2)
+    x32 = _dev_f32(pipe, data)
+    center_of, tol_raw, bl_raw = centers_and_decisions(pipe, x32, ranges, 25)
+    has_center = center_of == center_of
+    if (tol_raw == -3).any():                        # a message whose first plateau outlasts the search window: the per-message path
+        all_centers = [None if c != c else np.float64(c) for c in center_of.tolist()]
+        decisions = bit_lengths_batched(plateau_lengths_batched(pipe, data, message_indices, all_centers))
+        tol_of = np.array([-1 if t is None else t for t, _ in decisions], dtype=np.int64)
+        len_of = np.array([-1 if b is None else b for _, b in decisions], dtype=np.int64)
+    else:
+        tol_of, len_of = tol_raw.copy(), bl_raw.copy()
+        for m in np.nonzero((bl_raw == -2) | (tol_raw == -2))[0].tolist():      # numpy's order of equal histogram counts decides
+            t, b = _bit_length_with_numpy_order(
+                get_plateau_lengths_dev(pipe, x32[int(ranges[m, 0]):int(ranges[m, 1])], None if not has_center[m] else np.float64(center_of[m]), 25))
+            tol_of[m] = -1 if t is None else t
+            len_of[m] = -1 if b is None else b
+        tol_of[tol_of < 0] = -1
+        len_of[len_of < 0] = -1
+    return center_of, tol_of, len_of
+
+
+def vote_on_messages(modulation, noise, center_of, tol_of, len_of, lap=None):
+    """The tail of estimate_dev -- and of batch.estimate_batch, per capture on that capture's messages: the votes
+    (AutoInterpretation.py:407-470) on message_decisions' arrays.  A message with a center contributes its tolerance; it votes for a center
+    and a bit length when its merged plateaus gave a bit length above tolerance + 1.  Returns the estimate's dict, or None when no message
+    votes.  Host arithmetic on a few numbers per message."""
+    center_of, tol_of, len_of = np.asarray(center_of, dtype=np.float64), np.asarray(tol_of, dtype=np.int64), np.asarray(len_of, dtype=np.int64)
+    has_center = center_of == center_of
+    tolerances = tol_of[has_center & (tol_of >= 0)]
+    votes = has_center & (len_of >= 0) & (len_of > np.maximum(tol_of, 0) + 1)
+    if lap is not None:
+        lap("bit_lengths_host_ms")
+    if not votes.any():
+        return None
+    if modulation in ("OOK", "ASK"):
+        center = _inliers(center_of[votes], 2).min()         # min_without_outliers(centers, z=2)
+    else:
+        center = np.mean(center_of[votes])
+    bit_length = get_most_frequent_value(len_of[votes].tolist())
+    if len(tolerances):
+        # np.percentile(tolerances, 50) (:462), written out (numpy's own routine costs 60 us on a hundred values): linear interpolation
+        # between the two middle order statistics, in numpy's form b - (b - a) * (1 - t) for t >= 0.5; exact for these integers
+        v = np.sort(tolerances).astype(np.float64)
+        idx = 0.5 * (len(v) - 1)
+        lo, hi = int(np.floor(idx)), int(np.ceil(idx))
+        g = idx - lo
+        tolerance = v[lo] + (v[hi] - v[lo]) * g if g < 0.5 else v[hi] - (v[hi] - v[lo]) * (1.0 - g)
+    else:                                                # no message had a tolerance (np.percentile of an empty list: IndexError in the reference's numpy)
+        tolerance = max(1, int(0.05 * bit_length))
+    return {"modulation_type": "ASK" if modulation == "OOK" else modulation, "bit_length": bit_length, "center": center,
+            "tolerance": int(tolerance), "noise": noise}
+
+
 def estimate_dev(pipe, iq, noise: float = None, modulation: str = None, timings: dict = None, keep: dict = None):
     """AutoInterpretation.estimate (AutoInterpretation.py:373-470) for a float32 capture resident on the GPU: noise threshold,
     message ranges (segmentation + OOK merge on the device), modulation vote over the first 100 messages (device), demodulation, then
@@ -660,48 +725,6 @@ def estimate_dev(pipe, iq, noise: float = None, modulation: str = None, timings:
     if keep is not None:                             # the demodulated signal and what it was demodulated with: the caller's Signal.qad cache
         keep.update(qad=data, mod=mod, noise=float(noise))
     lap("afp_demod_ms")
-    # centers (float64, NaN = no center) and the plateau decisions of every message: ONE native call (round 5; two until then, with the
-    # centers crossing PCIe twice in between)
-    ranges = np.ascontiguousarray(message_indices, dtype=np.int64).reshape(-1, 2)
-    x32 = _dev_f32(pipe, data)
-    center_of, tol_raw, bl_raw = centers_and_decisions(pipe, x32, ranges, 25)
-    has_center = center_of == center_of
+    center_of, tol_of, len_of = message_decisions(pipe, data, message_indices)
     lap("centers_and_plateaus_ms")
-    if (tol_raw == -3).any():                        # a message whose first plateau outlasts the search window: the per-message path
-        all_centers = [None if c != c else np.float64(c) for c in center_of.tolist()]
-        decisions = bit_lengths_batched(plateau_lengths_batched(pipe, data, message_indices, all_centers))
-        tol_of = np.array([-1 if t is None else t for t, _ in decisions], dtype=np.int64)
-        len_of = np.array([-1 if b is None else b for _, b in decisions], dtype=np.int64)
-    else:
-        tol_of, len_of = tol_raw.copy(), bl_raw.copy()
-        for m in np.nonzero((bl_raw == -2) | (tol_raw == -2))[0].tolist():      # numpy's order of equal histogram counts decides
-            t, b = _bit_length_with_numpy_order(
-                get_plateau_lengths_dev(pipe, x32[int(ranges[m, 0]):int(ranges[m, 1])], None if not has_center[m] else np.float64(center_of[m]), 25))
-            tol_of[m] = -1 if t is None else t
-            len_of[m] = -1 if b is None else b
-        tol_of[tol_of < 0] = -1
-        len_of[len_of < 0] = -1
-    # the votes (AutoInterpretation.py:407-470) on arrays: a message with a center contributes its tolerance; it votes for a center and
-    # a bit length when its merged plateaus gave a bit length above tolerance + 1
-    tolerances = tol_of[has_center & (tol_of >= 0)]
-    votes = has_center & (len_of >= 0) & (len_of > np.maximum(tol_of, 0) + 1)
-    lap("bit_lengths_host_ms")
-    if not votes.any():
-        return None
-    if modulation in ("OOK", "ASK"):
-        center = _inliers(center_of[votes], 2).min()         # min_without_outliers(centers, z=2)
-    else:
-        center = np.mean(center_of[votes])
-    bit_length = get_most_frequent_value(len_of[votes].tolist())
-    if len(tolerances):
-        # np.percentile(tolerances, 50) (:462), written out (numpy's own routine costs 60 us on a hundred values): linear interpolation
-        # between the two middle order statistics, in numpy's form b - (b - a) * (1 - t) for t >= 0.5; exact for these integers
-        v = np.sort(tolerances).astype(np.float64)
-        idx = 0.5 * (len(v) - 1)
-        lo, hi = int(np.floor(idx)), int(np.ceil(idx))
-        g = idx - lo
-        tolerance = v[lo] + (v[hi] - v[lo]) * g if g < 0.5 else v[hi] - (v[hi] - v[lo]) * (1.0 - g)
-    else:                                                # no message had a tolerance (np.percentile of an empty list: IndexError in the reference's numpy)
-        tolerance = max(1, int(0.05 * bit_length))
-    return {"modulation_type": "ASK" if modulation == "OOK" else modulation, "bit_length": bit_length, "center": center,
-            "tolerance": int(tolerance), "noise": noise}
+    return vote_on_messages(modulation, noise, center_of, tol_of, len_of, lap)

@@ -883,7 +883,8 @@ class DevicePipeline:
         Returns a batch.BatchBits: a sequence of HostBits, each equal to what iq_to_bits gives for that capture alone; .qad(k) (want_qad)
         is capture k's slice of the demodulated signal on the device, .retry(k) runs a truncated capture again with the rows it needs.
         ASK and FSK; PSK, auto_center, auto_noise, msg_records and dc_correction are not options of a batch (ValueError says what to call:
-        for a noise threshold per capture, iq_to_bits_batch_auto; for the messages' records, iq_to_bits_batch_records)."""
+        for a noise threshold per capture, iq_to_bits_batch_auto; for the messages' records, iq_to_bits_batch_records).
+        p -- modulation, samples per symbol, tolerance, center -- where it is not known: estimate_batch gives it per capture."""
         from .batch import iq_to_bits_batch
         return iq_to_bits_batch(self, captures, p, want_qad, cap_rows, long_from, **options)
 
@@ -899,7 +900,8 @@ class DevicePipeline:
         HostBits is the reference's slicing of zeros(2), n_samples = 2.  Flag 0 -- the reference raises for that capture --: result[k],
         iteration at k and .check() raise the same exception (ValueError for a NaN, OverflowError for an infinity); every other capture is
         handed out.  .retry(k) runs a truncated capture again, alone, through this entry point: it detects the same threshold.
-        ASK and FSK; PSK, auto_center, msg_records and dc_correction are not options of a batch (ValueError says what to call)."""
+        ASK and FSK; PSK, auto_center, msg_records and dc_correction are not options of a batch (ValueError says what to call).
+        p where it is not known: estimate_batch gives it per capture."""
         from .batch import iq_to_bits_batch_auto
         return iq_to_bits_batch_auto(self, captures, p, auto_noise, want_qad, cap_rows, long_from, **options)
 
@@ -920,7 +922,8 @@ class DevicePipeline:
         settled to a center are sliced again by one more call; their HostBits replace the first ones.  With auto_noise, .noise and
         .noise_flags as for iq_to_bits_batch_auto: a noise flag 2 gives center None, center flag 0 and the slicing of two zeros with p.center;
         a noise flag 0 raises the reference's exception where that capture is handed out.
-        ASK and FSK; PSK, msg_records and dc_correction are not options of a batch (ValueError says what to call)."""
+        ASK and FSK; PSK, msg_records and dc_correction are not options of a batch (ValueError says what to call).
+        p where it is not known: estimate_batch gives it per capture."""
         from .batch import iq_to_bits_batch_center
         return iq_to_bits_batch_center(self, captures, p, auto_noise, center_max_size, want_qad, cap_rows, long_from, **options)
 
@@ -939,7 +942,8 @@ class DevicePipeline:
         record for record, iq_to_bits(capture_k, p, auto_noise=..., auto_center=..., msg_records=True, message_length_divisor=...) on it
         alone; the RSSI bit for bit.  A truncated capture's message_data() raises the capacity error; .retry(k) runs it again with records.
         A noise flag 2 capture is sliced as two zeros and its records, if any, read the real capture; noise flag 0 raises where the capture
-        is handed out.  ASK and FSK; PSK and dc_correction are not options of a batch (ValueError says what to call)."""
+        is handed out.  ASK and FSK; PSK and dc_correction are not options of a batch (ValueError says what to call).
+        p where it is not known: estimate_batch gives it per capture."""
         from .batch import iq_to_bits_batch_records
         return iq_to_bits_batch_records(self, captures, p, message_length_divisor, auto_noise, auto_center, center_max_size, want_qad, cap_rows, long_from,
                                         **options)
@@ -963,6 +967,32 @@ class DevicePipeline:
         """AutoInterpretation.detect_noise_level of every capture of a batch in ONE launch and one read (batch.detect_noise_levels)"""
         from .batch import detect_noise_levels
         return detect_noise_levels(self, captures)
+
+    def segment_messages_batch(self, captures, noise):
+        """auto_interpretation.segment_messages_from_magnitudes of every capture of a batch (the three input forms of iq_to_bits_batch), each
+        with its own noise threshold -- noise: one float, or one per capture --: three launches and two copies back whatever the number of
+        captures (include/urhgpu.h "a batch of captures: message ranges per capture").  Returns one int64 (n, 2) array per capture, equal to
+        estimators.segment_messages_dev(pipe, capture_k, noise_k, as_array=True)."""
+        from .batch import segment_messages_batch
+        return segment_messages_batch(self, captures, noise)
+
+    def estimate_batch(self, captures, noise=None, modulation=None, long_from=None):
+        """AutoInterpretation.estimate (AutoInterpretation.py:373-470) of EVERY capture of a session -- what the reference learns when it opens
+        each file, and the way to the DemodParams the four batch methods above take: entry k equals estimators.estimate_dev(pipe, capture_k,
+        noise_k, modulation_k).  The captures' messages are pooled: noise floors (k_batch_noise), message ranges (k_batch_segments), the
+        modulation vote, the demodulation (once per modulation present) and the center / tolerance / bit-length decisions each serve all
+        captures at once, and the number of native calls depends on ceil(messages / batch.MSG_GROUP), never on the number of captures.
+        captures: the three input forms of iq_to_bits_batch; float32, int8 and int16 samples (the types estimate_dev is verified on; uint8
+        and uint16 are refused with a ValueError).
+        noise: None -- detect_noise_level per capture --, one float, or one float (or None) per capture.  The estimate uses the value whatever
+        the sample type's max_magnitude is.
+        modulation: None -- a vote per capture over its first 100 messages --, "OOK", "ASK", "FSK", "PSK", or one of these (or None) per capture.
+        long_from: a capture of that many samples or more goes through estimate_dev alone and takes its place in the result; so does a
+        capture given or detected as PSK (a batch has no Costas loop).
+        Returns a batch.BatchEstimates: per capture the dict {modulation_type, bit_length, center, tolerance, noise}, or None; a capture for
+        which the reference raises (its noise level is a NaN or an infinity) raises the same exception where it is handed out."""
+        from .batch import estimate_batch
+        return estimate_batch(self, captures, noise, modulation, long_from)
 
     def iq_to_bits_checked(self, iq, p: DemodParams, want_qad=True, msg_records=False, message_length_divisor=1) -> BitsResult:
         """iq_to_bits with the output capacities verified (one 40-byte read-back) and, if the default capacities were

@@ -552,6 +552,10 @@ class Signal:
                                                      else self.modulation_type)
         keep = {}
         est = estimate_dev(self.pipe, self._iq, noise=None if detect_noise else self.noise_threshold, modulation=modulation, keep=keep)
+        return self._apply_estimate(est, keep, detect_modulation, detect_noise)
+
+    def _apply_estimate(self, est, keep, detect_modulation, detect_noise) -> bool:
+        """an estimate applied as Signal.auto_detect applies it (:537-577); keep: what estimate_dev left of its demodulation, or {}"""
         if est is None:
             return False
         if detect_noise:
@@ -650,3 +654,16 @@ class Signal:
         else:
             raise ValueError("could not broadcast the demodulated range into a cache of shape ({},)".format(int(self._qad.shape[0])))
         self._after_edit()
+
+
+def auto_detect_batch(signals, detect_modulation=True, detect_noise=False):
+    """Signal.auto_detect of every signal of a session from ONE DevicePipeline.estimate_batch over their captures (which share a sample
+    type): entry k is applied to signal k as auto_detect applies estimate_dev's result.  Returns the list of auto_detect's return values.
+    A signal for which the reference raises (its noise level is a NaN or an infinity) raises here, after the signals before it were set."""
+    signals = list(signals)
+    if not signals:
+        return []
+    modulation = [None if detect_modulation else ("OOK" if s.bits_per_symbol == 1 and s.modulation_type == "ASK" else s.modulation_type) for s in signals]
+    noise = [None if detect_noise else s.noise_threshold for s in signals]
+    found = signals[0].pipe.estimate_batch([s._iq for s in signals], noise=noise, modulation=modulation)
+    return [s._apply_estimate(est, {}, detect_modulation, detect_noise) for s, est in zip(signals, found)]
