@@ -1317,6 +1317,42 @@ int urhgpu_batch_segments_fetch(urhgpu_ctx *ctx, const int64_t *d_dir, int64_t k
 int urhgpu_batch_demod_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k,
                            const urhgpu_params *p, const urhgpu_noise_result *d_noise, float *d_qad);
 
+/* ---- a batch of captures: PSK, a Costas loop per capture in one launch ------------------------------------------------------------
+ * The Costas loop (costa_demod, signal_functions.pyx:252-330) is a serial recurrence: its cost is the latency of about 94 dependent
+ * instructions per sample.  A pass over one capture hides it by cutting a long capture into chunks and speculating on their start states; a
+ * short capture runs on one wavefront of the whole chip.  In a batch the parallelism is ACROSS captures: every capture starts in the known
+ * state {freq 0, phase 1.5}, nothing is speculated, and K loops run side by side -- a LANE per capture, a wavefront per 64 captures taken in
+ * the plan's launch order (urh_amd/csrc/batch_psk.hip).  The device time follows the LONGEST capture, not the number of captures.  Capture
+ * c's results are those of urhgpu_iq_to_bits_dev (with auto_noise / auto_center: urhgpu_iq_to_bits_auto_dev / _auto_center_dev) on that
+ * capture alone with PSK parameters, bit for bit.  The other batch entry points keep refusing PSK.
+ *   urhgpu_batch_costas_dev    the demodulation launch alone, asynchronous on the context's stream: afp_demod with PSK of every capture
+ *            into d_qad[total].  d_iq, total, d_start, d_plan, k: as for urhgpu_iq_to_bits_batch_dev (of the plan only the launch order
+ *            is read; a plan made for the same lengths, tolerance, samples per symbol and bits per symbol with the parameters recoded as
+ *            FSK serves).  Per capture: n <= 2 gives zeros(n); otherwise d_qad[s0] = -4 (the reference leaves that element unwritten) and the
+ *            loop runs from sample 1 in {freq 0, phase 1.5}; a sample with re * re + im * im <= noise_sqrd on its raw values gives -4 and
+ *            freezes the state; the state never crosses a capture boundary; a refused start or end reads and writes nothing.  d_noise: NULL
+ *            -- every capture gated with p->noise_threshold --, or urhgpu_noise_result[k]: capture c gated with block c's noise_sqrd; a
+ *            block with flag 2 writes two zeros and nothing else.  Loop order min(2 ^ bits_per_symbol, 4) (p->mod_order where > 0).  ONE
+ *            launch of ceil(k / 64) workgroups whatever the lengths are.  Rejected before anything is launched (and without a GPU):
+ *            anything but PSK and a loop order other than 2 / 4: URHGPU_ERR_UNSUPPORTED; a sample type: URHGPU_ERR_DTYPE; a negative
+ *            size, a misaligned pointer, a missing context or buffer: URHGPU_ERR_ARG.
+ *   urhgpu_iq_to_bits_batch_psk_dev   the whole pass: urhgpu_batch_noise_dev's launch when auto_noise is not 0, the Costas launch into
+ *            d_qad (required), -- when auto_center is not 0 -- the center chain and the publish step per group, the qad-input walk (its
+ *            FSK instantiation: the noise value is the same -4 and there is no ASK rule; without auto_center every capture is sliced with
+ *            p->center and d_scratch, d_thr, d_result, d_tie are not read), scan, pack.  4 launches (auto_noise: 5) without auto_center,
+ *            4 (5) + 14 n_groups with it: neither depends on k or the lengths.  Arguments and the flag protocol as for
+ *            urhgpu_iq_to_bits_batch_center_dev; fetched with urhgpu_batch_fetch, urhgpu_batch_noise_fetch and urhgpu_batch_center_fetch.
+ *            Records: urhgpu_batch_msg_records_dev behind it with the parameters recoded as FSK -- the record arithmetic reads the
+ *            modulation for the ASK padding alone.
+ * urhgpu_batch_launches counts these too: 1 launch per urhgpu_batch_costas_dev, the launches above per urhgpu_iq_to_bits_batch_psk_dev. */
+int urhgpu_batch_costas_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k,
+                            const urhgpu_params *p, const urhgpu_noise_result *d_noise, float *d_qad);
+int urhgpu_iq_to_bits_batch_psk_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k,
+                                    const urhgpu_params *p, int auto_noise, int auto_center, int64_t max_size, float *d_qad, void *d_work,
+                                    int64_t work_bytes, int64_t *d_counts, int64_t *d_dir, void *d_blob, int64_t cap_blob,
+                                    urhgpu_noise_result *d_noise, void *d_scratch, int64_t scratch_bytes, float *d_thr, int64_t cap_thr,
+                                    void *d_result, int64_t cap_result, uint32_t *d_tie, int64_t cap_tie);
+
 #ifdef __cplusplus
 }
 #endif

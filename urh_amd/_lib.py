@@ -255,6 +255,9 @@ PROTOTYPES = {
     "urhgpu_batch_segments_dev": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64]),
     "urhgpu_batch_segments_fetch": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
     "urhgpu_batch_demod_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _vp, _vp]),
+    "urhgpu_batch_costas_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _vp, _vp]),
+    "urhgpu_iq_to_bits_batch_psk_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _i, _i, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp,
+                                             _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
 }
 
 _lib = None

@@ -26,6 +26,12 @@ DevicePipeline.estimate_batch stands in front of all of them: AutoInterpretation
 center, tolerance, noise --, with the captures' message ranges from three launches (urh_amd/csrc/batch_estimate.hip: a wavefront per capture
 follows segment_messages_from_magnitudes) and the messages of all captures pooled through the native calls estimators.estimate_dev makes for one
 capture.  segment_messages_batch is the segmentation alone.
+
+DevicePipeline.iq_to_bits_batch_psk is the batch of PSK captures (urh_amd/csrc/batch_psk.hip): ONE launch runs the Costas loop of every
+capture -- a lane per capture, each from the known start state, nothing speculated -- into the demodulated buffer, and the route of
+iq_to_bits_batch_center goes on from there (the center chain only when asked for, the qad-input walk, the records) with the parameters
+recoded as FSK, whose noise value PSK shares.  The loop is serial: the device time follows the LONGEST capture of the batch, not their
+number.  costas_demod_batch is that launch alone.  The entry points above keep refusing PSK and name this one.
 """
 import ctypes as C
 from dataclasses import replace
@@ -38,7 +44,9 @@ from .signal_functions import mod_code
 
 # a capture of this many samples or more goes through an ordinary pass: the capture length at which a batch's wavefront per capture stops
 # beating a pipelined stream's pass per capture -- measured: B / A = 1.39 at 131 072 samples, 1.02 and 0.98 at 196 608 (two runs), 0.98 at 262 144
-# (tools/batch_probe.py, profiles/batch_probe.txt; DESIGN.md 7.7e has the table)
+# (tools/batch_probe.py, profiles/batch_probe.txt; DESIGN.md 7.7e has the table).  PSK keeps it: no measured set has the stream ahead of
+# iq_to_bits_batch_psk at or below it -- B / A = 22.7 for 341 captures of 196 608 samples (tools/batch_psk_probe.py,
+# profiles/batch_psk_probe.txt)
 LONG_FROM_DEFAULT = 196_608
 
 _NOT_IN_A_BATCH = {
@@ -60,8 +68,18 @@ def check_batch_options(p, **options):
             raise ValueError(f"{name} is not an option of a batch: {_NOT_IN_A_BATCH[name]}")
     mod, _ = mod_code(p.modulation_type)
     if mod not in (_lib.MOD_ASK, _lib.MOD_FSK):
-        raise ValueError(f"a batch demodulates ASK and FSK, not {p.modulation_type}: call iq_to_bits per capture, or push the captures "
-                         "through a CaptureStream (a Costas loop in one wavefront lane is not worth having)")
+        raise ValueError(f"this batch demodulates ASK and FSK, not {p.modulation_type}: for PSK call iq_to_bits_batch_psk(captures, p), which runs a "
+                         "Costas loop per capture in one launch (or call iq_to_bits per capture, or push the captures through a CaptureStream)")
+
+
+def is_psk(p) -> bool:
+    return mod_code(p.modulation_type)[0] == _lib.MOD_PSK
+
+
+def as_fsk(p):
+    """PSK parameters recoded as FSK for what reads no modulation but through the noise value, which the two share (-4): the plan (lengths,
+    tolerance, samples per symbol, bits per symbol), the qad-input walk (no ASK rule) and the records (no ASK padding)"""
+    return replace(p, modulation_type="FSK") if is_psk(p) else p
 
 
 def batch_step() -> int:
@@ -332,7 +350,7 @@ def _walk_qad(pipe, pool, qad, starts, p, thresholds, cap_rows, tag="", records=
     starts = np.asarray(starts, dtype=np.int64)
     k = len(starts) - 1
     lengths = np.diff(starts)
-    cp = p.to_c(np.float32)
+    cp = as_fsk(p).to_c(np.float32)            # (PSK reaches this walk from iq_to_bits_batch_psk's second slicing alone: its FSK form serves)
     cp.write_bit_sample_pos = 0
     plan, work_bytes, blob_cap = batch_plan(lengths, cp, cap_rows)
     n_thr = 0 if thresholds is None else int(thresholds.size)
@@ -394,7 +412,8 @@ def _fetch_blobs(pipe, pool, d_dir, k, blob, blob_cap, tag=""):
     return h_dir, h_blob
 
 
-def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq=None, device_starts=None, auto_noise=False, center=None, records=None):
+def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq=None, device_starts=None, auto_noise=False, center=None, records=None,
+               psk=False):
     """the short captures of a batch through the three launches.  caps: numpy arrays (packed and uploaded here, one copy), or device_iq (a
     device tensor that holds them back to back) with device_starts.  auto_noise: four launches -- every capture gated with the threshold
     detected for it (urhgpu_iq_to_bits_batch_auto_dev) -- and one more read, of the K result blocks; "only": that first launch and that
@@ -402,13 +421,19 @@ def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq
     the centers the device left to the host settled and those captures sliced again by ONE more call.  records: None, or the
     message_length_divisor -- the records of all captures are queued behind the walk (urhgpu_batch_msg_records_dev: before anything reuses
     the work buffer) and fetched with one copy; the captures sliced again get the records of their second slicing the same way.
+    psk: the captures are demodulated by a Costas loop per capture (urhgpu_iq_to_bits_batch_psk_dev: one launch, into the qad buffer) and walked
+    from there, with or without a center per capture; the plan, the walk and the records take the parameters recoded as FSK (as_fsk).
     Returns (HostBits list, qad tensor or None, device input, starts, (noise values, flags) or None, (centers, flags) or None)."""
     torch, lib = pipe.torch, _lib.load()
     k = len(lengths)
     lengths = np.asarray(lengths, dtype=np.int64)
     cp = p.to_c(npdt)
     cp.write_bit_sample_pos = 0
-    plan, work_bytes, blob_cap = batch_plan(lengths, cp, cap_rows)
+    cp_walk = cp
+    if psk:
+        cp_walk = as_fsk(p).to_c(npdt)
+        cp_walk.write_bit_sample_pos = 0
+    plan, work_bytes, blob_cap = batch_plan(lengths, cp_walk, cap_rows)
     starts = np.zeros(k + 1, np.int64)
     np.cumsum(lengths, out=starts[1:])
     if device_starts is not None:
@@ -440,10 +465,10 @@ def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq
         blocks = (_lib.NoiseResult * k).from_address(h.data_ptr())
         return [float(r.noise) for r in blocks], [int(r.flag) for r in blocks]
     if auto_noise == "only":
-        _lib.check(lib.urhgpu_batch_noise_dev(pipe.ctx.handle, C.c_void_p(d_iq), total, C.c_void_p(d_start), C.c_void_p(d_plan), k, C.byref(cp),
+        _lib.check(lib.urhgpu_batch_noise_dev(pipe.ctx.handle, C.c_void_p(d_iq), total, C.c_void_p(d_start), C.c_void_p(d_plan), k, C.byref(cp_walk),
                                               C.c_void_p(d_noise.data_ptr())))
         return None, None, (dev_in, meta_bytes, device_iq), starts, fetch_noise(), None
-    qad = torch.empty(max(total, 1), dtype=torch.float32, device=pipe.device) if (want_qad or center is not None) else None
+    qad = torch.empty(max(total, 1), dtype=torch.float32, device=pipe.device) if (want_qad or center is not None or psk) else None
     work = pipe._buf("batch:work", (max(work_bytes, 16),), torch.uint8)
     counts = pipe._buf("batch:counts", (8 * max(k, 1),), torch.int64)
     d_dir = pipe._buf("batch:dir", (k + 1,), torch.int64)
@@ -454,14 +479,20 @@ def _run_batch(pipe, caps, lengths, npdt, p, want_qad, cap_rows, pool, device_iq
     if center is not None:
         max_size = -1 if center["max_size"] is None else int(center["max_size"])
         scratch, scratch_bytes, thr, cap_thr, res, tie, cap_tie = _center_buffers(pipe, k, total, 1 << p.bits_per_symbol, center.get("cap_tie"))
-        _lib.check(lib.urhgpu_iq_to_bits_batch_center_dev(
-            *args[:7], 1 if auto_noise else 0, max_size, *args[7:], C.c_void_p(d_noise.data_ptr()) if auto_noise else None, C.c_void_p(scratch.data_ptr()),
-            scratch_bytes, C.c_void_p(thr.data_ptr()), cap_thr, C.c_void_p(res.data_ptr()), k + 1, C.c_void_p(tie.data_ptr()), cap_tie))
+        outputs = (C.c_void_p(d_noise.data_ptr()) if auto_noise else None, C.c_void_p(scratch.data_ptr()), scratch_bytes, C.c_void_p(thr.data_ptr()),
+                   cap_thr, C.c_void_p(res.data_ptr()), k + 1, C.c_void_p(tie.data_ptr()), cap_tie)
+        if psk:
+            _lib.check(lib.urhgpu_iq_to_bits_batch_psk_dev(*args[:7], 1 if auto_noise else 0, 1, max_size, *args[7:], *outputs))
+        else:
+            _lib.check(lib.urhgpu_iq_to_bits_batch_center_dev(*args[:7], 1 if auto_noise else 0, max_size, *args[7:], *outputs))
+    elif psk:
+        _lib.check(lib.urhgpu_iq_to_bits_batch_psk_dev(*args[:7], 1 if auto_noise else 0, 0, -1, *args[7:], C.c_void_p(d_noise.data_ptr()) if auto_noise else None,
+                                                       None, 0, None, 0, None, 0, None, 0))
     elif auto_noise:
         _lib.check(lib.urhgpu_iq_to_bits_batch_auto_dev(*args, C.c_void_p(d_noise.data_ptr())))
     else:
         _lib.check(lib.urhgpu_iq_to_bits_batch_dev(*args))
-    rec_src = (d_iq, total, d_start, k, cp)
+    rec_src = (d_iq, total, d_start, k, cp_walk)
     queued = None if records is None else _queue_records(pipe, rec_src, None, d_plan, k, plan, records, d_noise, work, work_bytes, counts)
     h_dir, h_blob = _fetch_blobs(pipe, pool, d_dir, k, blob, blob_cap)
     noise = fetch_noise() if auto_noise else None
@@ -592,6 +623,102 @@ def iq_to_bits_batch_records(pipe, captures, p, message_length_divisor=1, auto_n
     return _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, bool(auto_noise), center=center, records=int(message_length_divisor))
 
 
+_NOT_IN_A_BATCH_PSK = {
+    "dc_correction": "a batch does not remove the captures' means: call iq_to_bits(..., dc_correction=True) per capture, or a CaptureStream(dc_correction=True)",
+}
+
+
+def check_batch_psk_options(p, message_length_divisor=None, **options):
+    """what iq_to_bits_batch_psk does not do raises ValueError with a sentence (host arithmetic: no GPU needed)"""
+    for name, value in options.items():
+        if name not in _NOT_IN_A_BATCH_PSK:
+            raise TypeError(f"iq_to_bits_batch_psk() got an unexpected keyword argument '{name}'")
+        if value:
+            raise ValueError(f"{name} is not an option of a batch: {_NOT_IN_A_BATCH_PSK[name]}")
+    if not is_psk(p):
+        raise ValueError(f"iq_to_bits_batch_psk demodulates PSK, not {p.modulation_type}: for ASK and FSK call iq_to_bits_batch or one of its siblings "
+                         "(iq_to_bits_batch_auto, iq_to_bits_batch_center, iq_to_bits_batch_records)")
+    if message_length_divisor is not None and not 1 <= int(message_length_divisor) <= 1 << 30:
+        raise ValueError("message_length_divisor must be at least 1 (and at most 2 ** 30)")
+
+
+def iq_to_bits_batch_psk(pipe, captures, p, auto_noise=False, auto_center=False, center_max_size=None, message_length_divisor=None, want_qad=False,
+                         cap_rows=None, long_from=None, _pool=None, _cap_tie=None, **options):
+    """DevicePipeline.iq_to_bits_batch_psk (see there)"""
+    check_batch_psk_options(p, message_length_divisor, **options)
+    center = {"max_size": center_max_size, "cap_tie": _cap_tie} if auto_center else None
+    return _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, bool(auto_noise), center=center,
+                  records=None if message_length_divisor is None else int(message_length_divisor), psk=True)
+
+
+def _idle_stage(torch, pool, key, nbytes):
+    """a pinned staging buffer of a call that RETURNS WITHOUT WAITING for its upload: the pool keeps, under `key`, the buffers handed out so
+    far with the event recorded behind each one's copy (_stage_in_flight), and a buffer is handed out again only when that event has completed
+    -- the next call must not rewrite bytes a queued copy has yet to read.  None is idle (or large enough): a new one."""
+    ring = pool.setdefault(key, [])
+    for item in list(ring):
+        event, buf = item
+        if event.query():
+            ring.remove(item)
+            if buf.numel() >= nbytes:
+                return buf
+    return torch.empty(max(int(nbytes) + int(nbytes) // 4, 4096), dtype=torch.uint8).pin_memory()
+
+
+def _stage_in_flight(torch, pool, key, buf, stream):
+    event = torch.cuda.Event()
+    event.record(stream)
+    pool[key].append((event, buf))
+
+
+def costas_demod_batch(pipe, captures, p, noise=None, _pool=None):
+    """DevicePipeline.costas_demod_batch (see there)"""
+    check_batch_psk_options(p)
+    torch, lib = pipe.torch, _lib.load()
+    pool = pipe._pinned if _pool is None else _pool
+    caps, on_device, packed, cat, starts_in, npdt, lengths = _batch_input(pipe, captures)
+    k = len(lengths)
+    if noise is not None and len(noise) != k:
+        raise ValueError("noise holds one threshold per capture (or is None: p.noise_threshold for all)")
+    cp = p.to_c(npdt)
+    plan, _, _ = batch_plan(lengths, as_fsk(p).to_c(npdt))
+    starts = starts_in if packed else np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    if on_device:
+        iq = cat if packed else (torch.cat(caps) if caps else torch.empty((0, 2), dtype=torch.float32, device=pipe.device))
+        iq = iq.contiguous()
+        total = int(iq.shape[0])
+    else:                                                  # (uploaded as bytes: every sample type the same way)
+        host = cat if packed else (np.concatenate(caps) if caps else np.zeros((0, 2), npdt))
+        total = int(host.shape[0])
+        iq = torch.from_numpy(np.ascontiguousarray(host).reshape(-1).view(np.uint8)).to(pipe.device)
+    n_meta = 4 * k + 1
+    meta_bytes = (8 * n_meta + _META_ALIGN - 1) // _META_ALIGN * _META_ALIGN
+    block = C.sizeof(_lib.NoiseResult)
+    # nothing below waits for the stream: the staging buffer is one no earlier call's upload is still reading (_idle_stage)
+    stage = _idle_stage(torch, pool, "batch_costas_stages", meta_bytes + block * k)
+    view = stage.numpy()
+    meta = view[:8 * n_meta].view(np.int64)
+    meta[:k + 1] = starts
+    meta[k + 1:] = plan
+    if noise is not None:                                  # a result block per capture as k_batch_noise leaves it for flag 1: noise_f32 and its fp32 square
+        view[meta_bytes:meta_bytes + block * k] = 0
+        blocks = (_lib.NoiseResult * k).from_address(stage.data_ptr() + meta_bytes)
+        for r, value in zip(blocks, noise):
+            f = np.float32(value)
+            r.noise, r.noise_f32, r.noise_sqrd, r.flag = float(value), float(f), float(f * f), 1
+    in_bytes = meta_bytes + (block * k if noise is not None else 0)
+    stream = torch.cuda.current_stream(pipe.device)
+    pipe.ctx.set_stream(stream.cuda_stream)
+    dev_in = torch.empty(max(in_bytes, 8), dtype=torch.uint8, device=pipe.device)      # (of this call alone: the launch before may still read its own)
+    dev_in.copy_(stage[:max(in_bytes, 8)], non_blocking=True)
+    _stage_in_flight(torch, pool, "batch_costas_stages", stage, stream)
+    qad = torch.empty(max(total, 1), dtype=torch.float32, device=pipe.device)
+    _lib.check(lib.urhgpu_batch_costas_dev(pipe.ctx.handle, C.c_void_p(iq.data_ptr()), total, C.c_void_p(dev_in.data_ptr()),
+                                           C.c_void_p(dev_in.data_ptr() + 8 * (k + 1)), k, C.byref(cp),
+                                           C.c_void_p(dev_in.data_ptr() + meta_bytes) if noise is not None else None, C.c_void_p(qad.data_ptr())))
+    return qad[:total], starts                             # (queued on torch's current stream: the samples' memory is not reused before the launch has run)
+
+
 def _qad_batch_input(pipe, captures):
     """(qad_cat, starts) as a contiguous float32 device tensor and K + 1 ascending sample indices inside it"""
     torch = pipe.torch
@@ -685,9 +812,9 @@ def _batch_input(pipe, captures):
     return caps, on_device, packed, cat, starts_in, npdt, lengths
 
 
-def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, center=None, records=None):
-    """iq_to_bits_batch, iq_to_bits_batch_auto, iq_to_bits_batch_center and iq_to_bits_batch_records (records: the message_length_divisor):
-    the input forms, the routing by length, the result sequence"""
+def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, center=None, records=None, psk=False):
+    """iq_to_bits_batch, iq_to_bits_batch_auto, iq_to_bits_batch_center, iq_to_bits_batch_records (records: the message_length_divisor) and
+    iq_to_bits_batch_psk (psk: any combination of the others' options): the input forms, the routing by length, the result sequence"""
     torch = pipe.torch
     long_from = LONG_FROM_DEFAULT if long_from is None else int(long_from)
     pool = pipe._pinned if _pool is None else _pool
@@ -709,10 +836,10 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, 
             dev_starts = None
         dev_cat = dev_cat.contiguous()
         got, qad, src, starts, found, cfound = _run_batch(pipe, None, sub_len, npdt, p, want_qad, cap_rows, pool, device_iq=dev_cat, device_starts=dev_starts,
-                                                          auto_noise=auto_noise, center=center, records=records)
+                                                          auto_noise=auto_noise, center=center, records=records, psk=psk)
     else:
         got, qad, src, starts, found, cfound = _run_batch(pipe, sub, sub_len, npdt, p, want_qad, cap_rows, pool, auto_noise=auto_noise, center=center,
-                                                          records=records)
+                                                          records=records, psk=psk)
     if auto_noise == "only":
         return found
     for j, i in enumerate(short):
@@ -756,7 +883,10 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, 
         """capture k alone with `rows` rows of capacity, results in pinned memory of their own"""
         c = caps[k]
         t = c if on_device else torch.from_numpy(c).to(pipe.device)
-        if records is not None:                            # (alone through the same entry point, records included)
+        if psk:                                            # (alone through the same entry point, with the options of the batch)
+            one = iq_to_bits_batch_psk(pipe, [t.contiguous()], p, bool(auto_noise), center is not None, center["max_size"] if center else None, records,
+                                       want_qad, int(rows), long_from, _pool={}, _cap_tie=center.get("cap_tie") if center else None)
+        elif records is not None:                          # (alone through the same entry point, records included)
             one = iq_to_bits_batch_records(pipe, [t.contiguous()], p, records, bool(auto_noise), center is not None, center["max_size"] if center else None,
                                            want_qad, int(rows), long_from, _pool={}, _cap_tie=center.get("cap_tie") if center else None)
         elif center is not None:                           # (alone through the same entry point: it detects the same threshold and center)
@@ -775,7 +905,9 @@ def launch_counts(pipe):
     """(kernel launches, copies) the batch entry points have issued on the pipeline's context so far: 3 and 2 per batch, 4 and 3 per batch
     with automatic noise thresholds, 1 and 1 per detect_noise_levels; iq_to_bits_batch_center: 4 + 14 ceil(K / group) launches (5 + ... with
     automatic noise) and 3 copies (4), plus -- whatever the number of tied captures -- 3 launches and 3 copies when any center was left to the host;
-    iq_to_bits_batch_records adds 3 launches and 1 copy to its batch, and as many to the second slicing of the captures left to the host"""
+    iq_to_bits_batch_records adds 3 launches and 1 copy to its batch, and as many to the second slicing of the captures left to the host;
+    iq_to_bits_batch_psk: 4 launches (5 with automatic noise) and the copies of the matching batch above, with a center per capture
+    14 ceil(K / group) launches more and the center's copies; costas_demod_batch: 1 launch"""
     out = (C.c_int64 * 2)()
     _lib.check(_lib.load().urhgpu_batch_launches(pipe.ctx.handle, out))
     return int(out[0]), int(out[1])
@@ -996,7 +1128,7 @@ def estimate_batch(pipe, captures, noise=None, modulation=None, long_from=None, 
     items, errors = [None] * k_all, [None] * k_all
 
     def alone(i):
-        """capture i through estimate_dev: a long capture, or PSK -- a batch has no Costas loop"""
+        """capture i through estimate_dev: a long capture, or PSK -- the estimate does not pool PSK captures through k_batch_costas"""
         c = caps[i]
         t = c if on_device else torch.from_numpy(c).to(pipe.device)
         try:

@@ -128,13 +128,27 @@ static int launch_batch_bits(const RunArgs &a, const BatchArgs &b, int dtype, in
     }
 }
 
-// the parameters a batch accepts (every entry point below, and batch_auto.hip's): ASK / FSK, the ranges of the other passes
-int batch_check_params(const urhgpu_params *p) {
+// the ranges of the other passes, whatever the modulation
+static int batch_check_ranges(const urhgpu_params *p) {
     if (!p) return URHGPU_ERR_ARG;
     if (p->dtype < URHGPU_DT_I8 || p->dtype > URHGPU_DT_F32) return URHGPU_ERR_DTYPE;
     if (p->tolerance < 0 || p->tolerance > 65535 || p->samples_per_symbol < 1 || p->bits_per_symbol < 1) return URHGPU_ERR_ARG;
     if (p->bits_per_symbol > 7) return URHGPU_ERR_UNSUPPORTED;
-    if (p->mod != URHGPU_MOD_ASK && p->mod != URHGPU_MOD_FSK) return URHGPU_ERR_UNSUPPORTED;      // a Costas loop in one lane is not worth having
+    return URHGPU_OK;
+}
+
+// the parameters a batch accepts (every entry point below, and batch_auto.hip's): ASK / FSK, the ranges of the other passes
+int batch_check_params(const urhgpu_params *p) {
+    URH_TRY(batch_check_ranges(p));
+    // (the walk follows a wavefront per capture: PSK has entry points of its own, batch_psk.hip, whose loop is a lane per capture)
+    if (p->mod != URHGPU_MOD_ASK && p->mod != URHGPU_MOD_FSK) return URHGPU_ERR_UNSUPPORTED;
+    return URHGPU_OK;
+}
+
+// ... and what the PSK entry points accept (batch_psk.hip): the same ranges, PSK alone
+int batch_check_params_psk(const urhgpu_params *p) {
+    URH_TRY(batch_check_ranges(p));
+    if (p->mod != URHGPU_MOD_PSK) return URHGPU_ERR_UNSUPPORTED;
     return URHGPU_OK;
 }
 

@@ -11,6 +11,7 @@
 //                                   peak tie -- its histogram's counts appended to a pool for the host
 //   k_batch_bits<.., QIN>           batch_kernels.hpp's walk reading qad and classifying through the capture's thresholds
 //   k_batch_scan, k_batch_pack      batch.hip's
+// The PSK pass (urhgpu_iq_to_bits_batch_psk_dev, below) is this route with k_batch_costas (batch_psk.hip) in k_batch_demod's place.
 // Nothing waits for another workgroup; the one atomic is the tie pool's cursor.
 #include "batch_kernels.hpp"      // (first: the fp64 forms of URH_FDIV / URH_FSQRT)
 
@@ -255,6 +256,48 @@ int urhgpu_iq_to_bits_batch_center_dev(urhgpu_ctx *ctx, const void *d_iq, int64_
     a.d_thr = d_thr;
     b.iq = nullptr;
     URH_TRY(launch_batch_bits_qin(a, b, p->mod, grid, ctx->stream));
+    launch_batch_scan_pack(b, grid, ctx->stream);
+    ctx->batch_launches += 3;
+    URH_HIP(hipGetLastError());
+    return URHGPU_OK;
+}
+
+// The whole PSK pass (include/urhgpu.h "a batch of captures: PSK"): urhgpu_iq_to_bits_batch_center_dev with k_batch_costas (batch_psk.hip) where
+// that demodulates, and the center chain only when asked for.  Everything behind the demodulation reads qad and the noise value alone, and
+// PSK shares -4 with FSK: the argument blocks are batch_setup's for the parameters recoded as FSK, the walk is its FSK instantiation (no
+// ASK rule), and the noise launch reads the sample type alone.
+int urhgpu_iq_to_bits_batch_psk_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t *d_start, const int64_t *d_plan, int64_t k,
+                                    const urhgpu_params *p, int auto_noise, int auto_center, int64_t max_size, float *d_qad, void *d_work,
+                                    int64_t work_bytes, int64_t *d_counts, int64_t *d_dir, void *d_blob, int64_t cap_blob, urhgpu_noise_result *d_noise,
+                                    void *d_scratch, int64_t scratch_bytes, float *d_thr, int64_t cap_thr, void *d_result, int64_t cap_result,
+                                    uint32_t *d_tie, int64_t cap_tie) {
+    if (!d_qad || (auto_noise && k > 0 && !d_noise) || ((uintptr_t)d_noise & 7) || (auto_center && k > 0 && !d_thr)) return URHGPU_ERR_ARG;
+    URH_TRY(batch_costas_check(p));
+    urhgpu_params q = *p;
+    q.mod = URHGPU_MOD_FSK;
+    RunArgs a;
+    BatchArgs b;
+    URH_TRY(batch_setup(ctx, d_iq, total, d_start, d_plan, k, &q, d_qad, d_work, work_bytes, d_counts, d_dir, d_blob, cap_blob, a, b));
+    BatchCenterScratch L;
+    if (auto_center) {
+        L = batch_center_scratch(k, total, ctx->tune_center_max_bins);
+        URH_TRY(center_outputs_check(k, a.order, d_scratch, scratch_bytes, L, d_thr, cap_thr, d_result, cap_result, d_tie, cap_tie));
+    }
+    const urhgpu_noise_result *noise = auto_noise ? d_noise : nullptr;
+    a.d_noise = (const float *)noise;
+    const unsigned grid = (unsigned)std::max<int64_t>(k, 1);
+    if (auto_noise) {
+        URH_TRY(urhgpu_batch_noise_dev(ctx, d_iq, total, d_start, d_plan, k, &q, d_noise));      // (counts its launch)
+    }
+    URH_TRY(launch_batch_costas(p, b, noise, ctx->stream));
+    ctx->batch_launches += 1;
+    if (auto_center) {
+        URH_TRY(center_groups(ctx, d_qad, total, d_start, k, &q, max_size, noise, L, (char *)d_scratch, d_thr, (urhgpu_batch_center_result *)d_result, d_tie,
+                              cap_tie));
+    }
+    a.d_thr = auto_center ? d_thr : nullptr;
+    b.iq = nullptr;
+    URH_TRY(launch_batch_bits_qin(a, b, q.mod, grid, ctx->stream));
     launch_batch_scan_pack(b, grid, ctx->stream);
     ctx->batch_launches += 3;
     URH_HIP(hipGetLastError());

@@ -323,6 +323,8 @@ __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchA
 // ---- host side, defined in batch.hip and shared with batch_auto.hip ----
 // the parameters a batch accepts (every entry point): ASK / FSK, the ranges of the other passes
 int batch_check_params(const urhgpu_params *p);
+// ... and the PSK entry points': the same ranges, PSK alone
+int batch_check_params_psk(const urhgpu_params *p);
 // the demodulation's argument block from the parameters of a batch (p has passed batch_check_params)
 void batch_run_args(const urhgpu_params *p, RunArgs &a);
 // the argument checks of urhgpu_iq_to_bits_batch_dev and the two argument blocks of its launches
@@ -330,5 +332,11 @@ int batch_setup(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t 
                 float *d_qad, void *d_work, int64_t work_bytes, int64_t *d_counts, int64_t *d_dir, void *d_blob, int64_t cap_blob, RunArgs &a, BatchArgs &b);
 // k_batch_scan and k_batch_pack behind a launch of k_batch_bits: two launches
 void launch_batch_scan_pack(const BatchArgs &b, unsigned grid, hipStream_t s);
+
+// ---- host side, defined in batch_psk.hip and used by batch_center.hip's whole PSK pass ----
+// PSK parameters a batch accepts: batch_check_params_psk's, and a loop order the reference writes an output for (2 or 4)
+int batch_costas_check(const urhgpu_params *p);
+// k_batch_costas: the Costas loop of every capture of b into b.qad, a lane per capture -- ONE launch.  d_noise: nullptr, or the batch's K result blocks
+int launch_batch_costas(const urhgpu_params *p, const BatchArgs &b, const urhgpu_noise_result *d_noise, hipStream_t s);
 
 }  // namespace urh

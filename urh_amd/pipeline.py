@@ -883,7 +883,8 @@ class DevicePipeline:
         Returns a batch.BatchBits: a sequence of HostBits, each equal to what iq_to_bits gives for that capture alone; .qad(k) (want_qad)
         is capture k's slice of the demodulated signal on the device, .retry(k) runs a truncated capture again with the rows it needs.
         ASK and FSK; PSK, auto_center, auto_noise, msg_records and dc_correction are not options of a batch (ValueError says what to call:
-        for a noise threshold per capture, iq_to_bits_batch_auto; for the messages' records, iq_to_bits_batch_records).
+        for a noise threshold per capture, iq_to_bits_batch_auto; for the messages' records, iq_to_bits_batch_records; for PSK,
+        iq_to_bits_batch_psk).
         p -- modulation, samples per symbol, tolerance, center -- where it is not known: estimate_batch gives it per capture."""
         from .batch import iq_to_bits_batch
         return iq_to_bits_batch(self, captures, p, want_qad, cap_rows, long_from, **options)
@@ -900,7 +901,7 @@ class DevicePipeline:
         HostBits is the reference's slicing of zeros(2), n_samples = 2.  Flag 0 -- the reference raises for that capture --: result[k],
         iteration at k and .check() raise the same exception (ValueError for a NaN, OverflowError for an infinity); every other capture is
         handed out.  .retry(k) runs a truncated capture again, alone, through this entry point: it detects the same threshold.
-        ASK and FSK; PSK, auto_center, msg_records and dc_correction are not options of a batch (ValueError says what to call).
+        ASK and FSK; PSK (iq_to_bits_batch_psk), auto_center, msg_records and dc_correction are not options of a batch (ValueError says what to call).
         p where it is not known: estimate_batch gives it per capture."""
         from .batch import iq_to_bits_batch_auto
         return iq_to_bits_batch_auto(self, captures, p, auto_noise, want_qad, cap_rows, long_from, **options)
@@ -922,7 +923,7 @@ class DevicePipeline:
         settled to a center are sliced again by one more call; their HostBits replace the first ones.  With auto_noise, .noise and
         .noise_flags as for iq_to_bits_batch_auto: a noise flag 2 gives center None, center flag 0 and the slicing of two zeros with p.center;
         a noise flag 0 raises the reference's exception where that capture is handed out.
-        ASK and FSK; PSK, msg_records and dc_correction are not options of a batch (ValueError says what to call).
+        ASK and FSK; PSK (iq_to_bits_batch_psk), msg_records and dc_correction are not options of a batch (ValueError says what to call).
         p where it is not known: estimate_batch gives it per capture."""
         from .batch import iq_to_bits_batch_center
         return iq_to_bits_batch_center(self, captures, p, auto_noise, center_max_size, want_qad, cap_rows, long_from, **options)
@@ -942,11 +943,39 @@ class DevicePipeline:
         record for record, iq_to_bits(capture_k, p, auto_noise=..., auto_center=..., msg_records=True, message_length_divisor=...) on it
         alone; the RSSI bit for bit.  A truncated capture's message_data() raises the capacity error; .retry(k) runs it again with records.
         A noise flag 2 capture is sliced as two zeros and its records, if any, read the real capture; noise flag 0 raises where the capture
-        is handed out.  ASK and FSK; PSK and dc_correction are not options of a batch (ValueError says what to call).
+        is handed out.  ASK and FSK; PSK (iq_to_bits_batch_psk) and dc_correction are not options of a batch (ValueError says what to call).
         p where it is not known: estimate_batch gives it per capture."""
         from .batch import iq_to_bits_batch_records
         return iq_to_bits_batch_records(self, captures, p, message_length_divisor, auto_noise, auto_center, center_max_size, want_qad, cap_rows, long_from,
                                         **options)
+
+    def iq_to_bits_batch_psk(self, captures, p: DemodParams, auto_noise=False, auto_center=False, center_max_size=None, message_length_divisor=None,
+                             want_qad=False, cap_rows=None, long_from=None, **options):
+        """The batch of PSK captures (include/urhgpu.h "a batch of captures: PSK"): ONE launch runs the Costas loop of every capture -- a lane
+        per capture, every loop from the known state {freq 0, phase 1.5}, nothing speculated -- into one demodulated buffer, and the batch's
+        qad-input walk slices from there.  The device time follows the LONGEST capture of the batch, not their number.  4 launches (5 with
+        auto_noise), with auto_center 14 more per group of the center chain; copies as for the matching ASK / FSK batch.
+        captures, want_qad, cap_rows, long_from: as for iq_to_bits_batch (the three input forms, the five sample types); a capture of long_from
+        samples or more goes through iq_to_bits with the same options.
+        auto_noise: a threshold per capture (as iq_to_bits_batch_auto; the result carries .noise / .noise_flags).  auto_center: a center per
+        capture (as iq_to_bits_batch_center with center_max_size; .centers / .center_flags; centers the device leaves to numpy are settled and
+        those captures sliced again by one more call).  message_length_divisor: None, or the divisor -- the records of every message are queued
+        behind the walk (as iq_to_bits_batch_records; three launches and one copy more).
+        Returns a batch.BatchBits; capture k equals iq_to_bits(capture_k, p, want_qad=True, auto_noise=..., auto_center=..., msg_records=...)
+        on that capture alone, bit for bit, .qad(k) included.  .retry(k) runs a truncated capture again through this entry point.
+        PSK alone (ValueError names iq_to_bits_batch and its siblings for ASK / FSK); dc_correction is not an option of a batch; an unknown option
+        is a TypeError -- all before a device is touched."""
+        from .batch import iq_to_bits_batch_psk
+        return iq_to_bits_batch_psk(self, captures, p, auto_noise, auto_center, center_max_size, message_length_divisor, want_qad, cap_rows, long_from,
+                                    **options)
+
+    def costas_demod_batch(self, captures, p: DemodParams, noise=None):
+        """The Costas launch of iq_to_bits_batch_psk alone (urhgpu_batch_costas_dev): afp_demod with PSK of every capture of a batch (the three
+        input forms of iq_to_bits_batch) in ONE launch.  noise: None -- every capture gated with p.noise_threshold --, or one threshold per
+        capture.  Returns (qad_cat, starts): a float32 device tensor and K + 1 sample indices, capture k = qad_cat[starts[k]:starts[k + 1]] --
+        the shape detect_centers and qad_to_bits_batch take."""
+        from .batch import costas_demod_batch
+        return costas_demod_batch(self, captures, p, noise)
 
     def detect_centers(self, captures, max_size=None):
         """AutoInterpretation.detect_center of every capture of a batch of DEMODULATED signals, captures = (qad_cat, starts) with capture k =
@@ -988,7 +1017,7 @@ class DevicePipeline:
         the sample type's max_magnitude is.
         modulation: None -- a vote per capture over its first 100 messages --, "OOK", "ASK", "FSK", "PSK", or one of these (or None) per capture.
         long_from: a capture of that many samples or more goes through estimate_dev alone and takes its place in the result; so does a
-        capture given or detected as PSK (a batch has no Costas loop).
+        capture given or detected as PSK (the estimate does not pool them through iq_to_bits_batch_psk's Costas launch).
         Returns a batch.BatchEstimates: per capture the dict {modulation_type, bit_length, center, tolerance, noise}, or None; a capture for
         which the reference raises (its noise level is a NaN or an infinity) raises the same exception where it is handed out."""
         from .batch import estimate_batch

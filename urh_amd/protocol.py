@@ -134,9 +134,15 @@ def get_protocols_from_signals_dev(pipe, captures, p, message_length_divisor=1, 
     """get_protocol_from_signal_dev for a recording session: captures as DevicePipeline.iq_to_bits_batch takes them (a list of numpy arrays
     or device tensors, or (iq_cat, starts)), one parameter set for all.  One batch with its records queued behind it
     (DevicePipeline.iq_to_bits_batch_records); a capture whose pulse table outgrew its capacity is run once more with the rows it needs.
-    timestamps: one per capture, default 0.0.  Returns a list of MessageData lists, one per capture in the order given."""
-    res = pipe.iq_to_bits_batch_records(captures, p, message_length_divisor, auto_noise=auto_noise, auto_center=auto_center, center_max_size=center_max_size,
-                                        cap_rows=cap_rows, long_from=long_from)
+    timestamps: one per capture, default 0.0.  Returns a list of MessageData lists, one per capture in the order given.
+    PSK parameters take DevicePipeline.iq_to_bits_batch_psk with the same options."""
+    from .batch import is_psk
+    if is_psk(p):
+        res = pipe.iq_to_bits_batch_psk(captures, p, auto_noise=auto_noise, auto_center=auto_center, center_max_size=center_max_size,
+                                        message_length_divisor=message_length_divisor, cap_rows=cap_rows, long_from=long_from)
+    else:
+        res = pipe.iq_to_bits_batch_records(captures, p, message_length_divisor, auto_noise=auto_noise, auto_center=auto_center, center_max_size=center_max_size,
+                                            cap_rows=cap_rows, long_from=long_from)
     for k in res.truncated:
         res.retry(k)
     return res.messages(sample_rate, timestamps)
