@@ -1353,6 +1353,28 @@ int urhgpu_iq_to_bits_batch_psk_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t t
                                     urhgpu_noise_result *d_noise, void *d_scratch, int64_t scratch_bytes, float *d_thr, int64_t cap_thr,
                                     void *d_result, int64_t cap_result, uint32_t *d_tie, int64_t cap_tie);
 
+/* ---- a batch of captures: DC correction per capture ---------------------------------------------------------------------------------
+ * out_c = x_c - mean(x_c, axis 0) for every capture c of a batch (Filter.py:31-35, Device.py:822-823: the default of the reference's receive
+ * path), bit for bit what urhgpu_dc_correct_dev gives for that capture alone and what numpy's expression gives -- for float32 captures that
+ * includes the strictly sequential float32 column sum.  urhgpu_dc_correct_dev takes one capture per call, up to five launches and a work area
+ * of the context; a batch evaluates the serial sums side by side instead (urh_amd/csrc/batch_dc.hip): nothing is speculated.
+ *   urhgpu_batch_dc_correct_dev   TWO launches on the context's stream whatever k and the lengths are, asynchronous: the two column means of
+ *            every capture (float32: a lane per capture and column, a wavefront per 32 captures taken in the plan's launch order, so the
+ *            device time follows the LONGEST capture; integers: exact int64 sums, a workgroup per capture), then the subtraction of all
+ *            captures (float32 subtracts in float32; integers give (T)(int32) trunc(double(x) - mean)).  d_iq, total, d_start, d_plan, k:
+ *            as for urhgpu_iq_to_bits_batch_dev (of the plan only the launch order is read); dtype: URHGPU_DT_*.  d_out: d_iq itself (in
+ *            place) or a buffer of total samples that does not overlap it; capture c lies at the same samples of it, so the same d_start
+ *            and d_plan serve every later batch call on d_out.  Samples that belong to no capture are neither read nor written; a capture
+ *            whose start or end is refused is an empty capture.  d_mean: NULL, or k pairs of means -- float[2 k] for float32 captures,
+ *            double[2 k] otherwise; an empty capture writes nothing but its pair, NaN (numpy's 0 / 0).  Without d_mean the pairs live in a
+ *            buffer of the context between the two launches (calls on one stream share it in order; it only grows).  k == 0 launches nothing.
+ *            Rejected before anything is launched (and without a GPU): a sample type: URHGPU_ERR_DTYPE; a negative size, a missing context
+ *            or buffer, d_iq or d_out not aligned to 16 bytes, d_start, d_plan or d_mean not aligned to 8, d_out overlapping d_iq without
+ *            being it: URHGPU_ERR_ARG.
+ * urhgpu_batch_launches counts the two launches. */
+int urhgpu_batch_dc_correct_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, int dtype, const int64_t *d_start, const int64_t *d_plan,
+                                int64_t k, void *d_out, void *d_mean);
+
 #ifdef __cplusplus
 }
 #endif

@@ -258,6 +258,7 @@ PROTOTYPES = {
     "urhgpu_batch_costas_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _vp, _vp]),
     "urhgpu_iq_to_bits_batch_psk_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _i, _i, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp,
                                              _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
+    "urhgpu_batch_dc_correct_dev": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None

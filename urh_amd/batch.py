@@ -32,6 +32,12 @@ capture -- a lane per capture, each from the known start state, nothing speculat
 iq_to_bits_batch_center goes on from there (the center chain only when asked for, the qad-input walk, the records) with the parameters
 recoded as FSK, whose noise value PSK shares.  The loop is serial: the device time follows the LONGEST capture of the batch, not their
 number.  costas_demod_batch is that launch alone.  The entry points above keep refusing PSK and name this one.
+
+DevicePipeline.iq_to_bits_batch_dc is any of the above over captures minus their own means -- the reference's DC correction, the default of
+its receive path (urh_amd/csrc/batch_dc.hip): TWO launches in front correct every capture on the device, bit-equal with numpy's expression
+(for float32 captures numpy's strictly sequential column sum, a lane per capture and column), and the matching batch runs on the corrected
+buffer.  dc_correct_batch is those two launches alone; what it returns is the third input form of every batch method.  The entry points
+above keep refusing dc_correction and name this one.
 """
 import ctypes as C
 from dataclasses import replace
@@ -49,13 +55,16 @@ from .signal_functions import mod_code
 # profiles/batch_psk_probe.txt)
 LONG_FROM_DEFAULT = 196_608
 
+# the refusals of dc_correction name the entry point that does it, then say what they always said
+_DC_FIRST = "call iq_to_bits_batch_dc(captures, p, ...), which removes every capture's means on the device in two more launches; apart from that method "
+
 _NOT_IN_A_BATCH = {
     "auto_center": "iq_to_bits_batch slices every capture with p.center: call iq_to_bits_batch_center(captures, p, auto_noise=False), which detects a center "
                    "per capture (or call iq_to_bits(..., auto_center=True) per capture, or a CaptureStream(auto_center=True))",
     "auto_noise": "iq_to_bits_batch gates every capture with p.noise_threshold: call iq_to_bits_batch_auto(captures, p), which detects a threshold per capture",
     "msg_records": "iq_to_bits_batch computes no message records: call iq_to_bits_batch_records(captures, p), which queues them behind the batch (or call "
                    "iq_to_bits(..., msg_records=True) per capture, or a CaptureStream(msg_records=True))",
-    "dc_correction": "a batch does not remove the captures' means: call iq_to_bits(..., dc_correction=True) per capture, or a CaptureStream(dc_correction=True)",
+    "dc_correction": _DC_FIRST + "a batch does not remove the captures' means: call iq_to_bits(..., dc_correction=True) per capture, or a CaptureStream(dc_correction=True)",
 }
 
 
@@ -120,8 +129,11 @@ class BatchBits:
     bit_sample_pos(), pos_offsets(), flat(), truncated, rows_needed, check() as for a stream's results).  Views of pinned memory of the
     pipeline: valid until its next batch; copy what has to live longer."""
 
-    def __init__(self, items, params, lengths, qads=None, rerun=None, noise=None, noise_flags=None, centers=None, center_flags=None):
+    def __init__(self, items, params, lengths, qads=None, rerun=None, noise=None, noise_flags=None, centers=None, center_flags=None, means=None):
         self._items = list(items)
+        # iq_to_bits_batch_dc: the two means taken off every capture, numpy [K, 2] (float32 for float32 captures, float64 otherwise; NaN for
+        # an empty capture)
+        self.means = means
         self.params = params
         self.lengths = [int(n) for n in lengths]
         self._qads = qads                  # per capture: device tensor or None
@@ -538,7 +550,7 @@ _NOT_IN_A_BATCH_AUTO = {
                    "center per capture (or call iq_to_bits(..., auto_noise=True, auto_center=True) per capture, or a CaptureStream)",
     "msg_records": "iq_to_bits_batch_auto computes no message records: call iq_to_bits_batch_records(captures, p, auto_noise=True), which queues them behind "
                    "the batch (or call iq_to_bits(..., auto_noise=True, msg_records=True) per capture, or a CaptureStream)",
-    "dc_correction": "a batch does not remove the captures' means: call iq_to_bits(..., auto_noise=True, dc_correction=True) per capture, or a CaptureStream",
+    "dc_correction": _DC_FIRST + "a batch does not remove the captures' means: call iq_to_bits(..., auto_noise=True, dc_correction=True) per capture, or a CaptureStream",
 }
 
 
@@ -577,7 +589,7 @@ def detect_noise_levels(pipe, captures):
 _NOT_IN_A_BATCH_CENTER = {
     "msg_records": "iq_to_bits_batch_center computes no message records: call iq_to_bits_batch_records(captures, p, auto_noise=..., auto_center=True), which "
                    "queues them behind the batch (or call iq_to_bits(..., auto_center=True, msg_records=True) per capture, or a CaptureStream)",
-    "dc_correction": "a batch does not remove the captures' means: call iq_to_bits(..., auto_center=True, dc_correction=True) per capture, or a CaptureStream",
+    "dc_correction": _DC_FIRST + "a batch does not remove the captures' means: call iq_to_bits(..., auto_center=True, dc_correction=True) per capture, or a CaptureStream",
 }
 
 
@@ -599,7 +611,7 @@ def iq_to_bits_batch_center(pipe, captures, p, auto_noise=True, center_max_size=
 
 
 _NOT_IN_A_BATCH_RECORDS = {
-    "dc_correction": "a batch does not remove the captures' means: call iq_to_bits(..., msg_records=True, dc_correction=True) per capture, or a CaptureStream",
+    "dc_correction": _DC_FIRST + "a batch does not remove the captures' means: call iq_to_bits(..., msg_records=True, dc_correction=True) per capture, or a CaptureStream",
 }
 
 
@@ -624,7 +636,7 @@ def iq_to_bits_batch_records(pipe, captures, p, message_length_divisor=1, auto_n
 
 
 _NOT_IN_A_BATCH_PSK = {
-    "dc_correction": "a batch does not remove the captures' means: call iq_to_bits(..., dc_correction=True) per capture, or a CaptureStream(dc_correction=True)",
+    "dc_correction": _DC_FIRST + "a batch does not remove the captures' means: call iq_to_bits(..., dc_correction=True) per capture, or a CaptureStream(dc_correction=True)",
 }
 
 
@@ -717,6 +729,97 @@ def costas_demod_batch(pipe, captures, p, noise=None, _pool=None):
                                            C.c_void_p(dev_in.data_ptr() + 8 * (k + 1)), k, C.byref(cp),
                                            C.c_void_p(dev_in.data_ptr() + meta_bytes) if noise is not None else None, C.c_void_p(qad.data_ptr())))
     return qad[:total], starts                             # (queued on torch's current stream: the samples' memory is not reused before the launch has run)
+
+
+def check_batch_dc_options(p, message_length_divisor=None, **options):
+    """iq_to_bits_batch_dc takes the options of its signature alone: anything else is a TypeError, a divisor below 1 and a modulation no batch
+    demodulates a ValueError (host arithmetic: no GPU needed)"""
+    for name in options:
+        raise TypeError(f"iq_to_bits_batch_dc() got an unexpected keyword argument '{name}'")
+    if is_psk(p):
+        check_batch_psk_options(p)
+    else:
+        check_batch_options(p)
+    if message_length_divisor is not None and not 1 <= int(message_length_divisor) <= 1 << 30:
+        raise ValueError("message_length_divisor must be at least 1 (and at most 2 ** 30)")
+
+
+def _dc_correct(pipe, pool, caps, lengths, npdt, on_device, cat=None, starts_in=None):
+    """urhgpu_batch_dc_correct_dev on the captures `caps` (numpy arrays or device tensors, as _batch_input hands them out), or on cat with
+    starts_in where a packed buffer is taken whole: one upload -- starts, plan and, for host captures, every sample --, two launches, nothing
+    waited for.  Host captures are corrected in place in their upload, a concatenation made here in place too; a caller's device tensor is
+    read and the result written into a buffer of the same geometry.  Returns (iq_cat (total, 2) on the device, starts, the means as a device
+    tensor of 2 K float32 / float64)."""
+    from .iq_array import _torch_dtype_for
+    from .pipeline import DemodParams
+    from .signal_functions import dtype_code
+    torch, lib = pipe.torch, _lib.load()
+    npdt = np.dtype(npdt)
+    k = len(lengths)
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    p = DemodParams("FSK", 1, 0.0, 0.0, 1.0, 5, 100, 0.1, 8, False)            # (of the plan only the launch order is read)
+    plan, _, _ = batch_plan(lengths, p.to_c(npdt))
+    if cat is not None:
+        starts, total = np.asarray(starts_in, dtype=np.int64), int(len(cat))
+    else:
+        starts = np.zeros(k + 1, np.int64)
+        np.cumsum(lengths, out=starts[1:])
+        total = int(starts[-1])
+    item = 2 * npdt.itemsize
+    n_meta = 4 * k + 1
+    meta_bytes = (8 * n_meta + _META_ALIGN - 1) // _META_ALIGN * _META_ALIGN
+    in_bytes = meta_bytes + (0 if on_device else total * item)
+    # nothing below waits for the stream: the staging buffer is one no earlier call's upload is still reading (_idle_stage)
+    stage = _idle_stage(torch, pool, "batch_dc_stages", in_bytes)
+    view = stage.numpy()
+    meta = view[:8 * n_meta].view(np.int64)
+    meta[:k + 1] = starts
+    meta[k + 1:] = plan
+    if not on_device:
+        if cat is not None:
+            view[meta_bytes:in_bytes] = cat.reshape(-1).view(np.uint8)
+        else:
+            for a, s in zip(caps, starts[:-1]):
+                if len(a):
+                    view[meta_bytes + int(s) * item: meta_bytes + (int(s) + len(a)) * item] = a.reshape(-1).view(np.uint8)
+    stream = torch.cuda.current_stream(pipe.device)
+    pipe.ctx.set_stream(stream.cuda_stream)
+    dev_in = torch.empty(in_bytes, dtype=torch.uint8, device=pipe.device)       # (of this call alone: the result of a host batch is a view of it)
+    dev_in.copy_(stage[:in_bytes], non_blocking=True)                            # THE upload
+    _stage_in_flight(torch, pool, "batch_dc_stages", stage, stream)
+    tdt = _torch_dtype_for(npdt)
+    if not on_device:
+        src = out = dev_in[meta_bytes:in_bytes].view(tdt).reshape(total, 2)
+    else:
+        src = cat if cat is not None else (torch.cat(caps) if caps else torch.empty((0, 2), dtype=tdt, device=pipe.device))
+        mine = cat is None or not src.is_contiguous()                            # a tensor made here may be corrected where it lies
+        src = src.contiguous()
+        if src.data_ptr() % 16:                                                  # (a view that starts off a 16-byte boundary)
+            src, mine = src.clone(), True
+        out = src if mine else torch.empty_like(src)
+    d_mean = torch.empty(max(2 * k, 1), dtype=torch.float32 if npdt == np.float32 else torch.float64, device=pipe.device)
+    _lib.check(lib.urhgpu_batch_dc_correct_dev(pipe.ctx.handle, C.c_void_p(src.data_ptr()), total, dtype_code(npdt), C.c_void_p(dev_in.data_ptr()),
+                                               C.c_void_p(dev_in.data_ptr() + 8 * (k + 1)), k, C.c_void_p(out.data_ptr()), C.c_void_p(d_mean.data_ptr())))
+    return out, starts, d_mean[:2 * k]     # (queued on torch's current stream: no memory of this call is reused before the launches have run)
+
+
+def dc_correct_batch(pipe, captures, want_means=False, _pool=None):
+    """DevicePipeline.dc_correct_batch (see there)"""
+    pool = pipe._pinned if _pool is None else _pool
+    caps, on_device, packed, cat, starts_in, npdt, lengths = _batch_input(pipe, captures)
+    iq, starts, d_mean = _dc_correct(pipe, pool, caps, lengths, npdt, on_device, cat if packed else None, starts_in if packed else None)
+    if want_means:
+        return iq, starts, d_mean.cpu().numpy().reshape(len(lengths), 2)
+    return iq, starts
+
+
+def iq_to_bits_batch_dc(pipe, captures, p, auto_noise=False, auto_center=False, center_max_size=None, message_length_divisor=None, want_qad=False,
+                        cap_rows=None, long_from=None, _pool=None, _cap_tie=None, **options):
+    """DevicePipeline.iq_to_bits_batch_dc (see there)"""
+    check_batch_dc_options(p, message_length_divisor, **options)
+    center = {"max_size": center_max_size, "cap_tie": _cap_tie} if auto_center else None
+    return _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, bool(auto_noise), center=center,
+                  records=None if message_length_divisor is None else int(message_length_divisor), psk=is_psk(p), dc=True)
 
 
 def _qad_batch_input(pipe, captures):
@@ -812,9 +915,10 @@ def _batch_input(pipe, captures):
     return caps, on_device, packed, cat, starts_in, npdt, lengths
 
 
-def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, center=None, records=None, psk=False):
-    """iq_to_bits_batch, iq_to_bits_batch_auto, iq_to_bits_batch_center, iq_to_bits_batch_records (records: the message_length_divisor) and
-    iq_to_bits_batch_psk (psk: any combination of the others' options): the input forms, the routing by length, the result sequence"""
+def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, center=None, records=None, psk=False, dc=False):
+    """iq_to_bits_batch, iq_to_bits_batch_auto, iq_to_bits_batch_center, iq_to_bits_batch_records (records: the message_length_divisor),
+    iq_to_bits_batch_psk (psk: any combination of the others' options) and iq_to_bits_batch_dc (dc: any of them over the corrected captures):
+    the input forms, the routing by length, the result sequence"""
     torch = pipe.torch
     long_from = LONG_FROM_DEFAULT if long_from is None else int(long_from)
     pool = pipe._pinned if _pool is None else _pool
@@ -824,11 +928,20 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, 
     qads = [None] * len(caps) if want_qad else None
     noise, flags = ([0.0] * len(caps), [1] * len(caps)) if auto_noise else (None, None)
     centers, cflags = ([None] * len(caps), [0] * len(caps)) if center is not None else (None, None)
+    means = np.full((len(caps), 2), np.nan, np.float32 if npdt == np.float32 else np.float64) if dc else None
 
     # the short ones: one batch
     sub = [caps[i] for i in short]
     sub_len = [lengths[i] for i in short]
-    if on_device:
+    d_mean = None
+    if dc:
+        # two launches in front: the short captures corrected in ONE buffer on the device (host captures: in their upload), which the batch
+        # then reads through its device_iq form
+        whole = packed and len(long_) == 0
+        dev_cat, dev_starts, d_mean = _dc_correct(pipe, pool, sub, sub_len, npdt, on_device, cat if whole else None, starts_in if whole else None)
+        got, qad, src, starts, found, cfound = _run_batch(pipe, None, sub_len, npdt, p, want_qad, cap_rows, pool, device_iq=dev_cat, device_starts=dev_starts,
+                                                          auto_noise=auto_noise, center=center, records=records, psk=psk)
+    elif on_device:
         if packed and len(long_) == 0 and cat.is_contiguous():
             dev_cat, dev_starts = cat, starts_in
         else:
@@ -851,15 +964,20 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, 
             centers[i], cflags[i] = cfound[0][j], cfound[1][j]
         if want_qad:
             qads[i] = qad[int(starts[j]):int(starts[j]) + items[i].n_samples]     # (an auto_noise capture that is gated entirely: zeros(2))
+    if dc and len(short):
+        means[short] = d_mean.cpu().numpy().reshape(-1, 2)       # (the batch's fetch has waited for the stream: this copy waits for nothing)
 
     # the long ones: an ordinary pass each
     p_pass = replace(p, write_bit_sample_pos=False)
     for i in long_:
         c = caps[i]
         t = c if on_device else torch.from_numpy(c).to(pipe.device)
+        if dc:                                             # (the pass keeps its means to itself: they are taken once more for .means)
+            from .filter import dc_correct_dev
+            means[i] = dc_correct_dev(pipe, t.contiguous(), want_mean=True)[1].cpu().numpy()
         res = pipe.iq_to_bits(t.contiguous(), p_pass, want_qad=want_qad or center is not None, cap_rows=cap_rows if isinstance(cap_rows, int) else None,
                               auto_noise=bool(auto_noise), auto_center=center is not None, center_max_size=center["max_size"] if center else None,
-                              msg_records=records is not None, message_length_divisor=records or 1)
+                              msg_records=records is not None, message_length_divisor=records or 1, dc_correction=dc)
         if auto_noise:
             flags[i] = res.noise_flag
             noise[i] = float(res._noise)
@@ -883,7 +1001,10 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, 
         """capture k alone with `rows` rows of capacity, results in pinned memory of their own"""
         c = caps[k]
         t = c if on_device else torch.from_numpy(c).to(pipe.device)
-        if psk:                                            # (alone through the same entry point, with the options of the batch)
+        if dc:                                             # (corrected again, alone through the same entry point, with the options of the batch)
+            one = iq_to_bits_batch_dc(pipe, [t.contiguous()], p, bool(auto_noise), center is not None, center["max_size"] if center else None, records,
+                                      want_qad, int(rows), long_from, _pool={}, _cap_tie=center.get("cap_tie") if center else None)
+        elif psk:                                          # (alone through the same entry point, with the options of the batch)
             one = iq_to_bits_batch_psk(pipe, [t.contiguous()], p, bool(auto_noise), center is not None, center["max_size"] if center else None, records,
                                        want_qad, int(rows), long_from, _pool={}, _cap_tie=center.get("cap_tie") if center else None)
         elif records is not None:                          # (alone through the same entry point, records included)
@@ -898,7 +1019,7 @@ def _batch(pipe, captures, p, want_qad, cap_rows, long_from, _pool, auto_noise, 
             one = iq_to_bits_batch(pipe, [t.contiguous()], p, want_qad=want_qad, cap_rows=int(rows), long_from=long_from, _pool={})
         return one[0], (one.qad(0) if want_qad else None)
 
-    return BatchBits(items, p, lengths, qads, rerun, noise, flags, centers, cflags)
+    return BatchBits(items, p, lengths, qads, rerun, noise, flags, centers, cflags, means)
 
 
 def launch_counts(pipe):
@@ -907,7 +1028,8 @@ def launch_counts(pipe):
     automatic noise) and 3 copies (4), plus -- whatever the number of tied captures -- 3 launches and 3 copies when any center was left to the host;
     iq_to_bits_batch_records adds 3 launches and 1 copy to its batch, and as many to the second slicing of the captures left to the host;
     iq_to_bits_batch_psk: 4 launches (5 with automatic noise) and the copies of the matching batch above, with a center per capture
-    14 ceil(K / group) launches more and the center's copies; costas_demod_batch: 1 launch"""
+    14 ceil(K / group) launches more and the center's copies; costas_demod_batch: 1 launch; dc_correct_batch: 2 launches, and
+    iq_to_bits_batch_dc those 2 more than its batch"""
     out = (C.c_int64 * 2)()
     _lib.check(_lib.load().urhgpu_batch_launches(pipe.ctx.handle, out))
     return int(out[0]), int(out[1])

@@ -192,6 +192,7 @@ struct urhgpu_ctx {
     hipStream_t dc_stream = nullptr;
     const void *dc_shard_in = nullptr;     // the shard whose chunk records urhgpu_shard_dc_spec_dev left in dc_work (urhgpu_shard_dc_resolve_dev takes no other)
     int64_t dc_shard_n = -1;
+    urh::Arena batch_dc_mean;              // urhgpu_batch_dc_correct_dev without d_mean: the K mean pairs between its two launches (batch_dc.hip)
 };
 constexpr size_t kSegBlockBytes = 4096;      // 16 progress counters on their own 128-byte lines, then the SegState
 

@@ -129,6 +129,7 @@ int urhgpu_ctx_destroy(urhgpu_ctx *ctx) {
     ctx->chunk_work.release();
     ctx->center_work.release();
     ctx->dc_work.release();
+    ctx->batch_dc_mean.release();
     if (ctx->ev_dc) (void)hipEventDestroy(ctx->ev_dc);
     if (ctx->ev_center) (void)hipEventDestroy(ctx->ev_center);
     if (ctx->h_chunk) (void)hipHostFree(ctx->h_chunk);

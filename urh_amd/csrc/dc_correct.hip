@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "dc_sub.hpp"
 
 namespace urh {
 
@@ -119,11 +120,7 @@ __global__ void __launch_bounds__(kDcBlock) k_dc_isum(const T *__restrict__ in, 
     }
 }
 
-// ---- the subtraction, every sample type ----------------------------------------------------------------------------------------------
-template <class T, class M> __device__ __forceinline__ T dc_sub(T x, M m) {
-    if constexpr (std::is_same<T, float>::value) return x - m;
-    else return (T)(int)((double)x - m);             // truncated toward zero into an int32, low bits kept: numpy's cast on x86-64
-}
+// ---- the subtraction, every sample type (dc_sub: dc_sub.hpp) -------------------------------------------------------------------------
 template <class T, class M>
 __global__ void __launch_bounds__(kDcBlock) k_dc_sub(const T *in, T *out, DcSpan sp, const M *mean) {
     constexpr int kPer = 16 / (int)sizeof(T);

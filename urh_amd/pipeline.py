@@ -884,7 +884,7 @@ class DevicePipeline:
         is capture k's slice of the demodulated signal on the device, .retry(k) runs a truncated capture again with the rows it needs.
         ASK and FSK; PSK, auto_center, auto_noise, msg_records and dc_correction are not options of a batch (ValueError says what to call:
         for a noise threshold per capture, iq_to_bits_batch_auto; for the messages' records, iq_to_bits_batch_records; for PSK,
-        iq_to_bits_batch_psk).
+        iq_to_bits_batch_psk; for dc_correction, iq_to_bits_batch_dc).
         p -- modulation, samples per symbol, tolerance, center -- where it is not known: estimate_batch gives it per capture."""
         from .batch import iq_to_bits_batch
         return iq_to_bits_batch(self, captures, p, want_qad, cap_rows, long_from, **options)
@@ -901,7 +901,8 @@ class DevicePipeline:
         HostBits is the reference's slicing of zeros(2), n_samples = 2.  Flag 0 -- the reference raises for that capture --: result[k],
         iteration at k and .check() raise the same exception (ValueError for a NaN, OverflowError for an infinity); every other capture is
         handed out.  .retry(k) runs a truncated capture again, alone, through this entry point: it detects the same threshold.
-        ASK and FSK; PSK (iq_to_bits_batch_psk), auto_center, msg_records and dc_correction are not options of a batch (ValueError says what to call).
+        ASK and FSK; PSK (iq_to_bits_batch_psk), auto_center, msg_records and dc_correction (iq_to_bits_batch_dc) are not options of a batch
+        (ValueError says what to call).
         p where it is not known: estimate_batch gives it per capture."""
         from .batch import iq_to_bits_batch_auto
         return iq_to_bits_batch_auto(self, captures, p, auto_noise, want_qad, cap_rows, long_from, **options)
@@ -923,7 +924,8 @@ class DevicePipeline:
         settled to a center are sliced again by one more call; their HostBits replace the first ones.  With auto_noise, .noise and
         .noise_flags as for iq_to_bits_batch_auto: a noise flag 2 gives center None, center flag 0 and the slicing of two zeros with p.center;
         a noise flag 0 raises the reference's exception where that capture is handed out.
-        ASK and FSK; PSK (iq_to_bits_batch_psk), msg_records and dc_correction are not options of a batch (ValueError says what to call).
+        ASK and FSK; PSK (iq_to_bits_batch_psk), msg_records and dc_correction (iq_to_bits_batch_dc) are not options of a batch (ValueError says
+        what to call).
         p where it is not known: estimate_batch gives it per capture."""
         from .batch import iq_to_bits_batch_center
         return iq_to_bits_batch_center(self, captures, p, auto_noise, center_max_size, want_qad, cap_rows, long_from, **options)
@@ -943,7 +945,8 @@ class DevicePipeline:
         record for record, iq_to_bits(capture_k, p, auto_noise=..., auto_center=..., msg_records=True, message_length_divisor=...) on it
         alone; the RSSI bit for bit.  A truncated capture's message_data() raises the capacity error; .retry(k) runs it again with records.
         A noise flag 2 capture is sliced as two zeros and its records, if any, read the real capture; noise flag 0 raises where the capture
-        is handed out.  ASK and FSK; PSK (iq_to_bits_batch_psk) and dc_correction are not options of a batch (ValueError says what to call).
+        is handed out.  ASK and FSK; PSK (iq_to_bits_batch_psk) and dc_correction (iq_to_bits_batch_dc) are not options of a batch (ValueError says
+        what to call).
         p where it is not known: estimate_batch gives it per capture."""
         from .batch import iq_to_bits_batch_records
         return iq_to_bits_batch_records(self, captures, p, message_length_divisor, auto_noise, auto_center, center_max_size, want_qad, cap_rows, long_from,
@@ -963,11 +966,43 @@ class DevicePipeline:
         behind the walk (as iq_to_bits_batch_records; three launches and one copy more).
         Returns a batch.BatchBits; capture k equals iq_to_bits(capture_k, p, want_qad=True, auto_noise=..., auto_center=..., msg_records=...)
         on that capture alone, bit for bit, .qad(k) included.  .retry(k) runs a truncated capture again through this entry point.
-        PSK alone (ValueError names iq_to_bits_batch and its siblings for ASK / FSK); dc_correction is not an option of a batch; an unknown option
-        is a TypeError -- all before a device is touched."""
+        PSK alone (ValueError names iq_to_bits_batch and its siblings for ASK / FSK); dc_correction is not an option of a batch (ValueError names
+        iq_to_bits_batch_dc, which takes PSK parameters too); an unknown option is a TypeError -- all before a device is touched."""
         from .batch import iq_to_bits_batch_psk
         return iq_to_bits_batch_psk(self, captures, p, auto_noise, auto_center, center_max_size, message_length_divisor, want_qad, cap_rows, long_from,
                                     **options)
+
+    def dc_correct_batch(self, captures, want_means=False):
+        """DC correction of every capture of a batch (include/urhgpu.h "a batch of captures: DC correction per capture"): capture k minus
+        np.mean(capture_k, axis=0), bit for bit numpy's expression and filter.dc_correct_dev on that capture alone -- for float32 captures
+        that includes numpy's strictly sequential column sum --, in TWO launches whatever the number of captures.
+        captures: the three input forms of iq_to_bits_batch, the five sample types.  Host captures are uploaded once and corrected in place
+        in that upload; a caller's device tensors are never modified.
+        Returns (iq_cat, starts): a device tensor (total, 2) of the sample type and K + 1 sample indices, capture k =
+        iq_cat[starts[k]:starts[k + 1]] -- itself the third input form: it feeds iq_to_bits_batch and its siblings, detect_noise_levels,
+        estimate_batch and segment_messages_batch unchanged.  For captures given as (iq_cat, starts) the result has the same geometry, and
+        what lies between the captures is not written.  want_means: also the means as a numpy array [K, 2] (float32 for float32 captures,
+        float64 otherwise; NaN for an empty capture) -- the one thing here that waits for the device."""
+        from .batch import dc_correct_batch
+        return dc_correct_batch(self, captures, want_means)
+
+    def iq_to_bits_batch_dc(self, captures, p: DemodParams, auto_noise=False, auto_center=False, center_max_size=None, message_length_divisor=None,
+                            want_qad=False, cap_rows=None, long_from=None, **options):
+        """A batch over captures minus their own means, as iq_to_bits(..., dc_correction=True) is a pass over one: dc_correct_batch corrects the
+        short captures in one buffer on the device, and the matching batch -- iq_to_bits_batch, iq_to_bits_batch_auto (auto_noise),
+        iq_to_bits_batch_center (auto_center), iq_to_bits_batch_records (message_length_divisor not None) or, for PSK parameters,
+        iq_to_bits_batch_psk -- runs on that buffer: two launches more than the same batch without the correction, whatever the number of
+        captures.  Everything downstream reads the corrected capture: the noise threshold, the center, the records' RSSI.
+        captures, want_qad, cap_rows, long_from, center_max_size: as for those methods; a capture of long_from samples or more goes through
+        iq_to_bits(..., dc_correction=True) with the same options.
+        Returns a batch.BatchBits that also carries .means (numpy [K, 2]: what was taken off every capture) beside what the matching batch
+        gives (.noise / .noise_flags, .centers / .center_flags, the records).  Capture k equals iq_to_bits(capture_k, p, dc_correction=True,
+        auto_noise=..., auto_center=..., msg_records=...) on it alone, bit for bit, .qad(k) and the records included.  .retry(k) corrects a
+        truncated capture again and runs it alone through this entry point.  The captures themselves are not modified.
+        An unknown option is a TypeError, a divisor below 1 a ValueError -- before a device is touched."""
+        from .batch import iq_to_bits_batch_dc
+        return iq_to_bits_batch_dc(self, captures, p, auto_noise, auto_center, center_max_size, message_length_divisor, want_qad, cap_rows, long_from,
+                                   **options)
 
     def costas_demod_batch(self, captures, p: DemodParams, noise=None):
         """The Costas launch of iq_to_bits_batch_psk alone (urhgpu_batch_costas_dev): afp_demod with PSK of every capture of a batch (the three

@@ -130,14 +130,19 @@ def get_protocol_from_signal_dev(pipe, iq, p, message_length_divisor=1, sample_r
 
 
 def get_protocols_from_signals_dev(pipe, captures, p, message_length_divisor=1, sample_rate=1e6, timestamps=None, auto_noise=False, auto_center=False,
-                                   center_max_size=None, cap_rows=None, long_from=None):
+                                   center_max_size=None, cap_rows=None, long_from=None, dc_correction=False):
     """get_protocol_from_signal_dev for a recording session: captures as DevicePipeline.iq_to_bits_batch takes them (a list of numpy arrays
     or device tensors, or (iq_cat, starts)), one parameter set for all.  One batch with its records queued behind it
     (DevicePipeline.iq_to_bits_batch_records); a capture whose pulse table outgrew its capacity is run once more with the rows it needs.
     timestamps: one per capture, default 0.0.  Returns a list of MessageData lists, one per capture in the order given.
-    PSK parameters take DevicePipeline.iq_to_bits_batch_psk with the same options."""
+    PSK parameters take DevicePipeline.iq_to_bits_batch_psk with the same options.
+    dc_correction: every capture minus its own means, corrected on the device in front of the batch (DevicePipeline.iq_to_bits_batch_dc, for
+    every modulation a batch takes)."""
     from .batch import is_psk
-    if is_psk(p):
+    if dc_correction:
+        res = pipe.iq_to_bits_batch_dc(captures, p, auto_noise=auto_noise, auto_center=auto_center, center_max_size=center_max_size,
+                                       message_length_divisor=message_length_divisor, cap_rows=cap_rows, long_from=long_from)
+    elif is_psk(p):
         res = pipe.iq_to_bits_batch_psk(captures, p, auto_noise=auto_noise, auto_center=auto_center, center_max_size=center_max_size,
                                         message_length_divisor=message_length_divisor, cap_rows=cap_rows, long_from=long_from)
     else:
