@@ -1,4 +1,4 @@
-"""Inputs of the tests of the batch's DC correction (tests/test_batch_dc_host.py, tests/test_batch_dc_gpu.py; urh_amd/batch.py
+"""Inputs of the tests of the batch's DC correction (tests/test_batch_dc_host.py, tests/test_batch_dc_gpu.py; urh_amd/batch/
 dc_correct_batch, iq_to_bits_batch_dc), each built once and read-only.  The expected values are numpy's own expression per capture
 (dc_cases.numpy_dc) -- never the code under test."""
 import functools

@@ -1,4 +1,4 @@
-"""Seeded PSK captures and the oracle's results for the tests of the PSK batch (tests/test_batch_psk_gpu.py; urh_amd/batch.py
+"""Seeded PSK captures and the oracle's results for the tests of the PSK batch (tests/test_batch_psk_gpu.py; urh_amd/batch/
 iq_to_bits_batch_psk).  The generator follows the recipe of tests/test_costas_shard.py::psk_capture: PSK at 100 samples per symbol with a
 carrier offset, AWGN, gated gaps at 1 % amplitude, and the integer sample types with their thresholds."""
 import numpy as np

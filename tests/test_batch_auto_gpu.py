@@ -1,4 +1,4 @@
-"""DevicePipeline.iq_to_bits_batch_auto and detect_noise_levels (urh_amd/batch.py, urh_amd/csrc/batch_auto.hip; include/urhgpu.h "a batch of
+"""DevicePipeline.iq_to_bits_batch_auto and detect_noise_levels (urh_amd/batch/, urh_amd/csrc/batch_auto.hip; include/urhgpu.h "a batch of
 captures: automatic noise threshold per capture") against the oracle: every capture of a batch comes back with the threshold that
 detect_noise_level gives for it alone and with the pulse table, bits, offsets, pauses and demodulated signal of the reference gated with
 THAT threshold, whatever lies beside it in the buffer.  Every result is compared with the oracle (noise_cases.oracle_threshold /

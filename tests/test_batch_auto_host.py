@@ -1,4 +1,4 @@
-"""The host side of a batch with an automatic noise threshold per capture (urh_amd/csrc/batch_auto.hip, urh_amd/batch.py; include/urhgpu.h
+"""The host side of a batch with an automatic noise threshold per capture (urh_amd/csrc/batch_auto.hip, urh_amd/batch/; include/urhgpu.h
 "a batch of captures: automatic noise threshold per capture"): the kernel's summation order against numpy, the model of the whole kernel
 against the oracle and the real reference's fixture, the option errors, and the code objects' metadata.  No GPU needed."""
 import math

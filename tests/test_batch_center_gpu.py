@@ -1,4 +1,4 @@
-"""DevicePipeline.iq_to_bits_batch_center, detect_centers and qad_to_bits_batch (urh_amd/batch.py, urh_amd/csrc/batch_center.hip;
+"""DevicePipeline.iq_to_bits_batch_center, detect_centers and qad_to_bits_batch (urh_amd/batch/, urh_amd/csrc/batch_center.hip;
 include/urhgpu.h "a batch of captures: automatic center per capture") against the oracle: every capture of a batch comes back with the
 center detect_center gives for its own demodulated signal and with the pulse table, bits, offsets, pauses, positions and demodulated
 signal of the reference sliced with THAT center, whatever lies beside it in the buffer -- and with what DevicePipeline.iq_to_bits(...,

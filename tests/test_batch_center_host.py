@@ -1,4 +1,4 @@
-"""The host side of a batch with an automatic center per capture (urh_amd/csrc/batch_center.hip, urh_amd/batch.py; include/urhgpu.h "a
+"""The host side of a batch with an automatic center per capture (urh_amd/csrc/batch_center.hip, urh_amd/batch/; include/urhgpu.h "a
 batch of captures: automatic center per capture"): the option errors, the size / plan call against a restatement, the numpy model of the
 pass against the oracle and the real reference's fixture, the slicing thresholds against the library's host arithmetic, and the code
 objects' metadata.  No GPU needed."""

@@ -1,4 +1,4 @@
-"""DevicePipeline.dc_correct_batch and iq_to_bits_batch_dc (urh_amd/batch.py; include/urhgpu.h "a batch of captures: DC correction per
+"""DevicePipeline.dc_correct_batch and iq_to_bits_batch_dc (urh_amd/batch/; include/urhgpu.h "a batch of captures: DC correction per
 capture") on the GPU.  Expected values: numpy's own expression per capture (dc_cases.numpy_dc) for the correction, and the existing
 single-capture paths -- iq_to_bits, get_protocol_from_signal_dev, estimate_dev -- over numpy-corrected captures for everything built on it;
 never the code under test.  The inputs come from tests/batch_dc_cases.py, where tests/test_batch_dc_host.py holds them against the oracle."""

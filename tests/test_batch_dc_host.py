@@ -1,4 +1,4 @@
-"""The host side of the batch's DC correction (urh_amd/batch.py dc_correct_batch, iq_to_bits_batch_dc; include/urhgpu.h "a batch of captures:
+"""The host side of the batch's DC correction (urh_amd/batch/ dc_correct_batch, iq_to_bits_batch_dc; include/urhgpu.h "a batch of captures:
 DC correction per capture"): the option errors, raised before a device is touched; the older entry points' refusals, which now name the new
 method; the C ABI's refusals; the conditions on the inputs of tests/test_batch_dc_gpu.py, checked with the oracle; and the code objects'
 metadata of batch_dc.hip.  No GPU needed."""

@@ -378,7 +378,7 @@ def test_c4_blobs_beyond_the_first_host_buffer_take_a_second_fetch(oracle):
     pp = np.asarray(oracle.grab_pulse_lens(qad, 0.0, 0, "FSK", 8, 1, 1.0)).reshape(-1, 2)
     flat = oracle.ppseq_to_bits_flat(pp, 8, 1, True, 8)
     one = B.blob_bytes(len(pp), len(flat[2]), len(flat[0]))
-    # (the pinned buffer is made a quarter larger than asked for -- urh_amd/batch.py::_pinned --: the first fetch is refused from 10 MiB on, so
+    # (the pinned buffer is made a quarter larger than asked for -- urh_amd/batch/staging.py::_pinned --: the first fetch is refused from 10 MiB on, so
     # the total is taken 35 % above the constant, which is "at least 10 %" as well)
     m = -(-(first + first // 4 + first // 10) // one) + 1
     total = m * one

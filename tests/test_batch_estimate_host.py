@@ -1,4 +1,4 @@
-"""The host side of the estimate of a session (urh_amd/batch.py: estimate_batch, segment_messages_batch; urh_amd/csrc/batch_estimate.hip;
+"""The host side of the estimate of a session (urh_amd/batch/: estimate_batch, segment_messages_batch; urh_amd/csrc/batch_estimate.hip;
 include/urhgpu.h "a batch of captures: message ranges per capture"): the numpy model of the kernel's step-and-run walk against the recorded
 reference ranges and the oracle, the factored vote function against the reference's estimates, the code objects' metadata of the new
 kernels, and the option checks.  No GPU needed."""

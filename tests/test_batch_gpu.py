@@ -1,4 +1,4 @@
-"""DevicePipeline.iq_to_bits_batch (urh_amd/batch.py; include/urhgpu.h "a batch of captures") against the oracle: every capture of a batch
+"""DevicePipeline.iq_to_bits_batch (urh_amd/batch/; include/urhgpu.h "a batch of captures") against the oracle: every capture of a batch
 comes back with the pulse table, bits, offsets, pauses, positions, position offsets and demodulated signal that oracle.afp_demod ->
 grab_pulse_lens -> ppseq_to_bits_flat give for that capture alone, whatever lies beside it in the buffer.  The exactness tests run with
 cap_rows="bound" (the default policy does overflow for ordinary inputs, which has a test of its own) and assert that NO capture was

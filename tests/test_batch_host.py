@@ -1,4 +1,4 @@
-"""The host side of a batch of captures (urh_amd/batch.py, urhgpu_batch_plan; include/urhgpu.h "a batch of captures"): sizing, launch
+"""The host side of a batch of captures (urh_amd/batch/, urhgpu_batch_plan; include/urhgpu.h "a batch of captures"): sizing, launch
 order, routing, the result sequence over blobs built here with numpy from oracle results, the option errors, and the code objects'
 metadata of the batch kernels.  No GPU needed."""
 import os

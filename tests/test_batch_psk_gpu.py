@@ -1,4 +1,4 @@
-"""DevicePipeline.iq_to_bits_batch_psk and costas_demod_batch (urh_amd/batch.py; include/urhgpu.h "a batch of captures: PSK") against the
+"""DevicePipeline.iq_to_bits_batch_psk and costas_demod_batch (urh_amd/batch/; include/urhgpu.h "a batch of captures: PSK") against the
 oracle: every capture of a batch comes back with the demodulated signal (as uint32, element 0 = -4), pulse table, bits, offsets, pauses
 and positions that oracle.afp_demod(.., "PSK", ..) -> grab_pulse_lens -> ppseq_to_bits_flat give for that capture alone, whatever shares
 its wavefront; with automatic noise, automatic center and records, what the single pass iq_to_bits gives on that capture alone.  The

@@ -1,4 +1,4 @@
-"""The host side of the PSK batch (urh_amd/batch.py iq_to_bits_batch_psk, costas_demod_batch; include/urhgpu.h "a batch of captures: PSK"):
+"""The host side of the PSK batch (urh_amd/batch/ iq_to_bits_batch_psk, costas_demod_batch; include/urhgpu.h "a batch of captures: PSK"):
 the option errors, raised before a device is touched; the older entry points' refusals, which now name the new method; the C ABI's
 refusals; and the code objects' metadata of k_batch_costas.  No GPU needed."""
 import ctypes as C

@@ -2,7 +2,7 @@
 the ordered names of the urhgpu_* functions called (the Context's methods included; plain integer flags where they are no addresses), the
 pipeline's device and pinned buffers afterwards as {key: elements}, the host counts and the noise / center flags.  The other tests compare
 results bit for bit; they do not see a host wait, a second launch, or a buffer that changed its size or its name -- as
-tests/test_shard_call_trace.py has it for the sharded orchestration.  The traces were recorded with this file's recorder against the
+tests/test_shard_call_trace.py has it for the sharded orchestration.  The traces were recorded with tests/call_trace.py's recorder against the
 pipeline.py / shard_engine.py whose repeated blocks the shared helpers replaced.
 
 The scenarios: a one-shot pass and a CaptureStream (four pushes and the flush) -- plain, without the demodulated signal, auto_center with
@@ -13,7 +13,6 @@ Signal.get_protocol twice and one GpuShardEngine pass of a single rank with host
 
 `PYTHONPATH=.:oracle python tests/test_pipeline_call_trace.py` rewrites the fixture from the code as it is -- only from a commit whose calls
 are known good."""
-import contextlib
 import dataclasses
 import json
 import os
@@ -25,60 +24,19 @@ import center_cases as cc
 import dc_cases
 import msg_record_cases as mc
 import noise_cases as nc
+from call_trace import recording, trace
 from conftest import synth_fsk
 
 pytestmark = pytest.mark.gpu
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pipeline_trace", "traces.json")
 DIVISOR = 8
-# when a pipeline or a stream is let go of is the garbage collector's business, not a pass's
-UNORDERED = ("urhgpu_ctx_destroy", "urhgpu_stream_destroy")
 # the arguments that are plain integers (flags, lengths, capacities), by position; never an address or a size made from one
 INT_ARGS = {"urhgpu_ctx_set_pipelined": (1,), "urhgpu_ctx_set_tuning": (1, 2), "urhgpu_iq_to_bits_dev": (2,), "urhgpu_iq_to_bits_auto_center_dev": (2, 4),
             "urhgpu_iq_to_bits_auto_dev": (2, 4, 5, 6), "urhgpu_grab_pulse_lens_dev": (2, 5), "urhgpu_ppseq_to_bits_dev": (3,),
             "urhgpu_msg_records_dev": (2, 5, 7), "urhgpu_blob_capacity": (0, 1, 2, 3, 4), "urhgpu_outputs_to_host": (2,),
             "urhgpu_stream_create": (1, 3, 4, 5), "urhgpu_stream_set_msg_records": (1, 2), "urhgpu_stream_set_auto_noise": (1,),
             "urhgpu_stream_set_auto_center": (1, 2), "urhgpu_stream_push": (2,)}
-
-
-class Recorder:
-    """forwards to the loaded library and notes the name of every urhgpu_* function called, with its plain integer arguments"""
-
-    def __init__(self, lib):
-        self.__dict__.update(_lib=lib, log=[])
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith("urhgpu_") or name in UNORDERED:
-            return fn
-
-        def call(*args):
-            plain = [args[i].decode() if isinstance(args[i], bytes) else int(args[i]) for i in INT_ARGS.get(name, ())]
-            self.log.append(" ".join([name] + [str(v) for v in plain]))
-            return fn(*args)
-        return call
-
-
-@contextlib.contextmanager
-def recording():
-    """_lib.load() hands out the recorder: every call of the package into the library, Context's methods included, goes through it"""
-    from urh_amd import _lib
-    _lib.host_libm_verdict()                                   # (once per process, whoever comes first: not a pass's call)
-    real = _lib.load
-    rec = Recorder(real())
-    _lib.load = lambda: rec
-    try:
-        yield rec
-    finally:
-        _lib.load = real
-
-
-def sizes(d):
-    return {str(k): int(v.numel()) for k, v in d.items() if hasattr(v, "numel")}
-
-
-def trace(rec, pipe, results):
-    return {"calls": list(rec.log), "bufs": sizes(pipe._bufs), "pinned": sizes(pipe._pinned), "results": results}
 
 
 def to_dev(pipe, iq):
@@ -235,7 +193,7 @@ def scenarios():
 
 
 def all_traces():
-    with recording() as rec:
+    with recording(INT_ARGS) as rec:
         return json.loads(json.dumps({name: run(rec) for name, run in scenarios().items()}))
 
 

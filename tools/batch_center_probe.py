@@ -112,20 +112,19 @@ def fmt(v):
 
 
 def measure(pipe, p, k, n, rounds, out):
-    from urh_amd import batch
-    from urh_amd.batch import launch_counts
+    from urh_amd.batch import center, launch_counts
     dev = pipe.device
     paths = Paths(pipe, p, captures(k, n, p.modulation_type), n)
     n_bits, n_trunc, flags, centers = paths.verify()
     host = []
-    settle = batch._settle_centers
+    settle = center._settle_centers                          # (looked up in urh_amd/batch/center.py by the function that calls it)
 
     def timed_settle(*a, **kw):                              # the host's share of one A: numpy on the tied histograms
         t0 = time.perf_counter()
         r = settle(*a, **kw)
         host.append((time.perf_counter() - t0) * 1e3)
         return r
-    batch._settle_centers = timed_settle
+    center._settle_centers = timed_settle
     for fn in (paths.a, paths.b, paths.c):                   # warm-up (buffers grown, pinned memory there)
         timed(fn, dev)
     a, b, c = [], [], []
@@ -136,7 +135,7 @@ def measure(pipe, p, k, n, rounds, out):
         b.append(timed(paths.b, dev))
         c.append(timed(paths.c, dev))
     paths.close()
-    batch._settle_centers = settle
+    center._settle_centers = settle
     host = host[-rounds:] or [0.0]
     ma, mb, mc = statistics.median(a), statistics.median(b), statistics.median(c)
     line = (f"{p.modulation_type} {k:6d} x {n:8d}  A batch_center {fmt(a)} ms  B stream auto_noise+auto_center {fmt(b)} ms  C batch_auto {fmt(c)} ms  B/A {mb / ma:6.2f}  "

@@ -13,7 +13,7 @@ tables are compared before anything is timed.
 
     set (a) 4096 x 16 384 float32   (b) 4096 x 16 384 int16   (c) 512 x 131 072   (d) 341 x 196 608   (e) 256 x 262 144   (c - e: float32)
 
-The table is read for B / A, for B - B0, and for the length at which a capture should leave the batch (urh_amd/batch.py LONG_FROM_DEFAULT;
+The table is read for B / A, for B - B0, and for the length at which a capture should leave the batch (urh_amd/batch/inputs.py LONG_FROM_DEFAULT;
 DESIGN.md 7.7k)."""
 import argparse
 import os

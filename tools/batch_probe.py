@@ -9,7 +9,7 @@ arrays; results on the host for both paths; both paths' bits and pulse tables ar
     set (a)  4096 captures of 16 384 samples      set (b)  512 of 262 144      set (c)  64 of 2^21
 
 --search N: N more lengths by halving (in log2) between the two neighbouring lengths that straddle B / A = 1: the crossover, which is
-DevicePipeline.iq_to_bits_batch's default `long_from` (urh_amd/batch.py LONG_FROM_DEFAULT).
+DevicePipeline.iq_to_bits_batch's default `long_from` (urh_amd/batch/inputs.py LONG_FROM_DEFAULT).
 --only-batch: path A alone, once per set after a warm-up (for a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/batch_probe.py
 --only-batch --sets a)."""
 import argparse

@@ -10,7 +10,7 @@ pulse tables are compared before anything is timed.
     set (a) 4096 x 8192    (b) 4096 x 16 384    (c) 1024 x 65 536    (d) 341 x 196 608    (e) a small session: 64 x 16 384
 
 A's cost follows the LONGEST capture (the loop is serial, about 0.4 us per sample), B's the NUMBER of captures: the table is read for the
-length at which a PSK capture should leave the batch (urh_amd/batch.py LONG_FROM_DEFAULT).
+length at which a PSK capture should leave the batch (urh_amd/batch/inputs.py LONG_FROM_DEFAULT).
 --only-batch: path A alone, once per set after a warm-up (for a kernel trace: rocprofv3 --kernel-trace --stats -- python
 tools/batch_psk_probe.py --only-batch --sets a)."""
 import argparse

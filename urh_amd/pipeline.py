@@ -870,7 +870,7 @@ class DevicePipeline:
         return res
 
     def iq_to_bits_batch(self, captures, p: DemodParams, want_qad=False, cap_rows=None, long_from=None, **options):
-        """Many captures in one pass (urh_amd/batch.py; include/urhgpu.h "a batch of captures"): one upload, three launches whatever the
+        """Many captures in one pass (urh_amd/batch/; include/urhgpu.h "a batch of captures"): one upload, three launches whatever the
         number of captures, one download.  For the short captures of a recording session, where a pass per capture is all fixed cost; long
         captures still belong to passes and streams.
         captures: a list of numpy arrays ((N, 2) of one of the five sample types, or complex64 (N,)) -- packed into ONE pinned staging buffer
