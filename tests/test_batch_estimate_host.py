@@ -163,8 +163,11 @@ def test_option_checks_need_no_device():
     assert noises == [0.5] * 3 and mods == ["OOK"] * 3
     noises, mods = batch.check_estimate_options(2, np.int16, [0.1, None], ["FSK", None])
     assert noises == [0.1, None] and mods == ["FSK", None]
-    for dt in (np.uint8, np.uint16):
-        with pytest.raises(ValueError, match="float32, int8 and int16"):
+    for dt in (np.uint8, np.uint16):               # admitted since tests/test_estimate_routes_gpu.py holds estimate_dev to the reference on them
+        assert batch.check_estimate_options(1, dt, None, None) == ([None], [None])
+    assert [np.dtype(t).name for t in batch.ESTIMATE_SAMPLE_TYPES] == ["float32", "int8", "int16", "uint8", "uint16"]
+    for dt in (np.float64, np.int32, np.uint32, np.complex64):
+        with pytest.raises(ValueError, match="float32, int8, uint8, int16 and uint16 captures, not " + np.dtype(dt).name):
             batch.check_estimate_options(1, dt, None, None)
     with pytest.raises(ValueError, match="Unsupported Modulation"):
         batch.check_estimate_options(1, np.float32, None, "QAM")

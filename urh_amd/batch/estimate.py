@@ -13,16 +13,16 @@ from .staging import _pinned, batch_plan, captures_at, detect_noise, order_param
 MSG_GROUP = 4096
 
 _ESTIMATE_MODULATIONS = ("OOK", "ASK", "FSK", "PSK")
-# estimators.estimate_dev agrees with the reference on these sample types here (tests/test_gpu_parity.py); uint8 and uint16 are not covered
-# by such a test, so a session of them is refused instead of estimated unchecked
-ESTIMATE_SAMPLE_TYPES = (np.float32, np.int8, np.int16)
+# estimators.estimate_dev agrees with the reference on these sample types (tests/test_gpu_parity.py; tests/test_estimate_routes_gpu.py for the
+# unsigned ones, which the reference takes as they stand: magnitudes around the middle of the range, uint16 squares that wrap in C int)
+ESTIMATE_SAMPLE_TYPES = (np.float32, np.int8, np.int16, np.uint8, np.uint16)
 
 
 def check_estimate_options(k, npdt, noise, modulation):
     """(noise per capture, modulation per capture) of estimate_batch, or ValueError with a sentence (host arithmetic: no GPU needed)"""
     if np.dtype(npdt) not in [np.dtype(t) for t in ESTIMATE_SAMPLE_TYPES]:
-        raise ValueError(f"estimate_batch takes float32, int8 and int16 captures, not {np.dtype(npdt).name}: estimate_dev is not verified against the "
-                         "reference on that sample type")
+        raise ValueError(f"estimate_batch takes float32, int8, uint8, int16 and uint16 captures, not {np.dtype(npdt).name}: estimate_dev is not verified "
+                         "against the reference on that sample type")
 
     def check_mod(m):
         if m is not None and m not in _ESTIMATE_MODULATIONS:

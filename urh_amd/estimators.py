@@ -139,7 +139,13 @@ def segment_messages_dev(pipe, iq, noise_threshold: float, as_array: bool = Fals
     return seg if as_array else _as_tuples(seg)
 
 
-def message_ranges_dev(pipe, iq, noise_threshold: float, merge: bool = True, cap_seg: int = 4096, cap_merged: int = 65536, qad_ask=None):
+# what estimate_dev's first urhgpu_message_ranges_dev call has room for: segments (modulation detection looks at the first 100) and merged
+# OOK messages.  A capture that holds more is read in a second call with room for the count the first one reported.
+CAP_SEG = 4096
+CAP_MERGED = 65536
+
+
+def message_ranges_dev(pipe, iq, noise_threshold: float, merge: bool = True, cap_seg: int = CAP_SEG, cap_merged: int = CAP_MERGED, qad_ask=None):
     """Segmentation and (optionally) the OOK merge without the per-pulse table leaving the GPU (urhgpu_message_ranges_dev).
     Returns (segments[:cap_seg], n_segments, merged[:cap_merged] or None, n_merged, ambiguous): (K, 2) int64 arrays as
     segment_messages_dev(as_array=True) / merge_message_segments_for_ook give them, truncated to the capacities.
@@ -696,7 +702,7 @@ def estimate_dev(pipe, iq, noise: float = None, modulation: str = None, timings:
     data = None
     if modulation in ("OOK", "ASK") and iq.dtype == torch.float32 and int(iq.shape[0]) > 0 and float(noise) == float(noise):
         data = torch.empty(int(iq.shape[0]), dtype=torch.float32, device=iq.device)
-    segments, n_segments, merged, n_merged, ambiguous = message_ranges_dev(pipe, iq, noise, qad_ask=data)
+    segments, n_segments, merged, n_merged, ambiguous = message_ranges_dev(pipe, iq, noise, cap_seg=CAP_SEG, cap_merged=CAP_MERGED, qad_ask=data)
     lap("segment_messages_ms")
     if modulation is None:
         modulation = detect_modulation_for_messages_dev(iq, segments[:100].tolist(), pipe=pipe)

@@ -1046,8 +1046,8 @@ class DevicePipeline:
         noise_k, modulation_k).  The captures' messages are pooled: noise floors (k_batch_noise), message ranges (k_batch_segments), the
         modulation vote, the demodulation (once per modulation present) and the center / tolerance / bit-length decisions each serve all
         captures at once, and the number of native calls depends on ceil(messages / batch.MSG_GROUP), never on the number of captures.
-        captures: the three input forms of iq_to_bits_batch; float32, int8 and int16 samples (the types estimate_dev is verified on; uint8
-        and uint16 are refused with a ValueError).
+        captures: the three input forms of iq_to_bits_batch; float32, int8, uint8, int16 and uint16 samples (the types estimate_dev is
+        verified on; an unsigned sample counts as it stands, as in the reference).
         noise: None -- detect_noise_level per capture --, one float, or one float (or None) per capture.  The estimate uses the value whatever
         the sample type's max_magnitude is.
         modulation: None -- a vote per capture over its first 100 messages --, "OOK", "ASK", "FSK", "PSK", or one of these (or None) per capture.
