@@ -1375,6 +1375,63 @@ int urhgpu_iq_to_bits_batch_psk_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t t
 int urhgpu_batch_dc_correct_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, int dtype, const int64_t *d_start, const int64_t *d_plan,
                                 int64_t k, void *d_out, void *d_mean);
 
+/* ---- a batch of captures: parameters per capture ------------------------------------------------------------------------------------
+ * Every batch entry point above takes ONE urhgpu_params for all captures.  A recording session's transmitters are not alike, and the
+ * reference opens each file with its own Signal parameters (ProtocolAnalyzer.get_protocol_from_signal per file): estimated centers and noise
+ * floors are floats that differ in every capture, so grouping by equal parameters is a batch per capture.  Here capture c is demodulated,
+ * sliced and turned into bits -- and, on request, message records -- with table[c], and the launch count depends neither on k nor on the
+ * number of different parameter sets.  Capture c's results are those of urhgpu_iq_to_bits_dev (records: urhgpu_msg_records_dev behind it) on
+ * that capture alone with its parameters, bit for bit, the demodulated signal and the RSSI included (urh_amd/csrc/batch_each.hip).
+ *   Table    urhgpu_batch_each[k] in device memory, 16-byte aligned, 32 bytes per capture: the modulation (URHGPU_MOD_ASK or _FSK),
+ *            bits_per_symbol (1 .. 7), samples_per_symbol (>= 1), tolerance (0 .. 65535), pause_threshold, noise_val (0 for ASK, -4 for
+ *            FSK: get_noise_for_mod_type) and thr_first, the index of the capture's first slicing threshold in ONE shared table
+ *            d_thr = float[n_thr], n_thr = the sum of (1 << bits_per_symbol) - 1 over the captures, which the host fills with
+ *            urhgpu_get_center_thresholds(center_c, center_spacing_c, 1 << bits_per_symbol_c, d_thr + thr_first_c).  The wavefront of
+ *            capture c loads its record and its thresholds through uniform addresses and reads no other capture's.  A record the device
+ *            does not accept -- a value outside these ranges, thresholds that do not lie inside [0, n_thr), a noise_val that is not its
+ *            modulation's, a modulation other than that of the launch its plan position falls in -- makes capture c a refused capture
+ *            (truncated bit 3: nothing of it is read or stored, a well-formed empty blob); the other captures are not affected.
+ *   Noise    d_noise: urhgpu_noise_result[k], 8-byte aligned, always read: capture c is gated with block c's noise_sqrd.  auto_noise 0:
+ *            the CALLER has written the blocks -- flag 1, noise_f32 = (float)noise_threshold_c, noise_sqrd its fp32 square; flag 2 where the
+ *            threshold is not below the sample type's max_magnitude (walked as two zeros).  auto_noise not 0: urhgpu_batch_noise_dev's
+ *            launch runs in front and writes them; the flag protocol of urhgpu_iq_to_bits_batch_auto_dev.
+ *   Plan     urhgpu_batch_plan_each (host arithmetic, works without a GPU): urhgpu_batch_plan with tolerance, samples_per_symbol and
+ *            bits_per_symbol of each capture's own record (a host copy of the table): region c has the size of that capture's own values.
+ *            The launch order holds the ASK captures first, then the FSK captures, each group longest first -- a permutation; a uniform
+ *            table gives exactly urhgpu_batch_plan's output.
+ *   Pass     urhgpu_iq_to_bits_batch_each_dev: asynchronous on the context's stream, the caller owns all memory, nothing is copied.  n_ask:
+ *            the number of ASK records (the first n_ask positions of the launch order).  Launches whatever k, the lengths and the parameter
+ *            sets are: ONE walk per modulation present (at most two; modulation is a template parameter of the walk, captures of every
+ *            order share a launch), scan, pack -- and one more in front with auto_noise.  The other arguments, the counts, the directory,
+ *            the blobs and the truncation protocol are those of urhgpu_iq_to_bits_batch_dev; fetched with urhgpu_batch_fetch (and
+ *            urhgpu_batch_noise_fetch).  No load leaves [d_start[c], d_start[c + 1]), no store leaves capture c's region.
+ *   Records  urhgpu_batch_msg_records_each_dev: urhgpu_batch_msg_records_dev (no map) behind that pass, three launches: positions from
+ *            capture c's samples_per_symbol, bits_per_symbol, pause_threshold and int(samples_per_symbol / bits_per_symbol), the padding to
+ *            message_length_divisor only where record c is ASK, the RSSI window [mid_pos, mid_pos + samples_per_symbol_c) clipped at the end
+ *            of its OWN capture.  Fetched with urhgpu_batch_records_fetch.
+ *   Rejected before anything is launched: a sample type: URHGPU_ERR_DTYPE; a negative size, n_ask outside [0, k], a misaligned pointer, a
+ *   missing context or buffer: URHGPU_ERR_ARG.  urhgpu_batch_plan_each: a record outside the ranges above: URHGPU_ERR_ARG, bits_per_symbol
+ *   above 7 or a modulation other than ASK / FSK: URHGPU_ERR_UNSUPPORTED.
+ * urhgpu_batch_launches counts these launches too. */
+typedef struct urhgpu_batch_each {
+    int32_t mod;                 /* URHGPU_MOD_ASK or URHGPU_MOD_FSK */
+    int32_t bits_per_symbol;     /* 1 .. 7 */
+    uint32_t samples_per_symbol; /* >= 1 */
+    int32_t tolerance;           /* 0 .. 65535 */
+    int64_t pause_threshold;
+    float noise_val;             /* 0 for ASK, -4 for FSK */
+    int32_t thr_first;           /* the capture's (1 << bits_per_symbol) - 1 thresholds are d_thr[thr_first ..] */
+} urhgpu_batch_each;
+int urhgpu_batch_plan_each(const int64_t *lengths, int64_t k, const urhgpu_batch_each *each, int policy, int64_t cap_rows_fixed, int64_t *plan,
+                           int64_t *work_bytes, int64_t *blob_capacity);
+int urhgpu_iq_to_bits_batch_each_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, int dtype, const int64_t *d_start, const int64_t *d_plan, int64_t k,
+                                     const urhgpu_batch_each *d_each, const float *d_thr, int64_t n_thr, int64_t n_ask, int auto_noise, float *d_qad,
+                                     void *d_work, int64_t work_bytes, int64_t *d_counts, int64_t *d_dir, void *d_blob, int64_t cap_blob,
+                                     urhgpu_noise_result *d_noise);
+int urhgpu_batch_msg_records_each_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total, int dtype, const int64_t *d_start, const int64_t *d_plan, int64_t k,
+                                      const urhgpu_batch_each *d_each, int64_t message_length_divisor, const void *d_work, int64_t work_bytes,
+                                      const int64_t *d_counts, int64_t *d_rec_dir, void *d_rec, int64_t cap_rec, int32_t *d_rec_capture);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,12 @@ class NoiseResult(C.Structure):
                 ("n_chunks", C.c_int64), ("n_candidates", C.c_int64), ("min_mean", C.c_double), ("max_mean", C.c_double)]
 
 
+class BatchEach(C.Structure):
+    """struct urhgpu_batch_each (include/urhgpu.h): a capture's record of the per-capture parameter table, 32 bytes"""
+    _fields_ = [("mod", C.c_int32), ("bits_per_symbol", C.c_int32), ("samples_per_symbol", C.c_uint32), ("tolerance", C.c_int32),
+                ("pause_threshold", C.c_int64), ("noise_val", C.c_float), ("thr_first", C.c_int32)]
+
+
 class MsgRecord(C.Structure):
     """struct urhgpu_msg_record (include/urhgpu.h)"""
     _fields_ = [("rssi", C.c_double), ("first_pos", C.c_int64), ("mid_pos", C.c_int64), ("n_pad", C.c_int32), ("flag", C.c_int32)]
@@ -259,6 +265,9 @@ PROTOTYPES = {
     "urhgpu_iq_to_bits_batch_psk_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(Params), _i, _i, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp,
                                              _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
     "urhgpu_batch_dc_correct_dev": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, _vp, _vp]),
+    "urhgpu_batch_plan_each": (_i, [_vp, _i64, _vp, _i, _i64, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "urhgpu_iq_to_bits_batch_each_dev": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "urhgpu_batch_msg_records_each_dev": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

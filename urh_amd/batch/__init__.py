@@ -38,12 +38,18 @@ its receive path (urh_amd/csrc/batch_dc.hip): TWO launches in front correct ever
 (for float32 captures numpy's strictly sequential column sum, a lane per capture and column), and the matching batch runs on the corrected
 buffer.  dc_correct_batch is those two launches alone; what it returns is the third input form of every batch method.  The entry points
 above keep refusing dc_correction and name this one.
+
+DevicePipeline.iq_to_bits_batch_each is the batch of a session whose transmitters are not alike (urh_amd/csrc/batch_each.hip): capture k is
+demodulated, sliced and -- on request -- given its message records with params[k], from a table of K records and one shared threshold table
+that travel in the batch's one upload.  One walk launch per modulation present (at most two), whatever the number of captures and of different
+parameter sets.  params_from_estimates turns what estimate_batch returns into that list.
 """
 from .center import TIE_POOL_COUNTS_PER_CAPTURE, batch_center_plan, center_thresholds, detect_centers
+from .each import EACH_DTYPE, batch_plan_each, each_table, iq_to_bits_batch_each, params_from_estimates
 from .estimate import ESTIMATE_SAMPLE_TYPES, MSG_GROUP, BatchEstimates, check_estimate_options, estimate_batch, segment_messages_batch
 from .inputs import LONG_FROM_DEFAULT, per_capture, route
-from .options import (as_fsk, check_batch_auto_options, check_batch_center_options, check_batch_dc_options, check_batch_options, check_batch_psk_options,
-                      check_batch_records_options, is_psk)
+from .options import (as_fsk, check_batch_auto_options, check_batch_center_options, check_batch_dc_options, check_batch_each_options, check_batch_options,
+                      check_batch_psk_options, check_batch_records_options, is_psk)
 from .psk_dc import costas_demod_batch, dc_correct_batch
 from .run import (BatchBits, detect_noise_levels, iq_to_bits_batch, iq_to_bits_batch_auto, iq_to_bits_batch_center, iq_to_bits_batch_dc, iq_to_bits_batch_psk,
                   iq_to_bits_batch_records, qad_to_bits_batch)

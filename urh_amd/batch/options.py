@@ -40,6 +40,14 @@ _NOT_IN_A_BATCH_PSK = {
 }
 
 
+_NOT_IN_A_BATCH_EACH = {
+    "auto_center": "iq_to_bits_batch_each slices every capture with the center of its own params[k] (estimated parameters already carry a center): to "
+                   "detect a center per capture call iq_to_bits_batch_center(captures, p), which takes one parameter set for all",
+    "dc_correction": "iq_to_bits_batch_each does not remove the captures' means: call dc_correct_batch(captures) first and hand what it returns, "
+                     "(iq_cat, starts), to iq_to_bits_batch_each as the captures -- two more launches, whatever the number of captures",
+}
+
+
 # the options of a batch as its entry point settled them, after its checks -- what _batch runs and what retry(k) runs again: center -- a center
 # per capture, detected with max_size, cap_tie the counts its tie pool holds (None: the default); records -- the message_length_divisor, or None
 BatchOptions = namedtuple("BatchOptions", "auto_noise center max_size cap_tie records psk dc", defaults=(False, False, None, None, None, False, False))
@@ -117,3 +125,22 @@ def check_batch_dc_options(p, message_length_divisor=None, **options):
         check_batch_options(p)
     if message_length_divisor is not None:
         _check_divisor(message_length_divisor)
+
+
+def check_batch_each_options(params, k, message_length_divisor=None, **options):
+    """what iq_to_bits_batch_each does not do raises ValueError with a sentence that says what to call instead; returns the K DemodParams, a
+    single one broadcast (host arithmetic: no GPU needed)"""
+    _refuse("iq_to_bits_batch_each", _NOT_IN_A_BATCH_EACH, options)
+    if hasattr(params, "modulation_type"):
+        params = [params] * int(k)
+    params = list(params)
+    if len(params) != int(k):
+        raise ValueError(f"params holds one DemodParams per capture ({int(k)}), or is one for all: {len(params)} were given")
+    for i, p in enumerate(params):
+        mod, _ = mod_code(p.modulation_type)
+        if mod not in (_lib.MOD_ASK, _lib.MOD_FSK):
+            raise ValueError(f"iq_to_bits_batch_each demodulates ASK and FSK, not {p.modulation_type} (params[{i}]): split the PSK captures off and call "
+                             "iq_to_bits_batch_psk(captures, p) per PSK parameter set, which runs a Costas loop per capture in one launch")
+    if message_length_divisor is not None:
+        _check_divisor(message_length_divisor)
+    return params

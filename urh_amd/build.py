@@ -13,7 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liburhgpu.so")
-SOURCES = ["demod_runs.hip", "pulse_table.hip", "filters.hip", "bandpass.hip", "modulate.hip", "plot.hip", "convert.hip", "fft_peak.hip", "spectrogram.hip", "costas.hip", "estimators.hip", "chunk_stats.hip", "msg_estimators.hip", "shard_estimators.hip", "msg_ranges.hip", "modulation.hip", "compact.hip", "msg_records.hip", "dc_correct.hip", "batch.hip", "batch_auto.hip", "batch_center.hip", "batch_records.hip", "batch_estimate.hip", "batch_psk.hip", "batch_dc.hip","stream.hip", "ctx.hip", "pass.hip", "stream_pass.hip", "shard.hip", "capi_estimators.hip", "capi_misc.hip", "capi_host.hip", "probes.hip"]
+SOURCES = ["demod_runs.hip", "pulse_table.hip", "filters.hip", "bandpass.hip", "modulate.hip", "plot.hip", "convert.hip", "fft_peak.hip", "spectrogram.hip", "costas.hip", "estimators.hip", "chunk_stats.hip", "msg_estimators.hip", "shard_estimators.hip", "msg_ranges.hip", "modulation.hip", "compact.hip", "msg_records.hip", "dc_correct.hip", "batch.hip", "batch_auto.hip", "batch_center.hip", "batch_records.hip", "batch_estimate.hip", "batch_psk.hip", "batch_dc.hip", "batch_each.hip", "stream.hip", "ctx.hip", "pass.hip", "stream_pass.hip", "shard.hip", "capi_estimators.hip", "capi_misc.hip", "capi_host.hip", "probes.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 

@@ -21,11 +21,6 @@
 
 namespace urh {
 
-__device__ __forceinline__ BlobLayout batch_blob_layout(const int64_t *cnt) {
-    const int64_t c5[5] = {cnt[0], cnt[1], cnt[2], 0, cnt[3]};
-    return blob_layout(c5, cnt[0], cnt[2], cnt[1], 0, 0);
-}
-
 // dir[i] = bytes of the blobs of the captures before i; dir[k] = all of them.  One workgroup: thread t owns a contiguous stretch.
 __global__ __launch_bounds__(256) void k_batch_scan(const BatchArgs b) {
     __shared__ int64_t part[256];
@@ -39,69 +34,6 @@ __global__ __launch_bounds__(256) void k_batch_scan(const BatchArgs b) {
     for (int j = 0; j < t; ++j) off += part[j];
     for (int64_t i = lo; i < hi; ++i) { b.dir[i] = off; off += batch_blob_layout(b.counts + kBatchCounts * i).total; }
     if (t == 255) b.dir[b.k] = off;
-}
-
-// capture c's results as a standard compact blob at dir[c]: header flags 0, int8 states, int32 lengths, bits packed MSB first, no positions
-__global__ __launch_bounds__(64) void k_batch_pack(const BatchArgs b) {
-    const int lane = (int)threadIdx.x;
-    const int64_t c = blockIdx.x;
-    if (c >= b.k) return;
-    const int64_t *cnt = b.counts + kBatchCounts * c;
-    const BlobLayout L = batch_blob_layout(cnt);
-    const int64_t at = b.dir[c];
-    if (at < 0 || at > b.cap_blob || L.total > b.cap_blob - at) return;        // (cannot happen with the planned capacity; the fetch reports it)
-    const BatchCapture cap = batch_capture(b, c);
-    const BatchRegion R = cap.R;
-    // (counts that are not this capture's -- a plan whose launch order left it out -- are not followed into the region)
-    if (cnt[0] < 0 || cnt[0] > R.cap_rows || cnt[1] < 0 || cnt[1] > R.cap_msg || cnt[2] < 0 || cnt[2] > R.cap_bits) return;
-    char *out = b.blob + at;
-    const char *region = b.work + (cap.ok ? cap.roff : 0);
-    if (lane < 16) {
-        int64_t v = 0;
-        switch (lane) {
-            case 0: v = URHGPU_BLOB_MAGIC; break;
-            case 1: v = L.n_rows; break;
-            case 2: v = L.n_msg; break;
-            case 3: v = L.n_bits; break;
-            case 5: v = cnt[3]; break;
-            case 6: v = L.total; break;
-            case 8: v = L.off_pauses; break;
-            case 9: v = L.off_msg_off; break;
-            case 10: v = L.off_pos_off; break;
-            case 11: v = L.off_row_state; break;
-            case 12: v = L.off_bits; break;
-            case 13: v = L.off_row_len; break;
-            case 14: v = L.off_pos32; break;
-            case 15: v = cnt[4]; break;
-            default: break;                                 // n_pos, flags: 0
-        }
-        ((int64_t *)out)[lane] = v;
-    }
-    if (!cap.ok) {                                          // nothing was stored: the counts are all 0 but msg_off / pos_off [0]
-        if (lane == 0) { *(int64_t *)(out + L.off_msg_off) = 0; *(int64_t *)(out + L.off_pos_off) = 0; }
-        return;
-    }
-    const int64_t *pauses = (const int64_t *)(region + R.off_pauses), *msg_off = (const int64_t *)(region + R.off_msg_off);
-    int64_t *o_pa = (int64_t *)(out + L.off_pauses), *o_mo = (int64_t *)(out + L.off_msg_off), *o_po = (int64_t *)(out + L.off_pos_off);
-    for (int64_t i = lane; i <= L.n_msg; i += 64) {
-        if (i < L.n_msg) o_pa[i] = pauses[i];
-        o_mo[i] = msg_off[i]; o_po[i] = 0;                  // (positions are derived from the rows on the host)
-    }
-    const int2 *rows = (const int2 *)(region + R.off_rows);
-    int8_t *o_st = (int8_t *)(out + L.off_row_state);
-    int32_t *o_len = (int32_t *)(out + L.off_row_len);
-    for (int64_t i = lane; i < L.n_rows; i += 64) { const int2 r = rows[i]; o_st[i] = (int8_t)r.y; o_len[i] = r.x; }
-    // bits: eight bytes in, one byte out; the bits beyond n_bits of the last byte are zero
-    const uint8_t *bits = (const uint8_t *)(region + R.off_bits);
-    const unsigned long long *in = (const unsigned long long *)bits;
-    uint8_t *o_bits = (uint8_t *)(out + L.off_bits);
-    const int64_t nb = (L.n_bits + 7) / 8;
-    for (int64_t j = lane; j < nb; j += 64) {
-        unsigned long long w;
-        if (8 * j + 8 <= L.n_bits) w = in[j];
-        else { w = 0; for (int k = 0; k < 8 && 8 * j + k < L.n_bits; ++k) w |= (unsigned long long)bits[8 * j + k] << (8 * k); }
-        o_bits[j] = (uint8_t)(((w & 0x0101010101010101ull) * 0x8040201008040201ull) >> 56);
-    }
 }
 
 template <int DT, int MOD>
@@ -184,12 +116,15 @@ int batch_setup(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t 
     b.iq = d_iq; b.start = d_start; b.plan = d_plan; b.k = k; b.total = total; b.qad = d_qad;
     b.work = (char *)d_work; b.work_bytes = work_bytes; b.counts = d_counts; b.dir = d_dir; b.blob = (char *)d_blob; b.cap_blob = cap_blob;
     b.pause_threshold = p->pause_threshold; b.sps = p->samples_per_symbol; b.bps = p->bits_per_symbol; b.tol = p->tolerance;
+    b.each = nullptr; b.each_thr = nullptr; b.n_thr = 0; b.each_lo = 0; b.each_n = 0;      // (one parameter set for all)
     return URHGPU_OK;
 }
 
+void launch_batch_scan(const BatchArgs &b, hipStream_t s) { hipLaunchKernelGGL(k_batch_scan, dim3(1), dim3(256), 0, s, b); }
+
 void launch_batch_scan_pack(const BatchArgs &b, unsigned grid, hipStream_t s) {
     hipLaunchKernelGGL(k_batch_scan, dim3(1), dim3(256), 0, s, b);
-    hipLaunchKernelGGL(k_batch_pack, dim3(grid), dim3(64), 0, s, b);
+    hipLaunchKernelGGL(k_batch_pack<false>, dim3(grid), dim3(64), 0, s, b);
 }
 
 }  // namespace urh

@@ -57,6 +57,12 @@ struct BatchArgs {
     int64_t pause_threshold;
     uint32_t sps;
     int bps, tol;
+    // parameters per capture (batch_each.hip, the EACH forms below; not read elsewhere): the table, the shared thresholds, and the slice of
+    // the plan's launch order this walk launch takes
+    const urhgpu_batch_each *each;   // [k]
+    const float *each_thr;           // [n_thr]
+    int64_t n_thr;
+    int64_t each_lo, each_n;
 };
 
 // a capture's region of the work buffer: what a wavefront may write, from its length and its row capacity alone (host and device agree)
@@ -80,7 +86,7 @@ __host__ __device__ inline BatchRegion batch_region(int64_t n, int64_t cap_rows,
 
 // what capture c may use: its samples and its region, checked against the buffers (a wavefront never leaves either)
 struct BatchCapture { int64_t s0, n, roff; BatchRegion R; bool ok; };
-__device__ __forceinline__ BatchCapture batch_capture(const BatchArgs &b, int64_t c) {
+__device__ __forceinline__ BatchCapture batch_capture(const BatchArgs &b, int64_t c, uint32_t sps, int bps, bool each_ok = true) {
     BatchCapture v;
     v.s0 = b.start[c];
     const int64_t s1 = b.start[c + 1];
@@ -88,13 +94,30 @@ __device__ __forceinline__ BatchCapture batch_capture(const BatchArgs &b, int64_
     v.n = v.ok ? s1 - v.s0 : 0;
     v.roff = b.plan[c];
     const int64_t cap_rows = b.plan[b.k + c];
-    v.R = batch_region(v.n, v.ok ? cap_rows : 0, b.sps, b.bps);
+    v.R = batch_region(v.n, v.ok ? cap_rows : 0, sps, bps);
     if (cap_rows < 0 || cap_rows > 0x7fffffffll || v.roff < 0 || (v.roff & 15) || v.roff > b.work_bytes || v.R.bytes > b.work_bytes - v.roff) v.ok = false;
+    if (!each_ok) { v.ok = false; v.n = 0; }               // (a record the device does not accept: a refused capture)
     if (!v.ok) {                                           // no region: nothing is stored, everything is still counted
-        v.R = batch_region(0, 0, b.sps, b.bps);
+        v.R = batch_region(0, 0, sps, bps);
         v.R.cap_bits = v.R.cap_msg = 0;
     }
     return v;
+}
+__device__ __forceinline__ BatchCapture batch_capture(const BatchArgs &b, int64_t c) { return batch_capture(b, c, b.sps, b.bps); }
+
+// capture c's record of the per-capture table as the device accepts it: the ranges of batch_check_params, its order - 1 thresholds inside the
+// shared table, the noise value of its modulation.  Anything else is a refused capture: the record's values are not followed anywhere.
+__device__ __forceinline__ bool batch_each_ok(const urhgpu_batch_each &e, int64_t n_thr) {
+    if (e.mod != URHGPU_MOD_ASK && e.mod != URHGPU_MOD_FSK) return false;
+    if (e.bits_per_symbol < 1 || e.bits_per_symbol > 7 || e.samples_per_symbol < 1 || e.tolerance < 0 || e.tolerance > 65535) return false;
+    if (e.thr_first < 0 || (int64_t)e.thr_first + ((1 << e.bits_per_symbol) - 1) > n_thr) return false;
+    return e.noise_val == (e.mod == URHGPU_MOD_ASK ? 0.0f : -4.0f);
+}
+// ... and capture c's samples and region from ITS samples per symbol and bits per symbol (a refused record: 1 and 1, no region)
+__device__ __forceinline__ BatchCapture batch_capture_each(const BatchArgs &b, int64_t c) {
+    const urhgpu_batch_each e = b.each[c];
+    const bool ok = batch_each_ok(e, b.n_thr);
+    return batch_capture(b, c, ok ? e.samples_per_symbol : 1u, ok ? e.bits_per_symbol : 1, ok);
 }
 
 __device__ __forceinline__ float batch_shr1(float x, float lane0) {       // value of lane - 1; lane 0 receives `lane0`
@@ -124,13 +147,33 @@ __device__ __forceinline__ uint32_t classify_at(float q, const RunArgs &p, const
 // thresholds at p.d_thr + c (order - 1) (classify_at, the device-threshold form of classify<ORDER2, true>: k_batch_center_publish has
 // written them on the same stream), or through p.thr where p.d_thr is null.  p.d_noise, where not null, still tells a flag-2 capture (two
 // samples).  DT is not used.
-template <int DT, int MOD, bool ORDER2, bool DNOISE = false, bool QIN = false>
+// EACH (batch_each.hip): capture c is walked with ITS record of the table b.each -- samples per symbol, bits per symbol, tolerance, pause
+// threshold -- and classified through ITS order - 1 thresholds at b.each_thr + thr_first (the general form: captures of every order share a
+// launch; for order 2 it is the ORDER2 form, value for value); the record, the thresholds and the noise block (always DNOISE) are uniform loads.
+// The launch takes the slice [b.each_lo, b.each_lo + b.each_n) of the plan's launch order, the captures of modulation MOD; a record the
+// device does not accept, or one of another modulation, is a refused capture.  Without EACH every value is read exactly where it always was.
+template <int DT, int MOD, bool ORDER2, bool DNOISE = false, bool QIN = false, bool EACH = false>
 __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchArgs b) {
     const int lane = (int)threadIdx.x;
-    if ((int64_t)blockIdx.x >= b.k) return;
-    const int64_t c = b.plan[2 * b.k + blockIdx.x];            // launch order: longest capture first
+    if ((int64_t)blockIdx.x >= (EACH ? b.each_n : b.k)) return;
+    const int64_t c = b.plan[2 * b.k + (EACH ? b.each_lo : 0) + blockIdx.x];            // launch order: longest capture first
     if (c < 0 || c >= b.k) return;
-    const BatchCapture cap = batch_capture(b, c);
+    uint32_t e_sps = 0, e_tol = 0;
+    int e_order = 2;
+    const float *e_thr = nullptr;
+    if (EACH) {
+        const urhgpu_batch_each e = b.each[c];                 // (a uniform address)
+        if (!batch_each_ok(e, b.n_thr) || e.mod != MOD) {      // refused: the counts say so, nothing is read or stored
+            if (lane == 0) {
+                int64_t *o = b.counts + kBatchCounts * c;
+                o[0] = o[1] = o[2] = o[3] = 0; o[4] = kBatchBadStart; o[5] = o[6] = o[7] = 0;
+            }
+            return;
+        }
+        e_sps = e.samples_per_symbol; e_tol = (uint32_t)e.tolerance; e_order = 1 << e.bits_per_symbol;
+        e_thr = b.each_thr + e.thr_first;
+    }
+    const BatchCapture cap = EACH ? batch_capture(b, c, e_sps, 31 - __builtin_clz((unsigned)e_order)) : batch_capture(b, c);
     float nsq = 0.0f;
     bool two = false;
     if (DNOISE) {
@@ -141,7 +184,8 @@ __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchA
     if (QIN && p.d_noise) two = ((const urhgpu_noise_result *)p.d_noise)[c].flag == 2 && cap.n > 2;
     const float *thr_c = (QIN && p.d_thr) ? p.d_thr + c * (int64_t)(p.order - 1) : nullptr;      // (a uniform address)
     const uint32_t n = two ? 2u : (uint32_t)cap.n;             // < 2^31
-    const uint32_t tol = (uint32_t)b.tol;
+    const uint32_t tol = EACH ? e_tol : (uint32_t)b.tol;
+    const uint32_t sps1 = EACH ? e_sps : b.sps;               // the ASK short-pause rule's samples per symbol
     const char *iq = (const char *)b.iq + cap.s0 * Iq<DT>::kBytes;
     float *qad = b.qad ? b.qad + cap.s0 : nullptr;
     const float *qin = QIN ? b.qad + cap.s0 : nullptr;
@@ -193,10 +237,12 @@ __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchA
             q = (i == 0) ? p.noise_val : q;                                            // :361 (no predecessor: never the neighbouring capture's sample)
             q = (n <= 2) ? 0.0f : q;                                                   // :335-336
         }
-        const uint32_t st = QIN ? classify_at<ORDER2>(q, p, thr_c) : classify<ORDER2>(q, p);
+        const uint32_t st = EACH ? ((q == p.noise_val) ? kStPause : classify_thr<false>(q, e_thr, e_order))
+                                 : (QIN ? classify_at<ORDER2>(q, p, thr_c) : classify<ORDER2>(q, p));
         if (!QIN && qad && valid) qad[i] = q;
         if (base == 0)      // :421-427: PAUSE when sample 0 is NOISE, else the state of the literal 0.0 (s is still 0 there)
-            cur_state = ((uint32_t)batch_lane((int)st, 0) == kStPause) ? kStPause : (QIN ? classify_at<ORDER2>(0.0f, p, thr_c, false) : classify<ORDER2>(0.0f, p, false));
+            cur_state = ((uint32_t)batch_lane((int)st, 0) == kStPause) ? kStPause
+                        : (EACH ? classify_thr<false>(0.0f, e_thr, e_order) : (QIN ? classify_at<ORDER2>(0.0f, p, thr_c, false) : classify<ORDER2>(0.0f, p, false)));
         const uint32_t before = batch_shr1(st, run_state);
         const uint64_t bm = __builtin_amdgcn_ballot_w64(valid && st != before);    // lanes that start a run
         const int cnt = (int)((n - base < kBatchStep) ? (n - base) : kBatchStep);
@@ -223,7 +269,7 @@ __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchA
                 pl += k;
                 uint32_t r_st = cur_state;
                 const int64_t r_len = (int64_t)pl - (int64_t)tol;
-                if (MOD == URHGPU_MOD_ASK && r_st == kStPause && r_len < (int64_t)b.sps) r_st = 1u;     // the ASK short-pause rule (:464-465): state 0
+                if (MOD == URHGPU_MOD_ASK && r_st == kStPause && r_len < (int64_t)sps1) r_st = 1u;     // the ASK short-pause rule (:464-465): state 0
                 BATCH_EMIT(r_st, r_len);
                 pl = tol + (L - k);
                 cur_state = t;
@@ -247,8 +293,15 @@ __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchA
     // pointers and capacities -- does not occupy scalar registers during the first)
     uint32_t wg = blockIdx.x;
     __asm__ volatile("" : "+s"(wg));
-    const int64_t c_again = b.plan[2 * b.k + wg];
-    const BatchCapture cap2 = batch_capture(b, c_again);
+    const int64_t c_again = b.plan[2 * b.k + (EACH ? b.each_lo : 0) + wg];
+    uint32_t sps = b.sps;
+    int bps = b.bps;
+    int64_t pt = b.pause_threshold;
+    if (EACH) {                                            // (accepted above: the same record once more)
+        const urhgpu_batch_each e2 = b.each[c_again];
+        sps = e2.samples_per_symbol; bps = e2.bits_per_symbol; pt = e2.pause_threshold;
+    }
+    const BatchCapture cap2 = EACH ? batch_capture(b, c_again, sps, bps) : batch_capture(b, c_again);
     const BatchRegion R = cap2.R;
     const bool ok = cap2.ok;
     char *region = b.work + (ok ? cap2.roff : 0);
@@ -259,7 +312,6 @@ __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchA
 
     // ---- _ppseq_to_bits over the stored rows: 64 rows per load, walked one by one; the lanes expand a row's symbols ----
     __syncthreads();                                       // (one wavefront: lane 0's row stores are visible to every lane's loads)
-    const int64_t pt = b.pause_threshold;
     int64_t nbits = 0, nmsg = 0, msg_bits_start = 0;
     bool there_was_data = false;
     int last_state = 0;
@@ -271,8 +323,8 @@ __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchA
             const int2 row = rows2[rb + lane];
             len_v = row.x; st_v = row.y;
             // int(L / sps) + (fraction > 0.5): exact in integers for |L| < 2^31; a negative length truncates towards zero and rounds nowhere
-            const uint32_t a = (uint32_t)(len_v < 0 ? -(int64_t)len_v : (int64_t)len_v), qq = a / b.sps, rr = a - qq * b.sps;
-            nsym_v = len_v < 0 ? -(int)qq : (int)(qq + ((2 * (uint64_t)rr > (uint64_t)b.sps) ? 1u : 0u));
+            const uint32_t a = (uint32_t)(len_v < 0 ? -(int64_t)len_v : (int64_t)len_v), qq = a / sps, rr = a - qq * sps;
+            nsym_v = len_v < 0 ? -(int)qq : (int)(qq + ((2 * (uint64_t)rr > (uint64_t)sps) ? 1u : 0u));
         }
         const int m = (int)((nr - rb < 64) ? (nr - rb) : 64);
         for (int j = 0; j < m; ++j) {
@@ -280,7 +332,7 @@ __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchA
             const int s = batch_lane(st_v, j);
             last_state = s; last_len = L;
             if (rb + j == 0 && s == -1) continue;          // "starts with pause": only seeds total_samples (:338-340)
-            const int64_t k_bits = nsym * b.bps;
+            const int64_t k_bits = nsym * bps;
             if (s == -1 && !(nsym <= pt || pt == 0)) {     // a long pause
                 if (!there_was_data) {
                     nbits = msg_bits_start;                // drops what was gathered
@@ -294,9 +346,9 @@ __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchA
             }
             if (k_bits > 0) {
                 for (int64_t u = lane; u < nsym; u += 64)                          // a symbol per lane: util.number_to_bits, MSB first
-                    for (int bb = 0; bb < b.bps; ++bb) {
-                        const int64_t at = nbits + u * b.bps + bb;
-                        if (ok && at < R.cap_bits) bits[at] = (s == -1) ? (uint8_t)0 : (uint8_t)((s >> (b.bps - 1 - bb)) & 1);
+                    for (int bb = 0; bb < bps; ++bb) {
+                        const int64_t at = nbits + u * bps + bb;
+                        if (ok && at < R.cap_bits) bits[at] = (s == -1) ? (uint8_t)0 : (uint8_t)((s >> (bps - 1 - bb)) & 1);
                     }
                 nbits += k_bits;
             }
@@ -320,6 +372,78 @@ __global__ __launch_bounds__(64) void k_batch_bits(const RunArgs p, const BatchA
     }
 }
 
+__device__ __forceinline__ BlobLayout batch_blob_layout(const int64_t *cnt) {
+    const int64_t c5[5] = {cnt[0], cnt[1], cnt[2], 0, cnt[3]};
+    return blob_layout(c5, cnt[0], cnt[2], cnt[1], 0, 0);
+}
+
+// capture c's results as a standard compact blob at dir[c]: header flags 0, int8 states, int32 lengths, bits packed MSB first, no positions
+// (EACH, batch_each.hip: the region laid out from the capture's own record)
+template <bool EACH>
+__global__ __launch_bounds__(64) void k_batch_pack(const BatchArgs b) {
+    const int lane = (int)threadIdx.x;
+    const int64_t c = blockIdx.x;
+    if (c >= b.k) return;
+    const int64_t *cnt = b.counts + kBatchCounts * c;
+    const BlobLayout L = batch_blob_layout(cnt);
+    const int64_t at = b.dir[c];
+    if (at < 0 || at > b.cap_blob || L.total > b.cap_blob - at) return;        // (cannot happen with the planned capacity; the fetch reports it)
+    const BatchCapture cap = EACH ? batch_capture_each(b, c) : batch_capture(b, c);
+    const BatchRegion R = cap.R;
+    // (counts that are not this capture's -- a plan whose launch order left it out -- are not followed into the region)
+    if (cnt[0] < 0 || cnt[0] > R.cap_rows || cnt[1] < 0 || cnt[1] > R.cap_msg || cnt[2] < 0 || cnt[2] > R.cap_bits) return;
+    char *out = b.blob + at;
+    // (EACH: a capture the walk refused -- a record of another modulation than its launch's -- has a region nothing was written to)
+    const bool ok = EACH ? (cap.ok && !(cnt[4] & kBatchBadStart)) : cap.ok;
+    const char *region = b.work + (ok ? cap.roff : 0);
+    if (lane < 16) {
+        int64_t v = 0;
+        switch (lane) {
+            case 0: v = URHGPU_BLOB_MAGIC; break;
+            case 1: v = L.n_rows; break;
+            case 2: v = L.n_msg; break;
+            case 3: v = L.n_bits; break;
+            case 5: v = cnt[3]; break;
+            case 6: v = L.total; break;
+            case 8: v = L.off_pauses; break;
+            case 9: v = L.off_msg_off; break;
+            case 10: v = L.off_pos_off; break;
+            case 11: v = L.off_row_state; break;
+            case 12: v = L.off_bits; break;
+            case 13: v = L.off_row_len; break;
+            case 14: v = L.off_pos32; break;
+            case 15: v = cnt[4]; break;
+            default: break;                                 // n_pos, flags: 0
+        }
+        ((int64_t *)out)[lane] = v;
+    }
+    if (!ok) {                                              // nothing was stored: the counts are all 0 but msg_off / pos_off [0]
+        if (lane == 0) { *(int64_t *)(out + L.off_msg_off) = 0; *(int64_t *)(out + L.off_pos_off) = 0; }
+        return;
+    }
+    const int64_t *pauses = (const int64_t *)(region + R.off_pauses), *msg_off = (const int64_t *)(region + R.off_msg_off);
+    int64_t *o_pa = (int64_t *)(out + L.off_pauses), *o_mo = (int64_t *)(out + L.off_msg_off), *o_po = (int64_t *)(out + L.off_pos_off);
+    for (int64_t i = lane; i <= L.n_msg; i += 64) {
+        if (i < L.n_msg) o_pa[i] = pauses[i];
+        o_mo[i] = msg_off[i]; o_po[i] = 0;                  // (positions are derived from the rows on the host)
+    }
+    const int2 *rows = (const int2 *)(region + R.off_rows);
+    int8_t *o_st = (int8_t *)(out + L.off_row_state);
+    int32_t *o_len = (int32_t *)(out + L.off_row_len);
+    for (int64_t i = lane; i < L.n_rows; i += 64) { const int2 r = rows[i]; o_st[i] = (int8_t)r.y; o_len[i] = r.x; }
+    // bits: eight bytes in, one byte out; the bits beyond n_bits of the last byte are zero
+    const uint8_t *bits = (const uint8_t *)(region + R.off_bits);
+    const unsigned long long *in = (const unsigned long long *)bits;
+    uint8_t *o_bits = (uint8_t *)(out + L.off_bits);
+    const int64_t nb = (L.n_bits + 7) / 8;
+    for (int64_t j = lane; j < nb; j += 64) {
+        unsigned long long w;
+        if (8 * j + 8 <= L.n_bits) w = in[j];
+        else { w = 0; for (int k = 0; k < 8 && 8 * j + k < L.n_bits; ++k) w |= (unsigned long long)bits[8 * j + k] << (8 * k); }
+        o_bits[j] = (uint8_t)(((w & 0x0101010101010101ull) * 0x8040201008040201ull) >> 56);
+    }
+}
+
 // ---- host side, defined in batch.hip and shared with batch_auto.hip ----
 // the parameters a batch accepts (every entry point): ASK / FSK, the ranges of the other passes
 int batch_check_params(const urhgpu_params *p);
@@ -332,6 +456,8 @@ int batch_setup(urhgpu_ctx *ctx, const void *d_iq, int64_t total, const int64_t 
                 float *d_qad, void *d_work, int64_t work_bytes, int64_t *d_counts, int64_t *d_dir, void *d_blob, int64_t cap_blob, RunArgs &a, BatchArgs &b);
 // k_batch_scan and k_batch_pack behind a launch of k_batch_bits: two launches
 void launch_batch_scan_pack(const BatchArgs &b, unsigned grid, hipStream_t s);
+// k_batch_scan alone (batch_each.hip packs with a kernel of its own): one launch
+void launch_batch_scan(const BatchArgs &b, hipStream_t s);
 
 // ---- host side, defined in batch_psk.hip and used by batch_center.hip's whole PSK pass ----
 // PSK parameters a batch accepts: batch_check_params_psk's, and a loop order the reference writes an output for (2 or 4)

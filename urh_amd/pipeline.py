@@ -1004,6 +1004,27 @@ class DevicePipeline:
         return iq_to_bits_batch_dc(self, captures, p, auto_noise, auto_center, center_max_size, message_length_divisor, want_qad, cap_rows, long_from,
                                    **options)
 
+    def iq_to_bits_batch_each(self, captures, params, auto_noise=False, message_length_divisor=None, want_qad=False, cap_rows=None, long_from=None,
+                              **options):
+        """A batch in which EVERY CAPTURE HAS ITS OWN PARAMETERS (include/urhgpu.h "a batch of captures: parameters per capture"): capture k
+        is demodulated, sliced and turned into bits -- with message_length_divisor not None also into message records -- with params[k], the
+        way the reference opens each file of a session with its own Signal parameters.  The K parameter sets become a table of K records and
+        one shared table of slicing thresholds that travel in the batch's ONE upload; the wavefront of capture k reads its own record alone.
+        Launches, whatever the number of captures, their lengths and the number of different parameter sets: one walk per modulation present
+        (at most two), scan, pack; one more with auto_noise; three more with records.  Copies: those of iq_to_bits_batch_records.
+        captures, want_qad, cap_rows, long_from: as for iq_to_bits_batch (the three input forms -- what dc_correct_batch returns is one --, the
+        five sample types); a capture of long_from samples or more goes through iq_to_bits(capture, params[k], ...).
+        params: a sequence of K DemodParams (batch.params_from_estimates makes it of estimate_batch's result), or one for all.
+        auto_noise: a threshold per capture as in iq_to_bits_batch_auto (.noise / .noise_flags), instead of params[k].noise_threshold.
+        Returns a batch.BatchBits whose .params is the list; capture k equals iq_to_bits(capture_k, params[k], want_qad=True, auto_noise=...,
+        msg_records=..., message_length_divisor=...) on it alone, bit for bit, .qad(k) and the records' RSSI included; .messages() /
+        .message_data(k) use capture k's samples per symbol and bits per symbol; .retry(k) repeats a truncated capture alone with params[k].
+        ASK and FSK: a PSK entry (iq_to_bits_batch_psk), auto_center (iq_to_bits_batch_center) and dc_correction (dc_correct_batch in front) are
+        refused with a ValueError that says what to call, a wrong number of params and a divisor outside 1 .. 2 ** 30 likewise, an unknown
+        option is a TypeError -- all before a device is touched."""
+        from .batch import iq_to_bits_batch_each
+        return iq_to_bits_batch_each(self, captures, params, auto_noise, message_length_divisor, want_qad, cap_rows, long_from, **options)
+
     def costas_demod_batch(self, captures, p: DemodParams, noise=None):
         """The Costas launch of iq_to_bits_batch_psk alone (urhgpu_batch_costas_dev): afp_demod with PSK of every capture of a batch (the three
         input forms of iq_to_bits_batch) in ONE launch.  noise: None -- every capture gated with p.noise_threshold --, or one threshold per

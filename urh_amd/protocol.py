@@ -137,8 +137,16 @@ def get_protocols_from_signals_dev(pipe, captures, p, message_length_divisor=1, 
     timestamps: one per capture, default 0.0.  Returns a list of MessageData lists, one per capture in the order given.
     PSK parameters take DevicePipeline.iq_to_bits_batch_psk with the same options.
     dc_correction: every capture minus its own means, corrected on the device in front of the batch (DevicePipeline.iq_to_bits_batch_dc, for
-    every modulation a batch takes)."""
+    every modulation a batch takes).
+    p may also be a sequence of K DemodParams, one per capture -- what batch.params_from_estimates makes of DevicePipeline.estimate_batch's
+    result: the ASK and FSK captures then go through ONE DevicePipeline.iq_to_bits_batch_each (behind dc_correct_batch with dc_correction),
+    whatever the number of different parameter sets; PSK captures are split off and run through iq_to_bits_batch_psk ONCE PER DISTINCT PSK
+    PARAMETER SET (a Costas loop has no per-capture table); auto_center is refused (estimated parameters carry a center).  The results come
+    back in the order given."""
     from .batch import is_psk
+    if not hasattr(p, "modulation_type"):
+        return _protocols_each(pipe, captures, list(p), message_length_divisor, sample_rate, timestamps, auto_noise, auto_center, cap_rows, long_from,
+                               dc_correction)
     if dc_correction:
         res = pipe.iq_to_bits_batch_dc(captures, p, auto_noise=auto_noise, auto_center=auto_center, center_max_size=center_max_size,
                                        message_length_divisor=message_length_divisor, cap_rows=cap_rows, long_from=long_from)
@@ -151,6 +159,44 @@ def get_protocols_from_signals_dev(pipe, captures, p, message_length_divisor=1, 
     for k in res.truncated:
         res.retry(k)
     return res.messages(sample_rate, timestamps)
+
+
+def _protocols_each(pipe, captures, params, divisor, sample_rate, timestamps, auto_noise, auto_center, cap_rows, long_from, dc_correction):
+    """get_protocols_from_signals_dev with a parameter set per capture"""
+    from dataclasses import astuple
+    from .batch import check_batch_each_options, is_psk
+    from .batch.inputs import _batch_input
+    given = _batch_input(pipe, captures)
+    n = len(given.caps)
+    if len(params) != n:
+        raise ValueError(f"params holds one DemodParams per capture ({n}), or is one for all: {len(params)} were given")
+    if timestamps is not None and len(timestamps) != n:
+        raise ValueError("timestamps holds one entry per capture")
+    psk = [k for k in range(n) if is_psk(params[k])]
+    rest = [k for k in range(n) if not is_psk(params[k])]
+    check_batch_each_options([params[k] for k in rest], len(rest), divisor, auto_center=auto_center)
+    out = [None] * n
+    stamp = lambda k: 0.0 if timestamps is None else timestamps[k]      # noqa: E731
+
+    def hand_out(res, idx):
+        for k in res.truncated:
+            res.retry(k)
+        for j, k in enumerate(idx):
+            out[k] = res.message_data(j, sample_rate, stamp(k))
+    if rest:
+        sub = captures if len(rest) == n else [given.caps[k] for k in rest]
+        if dc_correction:
+            sub = pipe.dc_correct_batch(sub)
+        hand_out(pipe.iq_to_bits_batch_each(sub, [params[k] for k in rest], auto_noise=auto_noise, message_length_divisor=divisor, cap_rows=cap_rows,
+                                            long_from=long_from), rest)
+    sets = {}
+    for k in psk:
+        sets.setdefault(astuple(params[k]), []).append(k)
+    for idx in sets.values():
+        call = pipe.iq_to_bits_batch_dc if dc_correction else pipe.iq_to_bits_batch_psk
+        hand_out(call([given.caps[k] for k in idx], params[idx[0]], auto_noise=auto_noise, message_length_divisor=divisor, cap_rows=cap_rows,
+                      long_from=long_from), idx)
+    return out
 
 
 def messages_from_bits(pipe, iq, p, bit_data, pauses, bit_sample_pos, message_length_divisor=1, sample_rate=1e6, timestamp=0.0):

@@ -667,3 +667,35 @@ def auto_detect_batch(signals, detect_modulation=True, detect_noise=False):
     noise = [None if detect_noise else s.noise_threshold for s in signals]
     found = signals[0].pipe.estimate_batch([s._iq for s in signals], noise=noise, modulation=modulation)
     return [s._apply_estimate(est, {}, detect_modulation, detect_noise) for s, est in zip(signals, found)]
+
+
+def get_protocols_batch(signals):
+    """Signal.get_protocol of every signal of a session from ONE DevicePipeline.iq_to_bits_batch_each over their captures: signal k is handed
+    what signal.get_protocol() returns -- its MessageData list --, computed with its own params(), message_length_divisor, sample_rate and
+    timestamp, whatever the number of different parameter sets (one batch per distinct message_length_divisor: a batch pads to one).  A signal
+    whose noise_threshold is not below its max_magnitude is sliced as the two zeros Signal.qad gives it (the flag-2 case of a noise block).
+    Such a signal of batch.LONG_FROM_DEFAULT samples or more (a batch would hand it to a pass, which has no two-zeros form), signals that are
+    already demodulated, that are not ASK or FSK, whose samples_per_symbol, tolerance or bits_per_symbol a batch does not
+    take, or whose sample type differs from the first one's, go through get_protocol() alone.  Returns the lists in the order given."""
+    signals = list(signals)
+    out = [None] * len(signals)
+    groups = {}
+    for k, s in enumerate(signals):
+        p = s.params()
+        gated = not (s.noise_threshold < s.max_magnitude)
+        from .batch import LONG_FROM_DEFAULT
+        ok = (not s.already_demodulated and s.dtype == signals[0].dtype and not (gated and s.num_samples >= LONG_FROM_DEFAULT) and s.pipe is signals[0].pipe and p.modulation_type in ("ASK", "FSK") and s.num_samples > 0
+              and 0 <= p.tolerance <= 65535 and p.samples_per_symbol >= 1 and 1 <= p.bits_per_symbol <= 7)
+        if ok:
+            groups.setdefault(max(1, int(s.message_length_divisor)), []).append(k)
+        else:
+            out[k] = s.get_protocol()
+    for divisor, idx in groups.items():
+        flags = [1 if signals[k].noise_threshold < signals[k].max_magnitude else 2 for k in idx]
+        res = signals[idx[0]].pipe.iq_to_bits_batch_each([signals[k]._iq for k in idx], [signals[k].params() for k in idx], message_length_divisor=divisor,
+                                                         _noise_flags=flags)
+        for j in res.truncated:
+            res.retry(j)
+        for j, k in enumerate(idx):
+            out[k] = res.message_data(j, signals[k].sample_rate, signals[k].timestamp)
+    return out
