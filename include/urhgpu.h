@@ -198,13 +198,15 @@ int urhgpu_ppseq_to_bits(urhgpu_ctx *ctx, const int64_t *rows, int64_t n_rows, i
                          int64_t *pos, int64_t cap_pos, int64_t *pos_off, int64_t *counts);
 
 /* signal_functions.fir_filter (:513-525): complex64 x[n] (*) complex64 taps[m], causal, zero history,
- * accumulation order of the reference's scatter loop. */
+ * accumulation order of the reference's scatter loop.  out always holds n samples; with m = 0 they are n zeros.  (The reference
+ * itself returns n - 1 zeros for empty taps and raises ValueError for n = m = 0 -- np.zeros(n + m - 1)[:n]; the Python callers
+ * signal_functions.fir_filter and Filter.work shape that from this result, the device routes keep the capture's length.) */
 int urhgpu_fir_filter(urhgpu_ctx *ctx, const float *x, int64_t n, const float *taps, int64_t m, float *out);
 
 /* The same on device memory (asynchronous).  d_left_halo: NULL = zero history (the reference), or DEVICE pointer
  * to the m - 1 samples that precede d_x[0] (sharded captures: the left neighbour's tail).
  * Limits (URHGPU_ERR_UNSUPPORTED beyond them, nothing is computed): the taps and one tile of input are staged in LDS, which
- * holds about 8 900 taps; bits_per_symbol <= 7 (modulation order <= 128) in every entry point that slices. */
+ * holds at most 7 950 taps; bits_per_symbol <= 7 (modulation order <= 128) in every entry point that slices. */
 int urhgpu_fir_filter_dev(urhgpu_ctx *ctx, const float *d_x, int64_t n, const float *d_taps, int64_t m,
                           const float *d_left_halo, float *d_out);
 /* The same with the magnitude chunk statistics of the OUTPUT fused into the filter's epilogue (Signal.filter_range followed by

@@ -123,6 +123,9 @@ def grab_pulse_lens(samples, center: float, tolerance: int, modulation_type: str
 def fir_filter(input_samples, filter_taps) -> np.ndarray:
     x = np.ascontiguousarray(input_samples, dtype=np.complex64)
     h = np.ascontiguousarray(filter_taps, dtype=np.complex64)
+    if len(h) == 0:
+        # np.zeros(N + M - 1)[:N] (signal_functions.pyx:517, 525): N - 1 zeros, and numpy's ValueError for N = M = 0
+        return np.zeros(len(x) - 1, dtype=np.complex64)
     out = np.zeros(len(x), dtype=np.complex64)
     lib().orc_fir_filter(x.ctypes.data_as(C.c_void_p), C.c_int64(len(x)), h.ctypes.data_as(C.c_void_p),
                          C.c_int64(len(h)), out.ctypes.data_as(C.c_void_p))

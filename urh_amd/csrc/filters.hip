@@ -58,8 +58,8 @@ struct FirArgs {
 
 // The products of a tile can only come out as (NaN, NaN) -- the case the reference's complex multiply repairs with
 // __mulsc3 -- when an operand is non-finite or two products overflow.  While staging a tile the workgroup records the
-// largest |component| of its inputs and taps; if both stay below 2^60 every product and partial sum is finite (m < 2^20
-// terms of at most 2^121) and the per-product NaN test is skipped (wave-uniform branch): a third of the instructions.
+// largest |component| of its inputs and taps; if both stay below 2^60 every product is finite (parts below 2^121; a partial sum
+// may still overflow to an infinity, which the additions carry as the reference's do) and the per-product NaN test is skipped.
 constexpr uint32_t kFirSafeBits = 0x5d800000u;   // 2^60
 
 typedef float fir_v2f __attribute__((ext_vector_type(2)));
@@ -465,7 +465,7 @@ int launch_fir(const float2 *x, int64_t n, const float2 *taps, int m, const floa
     a.taps_pad = nullptr; a.redo = nullptr; a.tile_list = nullptr;
     a.hist = ((m - 1) / kFirR) * kFirR + kFirR - 1;
     const size_t lds = (size_t)(((m + 1) & ~1) + (a.hist + kFirTile) + ((a.hist + kFirTile) >> 3) + 1) * 8;
-    if (lds > 150 * 1024) return URHGPU_ERR_UNSUPPORTED;       // m <= ~8900 taps
+    if (lds > 150 * 1024) return URHGPU_ERR_UNSUPPORTED;       // m <= 7950 taps (153 592 bytes; 7951 would need 153 608)
     URH_TRY(fir_lds_attr(k_fir<true, false>, lds)); URH_TRY(fir_lds_attr(k_fir<false, false>, lds));
     URH_TRY(fir_lds_attr(k_fir<true, true>, lds)); URH_TRY(fir_lds_attr(k_fir<false, true>, lds));
     const int64_t tiles = (n + kFirTile - 1) / kFirTile;
@@ -515,10 +515,10 @@ int launch_fir(const float2 *x, int64_t n, const float2 *taps, int m, const floa
 // (parity unpinned there; checked here against the oracle / the reference build).
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float2 iir_term(double coef, float2 v) {
-    // (coef + 0j) * (v.x + v.y j) in complex128, rounded to complex64
-    const double re = coef * (double)v.x - 0.0 * (double)v.y;
-    const double im = coef * (double)v.y + 0.0 * (double)v.x;
-    return make_float2((float)re, (float)im);
+    // (coef + 0j) * (v.x + v.y j) in complex128 -- with the Annex G recovery (__muldc3) when both parts come out NaN: 0.0 * inf does that
+    // to a sample with two infinite parts, which the reference keeps infinite -- rounded to complex64
+    const double2 p = cmul128(make_double2(coef, 0.0), make_double2((double)v.x, (double)v.y));
+    return make_float2((float)p.x, (float)p.y);
 }
 
 __global__ void k_iir_ff(const double *a, int64_t M, const float2 *x, int64_t n, int64_t start, float2 *y) {

@@ -190,7 +190,8 @@ class Filter:
 
     def work(self, iq, pipe=None, ctx=None):
         """FIR types: the raw sample values as float32 through the FIR with zero history -- complex64 (n,) for a host array, float32 (n, 2)
-        for a device tensor.  DC correction: the capture minus its mean in the capture's own sample type, i.e. the reference's float64
+        for a device tensor.  With empty taps the host route returns what the reference returns (n - 1 zeros; ValueError for an empty
+        capture), the device route keeps the capture's length (n zeros).  DC correction: the capture minus its mean in the capture's own sample type, i.e. the reference's float64
         difference after the cast that storing it into an IQArray or the receive buffer applies."""
         if self.filter_type == FilterType.dc_correction:
             if isinstance(iq, np.ndarray):
@@ -217,7 +218,8 @@ def _need(pipe):
 
 def fir_filter_dev(pipe, iq, taps):
     """Filter.apply_fir_filter on a device capture: the raw sample values as float32 through the strict-order FIR with zero history
-    (urhgpu_fir_filter_dev) -> float32 (n, 2)."""
+    (urhgpu_fir_filter_dev) -> float32 (n, 2).  The result always has the capture's length: empty taps give n zeros, where the reference's
+    host function (and signal_functions.fir_filter) gives n - 1."""
     from .iq_array import astype
     torch = pipe.torch
     x = torch.view_as_real(iq) if iq.dtype == torch.complex64 else iq

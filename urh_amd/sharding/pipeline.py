@@ -125,7 +125,8 @@ class ShardedPipeline:
     def fir_filter(self, iq_local, taps, left_raw=None, want_halo=False, raw_halo=None):
         """Signal.filter_range semantics on a sharded capture (BASELINE.json configs[3], "FIR-halo exchange"): every rank
         filters its shard with the m-1 samples that precede it as history; rank 0 starts from zero history like the
-        reference's fir_filter (signal_functions.pyx:513-525).  Returns the filtered shard (same shape as iq_local).
+        reference's fir_filter (signal_functions.pyx:513-525).  Returns the filtered shard (same shape as iq_local -- also for empty
+        taps, where the reference's host function drops one sample: n - 1 zeros).
         left_raw is None: the history is the left neighbour's tail, one all-gather of (m-1) * 8 bytes per rank.
         left_raw given (every rank but the first; round 5): whoever distributed the capture handed the rank the m + 1 RAW samples
         that precede its shard ((m + 1, 2) float32 / complex64 (m + 1,): 520 bytes for 64 taps) -- no exchange at all: the last

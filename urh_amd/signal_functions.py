@@ -158,6 +158,10 @@ def ppseq_to_bits(ppseq, samples_per_symbol: int, bits_per_symbol: int, write_bi
 def fir_filter(input_samples, filter_taps, ctx=None) -> np.ndarray:
     x = np.ascontiguousarray(input_samples, dtype=np.complex64)
     h = np.ascontiguousarray(filter_taps, dtype=np.complex64)
+    if len(h) == 0:
+        # the reference's np.zeros(N + M - 1)[:N] (:517, :525): N - 1 zeros, and numpy's ValueError ("negative dimensions are not
+        # allowed") for N = M = 0; urhgpu_fir_filter itself writes N zeros
+        return np.zeros(len(x) - 1, dtype=np.complex64)
     out = np.zeros(len(x), dtype=np.complex64)
     if len(x) == 0:
         return out
