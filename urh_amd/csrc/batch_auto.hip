@@ -154,38 +154,21 @@ __global__ __launch_bounds__(256) void k_batch_noise(const BatchArgs b, double m
 }
 
 static int launch_batch_noise(const BatchArgs &b, int dtype, double max_mag, float cfg, urhgpu_noise_result *d_noise, unsigned grid, hipStream_t s) {
-    switch (dtype) {
-        case URHGPU_DT_I8: hipLaunchKernelGGL(k_batch_noise<URHGPU_DT_I8>, dim3(grid), dim3(256), 0, s, b, max_mag, cfg, d_noise); return URHGPU_OK;
-        case URHGPU_DT_U8: hipLaunchKernelGGL(k_batch_noise<URHGPU_DT_U8>, dim3(grid), dim3(256), 0, s, b, max_mag, cfg, d_noise); return URHGPU_OK;
-        case URHGPU_DT_I16: hipLaunchKernelGGL(k_batch_noise<URHGPU_DT_I16>, dim3(grid), dim3(256), 0, s, b, max_mag, cfg, d_noise); return URHGPU_OK;
-        case URHGPU_DT_U16: hipLaunchKernelGGL(k_batch_noise<URHGPU_DT_U16>, dim3(grid), dim3(256), 0, s, b, max_mag, cfg, d_noise); return URHGPU_OK;
-        case URHGPU_DT_F32: hipLaunchKernelGGL(k_batch_noise<URHGPU_DT_F32>, dim3(grid), dim3(256), 0, s, b, max_mag, cfg, d_noise); return URHGPU_OK;
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(k_batch_noise<dt.value>, dim3(grid), dim3(256), 0, s, b, max_mag, cfg, d_noise);
+        return URHGPU_OK;
+    });
 }
 
-template <int DT, int MOD>
-static void launch_batch_bits_dn_3(const RunArgs &a, const BatchArgs &b, unsigned grid, hipStream_t s) {
-    if (a.order == 2) hipLaunchKernelGGL((k_batch_bits<DT, MOD, true, true>), dim3(grid), dim3(64), 0, s, a, b);
-    else hipLaunchKernelGGL((k_batch_bits<DT, MOD, false, true>), dim3(grid), dim3(64), 0, s, a, b);
-}
-template <int DT>
-static int launch_batch_bits_dn_2(const RunArgs &a, const BatchArgs &b, int mod, unsigned grid, hipStream_t s) {
-    switch (mod) {
-        case URHGPU_MOD_ASK: launch_batch_bits_dn_3<DT, URHGPU_MOD_ASK>(a, b, grid, s); return URHGPU_OK;
-        case URHGPU_MOD_FSK: launch_batch_bits_dn_3<DT, URHGPU_MOD_FSK>(a, b, grid, s); return URHGPU_OK;
-        default: return URHGPU_ERR_UNSUPPORTED;
-    }
-}
 static int launch_batch_bits_dn(const RunArgs &a, const BatchArgs &b, int dtype, int mod, unsigned grid, hipStream_t s) {
-    switch (dtype) {
-        case URHGPU_DT_I8: return launch_batch_bits_dn_2<URHGPU_DT_I8>(a, b, mod, grid, s);
-        case URHGPU_DT_U8: return launch_batch_bits_dn_2<URHGPU_DT_U8>(a, b, mod, grid, s);
-        case URHGPU_DT_I16: return launch_batch_bits_dn_2<URHGPU_DT_I16>(a, b, mod, grid, s);
-        case URHGPU_DT_U16: return launch_batch_bits_dn_2<URHGPU_DT_U16>(a, b, mod, grid, s);
-        case URHGPU_DT_F32: return launch_batch_bits_dn_2<URHGPU_DT_F32>(a, b, mod, grid, s);
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(dtype, [&](auto dt) {
+        return dispatch_mod<URHGPU_MOD_ASK, URHGPU_MOD_FSK>(mod, URHGPU_ERR_UNSUPPORTED, [&](auto m) {
+            return dispatch_bool(a.order == 2, [&](auto o2) {
+                hipLaunchKernelGGL((k_batch_bits<dt.value, m.value, o2.value, true>), dim3(grid), dim3(64), 0, s, a, b);
+                return URHGPU_OK;
+            });
+        });
+    });
 }
 
 }  // namespace urh

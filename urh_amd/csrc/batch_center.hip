@@ -98,41 +98,25 @@ __global__ __launch_bounds__(64) void k_batch_center_publish(const MsgState *st,
     }
 }
 
-template <int DT, int MOD>
-static void launch_batch_demod_3(const RunArgs &a, const BatchArgs &b, bool dn, unsigned grid, hipStream_t s) {
-    if (dn) hipLaunchKernelGGL((k_batch_demod<DT, MOD, true>), dim3(grid), dim3(kBdBlock), 0, s, a, b);
-    else hipLaunchKernelGGL((k_batch_demod<DT, MOD, false>), dim3(grid), dim3(kBdBlock), 0, s, a, b);
-}
-template <int DT>
-static int launch_batch_demod_2(const RunArgs &a, const BatchArgs &b, int mod, bool dn, unsigned grid, hipStream_t s) {
-    switch (mod) {
-        case URHGPU_MOD_ASK: launch_batch_demod_3<DT, URHGPU_MOD_ASK>(a, b, dn, grid, s); return URHGPU_OK;
-        case URHGPU_MOD_FSK: launch_batch_demod_3<DT, URHGPU_MOD_FSK>(a, b, dn, grid, s); return URHGPU_OK;
-        default: return URHGPU_ERR_UNSUPPORTED;
-    }
-}
 static int launch_batch_demod(const RunArgs &a, const BatchArgs &b, int dtype, int mod, bool dn, unsigned grid, hipStream_t s) {
-    switch (dtype) {
-        case URHGPU_DT_I8: return launch_batch_demod_2<URHGPU_DT_I8>(a, b, mod, dn, grid, s);
-        case URHGPU_DT_U8: return launch_batch_demod_2<URHGPU_DT_U8>(a, b, mod, dn, grid, s);
-        case URHGPU_DT_I16: return launch_batch_demod_2<URHGPU_DT_I16>(a, b, mod, dn, grid, s);
-        case URHGPU_DT_U16: return launch_batch_demod_2<URHGPU_DT_U16>(a, b, mod, dn, grid, s);
-        case URHGPU_DT_F32: return launch_batch_demod_2<URHGPU_DT_F32>(a, b, mod, dn, grid, s);
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(dtype, [&](auto dt) {
+        return dispatch_mod<URHGPU_MOD_ASK, URHGPU_MOD_FSK>(mod, URHGPU_ERR_UNSUPPORTED, [&](auto m) {
+            return dispatch_bool(dn, [&](auto dnoise) {
+                hipLaunchKernelGGL((k_batch_demod<dt.value, m.value, dnoise.value>), dim3(grid), dim3(kBdBlock), 0, s, a, b);
+                return URHGPU_OK;
+            });
+        });
+    });
 }
 
 // the qad-input walk: MOD x ORDER2 (the sample type plays no part)
 static int launch_batch_bits_qin(const RunArgs &a, const BatchArgs &b, int mod, unsigned grid, hipStream_t s) {
-    constexpr int F = URHGPU_DT_F32;
-    if (mod == URHGPU_MOD_ASK) {
-        if (a.order == 2) hipLaunchKernelGGL((k_batch_bits<F, URHGPU_MOD_ASK, true, false, true>), dim3(grid), dim3(64), 0, s, a, b);
-        else hipLaunchKernelGGL((k_batch_bits<F, URHGPU_MOD_ASK, false, false, true>), dim3(grid), dim3(64), 0, s, a, b);
-    } else if (mod == URHGPU_MOD_FSK) {
-        if (a.order == 2) hipLaunchKernelGGL((k_batch_bits<F, URHGPU_MOD_FSK, true, false, true>), dim3(grid), dim3(64), 0, s, a, b);
-        else hipLaunchKernelGGL((k_batch_bits<F, URHGPU_MOD_FSK, false, false, true>), dim3(grid), dim3(64), 0, s, a, b);
-    } else return URHGPU_ERR_UNSUPPORTED;
-    return URHGPU_OK;
+    return dispatch_mod<URHGPU_MOD_ASK, URHGPU_MOD_FSK>(mod, URHGPU_ERR_UNSUPPORTED, [&](auto m) {
+        return dispatch_bool(a.order == 2, [&](auto o2) {
+            hipLaunchKernelGGL((k_batch_bits<URHGPU_DT_F32, m.value, o2.value, false, true>), dim3(grid), dim3(64), 0, s, a, b);
+            return URHGPU_OK;
+        });
+    });
 }
 
 // the argument checks the center outputs share: capacities against what k captures need

@@ -229,13 +229,10 @@ int urhgpu_batch_dc_correct_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t total
     memset(&b, 0, sizeof(b));                              // no work buffer: batch_capture then vouches for the samples alone
     b.iq = d_iq; b.start = d_start; b.plan = d_plan; b.k = k; b.total = total;
     b.sps = 1; b.bps = 1;
-    switch (dtype) {
-        case URHGPU_DT_I8: launch_batch_dc<int8_t>(b, d_out, d_mean, ctx->stream); break;
-        case URHGPU_DT_U8: launch_batch_dc<uint8_t>(b, d_out, d_mean, ctx->stream); break;
-        case URHGPU_DT_I16: launch_batch_dc<int16_t>(b, d_out, d_mean, ctx->stream); break;
-        case URHGPU_DT_U16: launch_batch_dc<uint16_t>(b, d_out, d_mean, ctx->stream); break;
-        default: launch_batch_dc<float>(b, d_out, d_mean, ctx->stream); break;
-    }
+    URH_TRY(dispatch_dtype(dtype, [&](auto dt) {           // (the range check above has refused every other code)
+        launch_batch_dc<typename decltype(dt)::type>(b, d_out, d_mean, ctx->stream);
+        return URHGPU_OK;
+    }));
     ctx->batch_launches += 2;
     URH_HIP(hipGetLastError());
     return URHGPU_OK;

@@ -21,12 +21,6 @@
 
 namespace urh {
 
-template <int DT>
-static void launch_each_bits(const RunArgs &a, const BatchArgs &b, int mod, unsigned grid, hipStream_t s) {
-    if (mod == URHGPU_MOD_ASK) hipLaunchKernelGGL((k_batch_bits<DT, URHGPU_MOD_ASK, false, true, false, true>), dim3(grid), dim3(64), 0, s, a, b);
-    else hipLaunchKernelGGL((k_batch_bits<DT, URHGPU_MOD_FSK, false, true, false, true>), dim3(grid), dim3(64), 0, s, a, b);
-}
-
 // one walk launch over the launch-order slice [lo, lo + n) of modulation `mod`
 static int launch_each_walk(int dtype, int mod, float noise_threshold, const urhgpu_noise_result *d_noise, BatchArgs b, int64_t lo, int64_t n, hipStream_t s) {
     urhgpu_params pp;
@@ -37,14 +31,12 @@ static int launch_each_walk(int dtype, int mod, float noise_threshold, const urh
     a.d_noise = (const float *)d_noise;
     b.each_lo = lo; b.each_n = n;
     const unsigned grid = (unsigned)n;
-    switch (dtype) {
-        case URHGPU_DT_I8: launch_each_bits<URHGPU_DT_I8>(a, b, mod, grid, s); return URHGPU_OK;
-        case URHGPU_DT_U8: launch_each_bits<URHGPU_DT_U8>(a, b, mod, grid, s); return URHGPU_OK;
-        case URHGPU_DT_I16: launch_each_bits<URHGPU_DT_I16>(a, b, mod, grid, s); return URHGPU_OK;
-        case URHGPU_DT_U16: launch_each_bits<URHGPU_DT_U16>(a, b, mod, grid, s); return URHGPU_OK;
-        case URHGPU_DT_F32: launch_each_bits<URHGPU_DT_F32>(a, b, mod, grid, s); return URHGPU_OK;
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(dtype, [&](auto dt) {
+        return dispatch_mod<URHGPU_MOD_ASK, URHGPU_MOD_FSK>(mod, URHGPU_ERR_UNSUPPORTED, [&](auto m) {
+            hipLaunchKernelGGL((k_batch_bits<dt.value, m.value, false, true, false, true>), dim3(grid), dim3(64), 0, s, a, b);
+            return URHGPU_OK;
+        });
+    });
 }
 
 // a record of the table as the host accepts it (the device checks every record again: batch_each_ok)
@@ -156,13 +148,10 @@ int urhgpu_batch_msg_records_each_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t
     const unsigned grid = (unsigned)std::max<int64_t>(k, 1), blocks = (unsigned)std::max<int64_t>(std::min<int64_t>(cap_rec, kRecMaxBlocks), 1);
     launch_batch_rec_dir(a, s);
     hipLaunchKernelGGL(k_batch_rec_pos<true>, dim3(grid), dim3(64), 0, s, a);
-    switch (dtype) {
-        case URHGPU_DT_I8: hipLaunchKernelGGL((k_batch_msg_records<URHGPU_DT_I8, true>), dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        case URHGPU_DT_U8: hipLaunchKernelGGL((k_batch_msg_records<URHGPU_DT_U8, true>), dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        case URHGPU_DT_I16: hipLaunchKernelGGL((k_batch_msg_records<URHGPU_DT_I16, true>), dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        case URHGPU_DT_U16: hipLaunchKernelGGL((k_batch_msg_records<URHGPU_DT_U16, true>), dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        default: hipLaunchKernelGGL((k_batch_msg_records<URHGPU_DT_F32, true>), dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-    }
+    URH_TRY(dispatch_dtype(dtype, [&](auto dt) {           // (the range check above has refused every other code)
+        hipLaunchKernelGGL((k_batch_msg_records<dt.value, true>), dim3(blocks), dim3(kRecThreads), 0, s, a);
+        return URHGPU_OK;
+    }));
     ctx->batch_launches += 3;
     URH_HIP(hipGetLastError());
     return URHGPU_OK;

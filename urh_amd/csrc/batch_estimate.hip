@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "launchers.hpp"
 
 // seg_above<F32> takes the magnitude's square root with __builtin_sqrtf, which the compiler expands into two v_fma_f32.  In this file the
@@ -183,14 +184,10 @@ __global__ __launch_bounds__(64) void k_batch_seg_pack(const BatchSegArgs b) {
 }
 
 static int launch_batch_segments(const BatchSegArgs &b, int dtype, unsigned grid, hipStream_t s) {
-    switch (dtype) {
-        case URHGPU_DT_I8: hipLaunchKernelGGL(k_batch_segments<URHGPU_DT_I8>, dim3(grid), dim3(64), 0, s, b); return URHGPU_OK;
-        case URHGPU_DT_U8: hipLaunchKernelGGL(k_batch_segments<URHGPU_DT_U8>, dim3(grid), dim3(64), 0, s, b); return URHGPU_OK;
-        case URHGPU_DT_I16: hipLaunchKernelGGL(k_batch_segments<URHGPU_DT_I16>, dim3(grid), dim3(64), 0, s, b); return URHGPU_OK;
-        case URHGPU_DT_U16: hipLaunchKernelGGL(k_batch_segments<URHGPU_DT_U16>, dim3(grid), dim3(64), 0, s, b); return URHGPU_OK;
-        case URHGPU_DT_F32: hipLaunchKernelGGL(k_batch_segments<URHGPU_DT_F32>, dim3(grid), dim3(64), 0, s, b); return URHGPU_OK;
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(k_batch_segments<dt.value>, dim3(grid), dim3(64), 0, s, b);
+        return URHGPU_OK;
+    });
 }
 
 }  // namespace urh

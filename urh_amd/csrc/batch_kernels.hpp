@@ -35,6 +35,7 @@ __host__ __device__ __forceinline__ float batch_fsqrt(float x) {
 #include "common.hpp"
 #include "compact.hpp"
 #include "demod_prims.hpp"
+#include "dispatch.hpp"
 
 namespace urh {
 

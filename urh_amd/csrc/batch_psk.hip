@@ -126,20 +126,6 @@ __global__ __launch_bounds__(64) void k_batch_costas(const CostasArgs a0, const 
     }
 }
 
-template <int DT, int ORDER>
-static void launch_batch_costas_3(const CostasArgs &a, const BatchArgs &b, const urhgpu_noise_result *d_noise, unsigned grid, hipStream_t s) {
-    if (d_noise) hipLaunchKernelGGL((k_batch_costas<DT, ORDER, true>), dim3(grid), dim3(64), 0, s, a, b, d_noise);
-    else hipLaunchKernelGGL((k_batch_costas<DT, ORDER, false>), dim3(grid), dim3(64), 0, s, a, b, d_noise);
-}
-template <int DT>
-static int launch_batch_costas_2(const CostasArgs &a, const BatchArgs &b, const urhgpu_noise_result *d_noise, unsigned grid, hipStream_t s) {
-    switch (a.loop_order) {
-        case 2: launch_batch_costas_3<DT, 2>(a, b, d_noise, grid, s); return URHGPU_OK;
-        case 4: launch_batch_costas_3<DT, 4>(a, b, d_noise, grid, s); return URHGPU_OK;
-        default: return URHGPU_ERR_UNSUPPORTED;            // the reference leaves the output unwritten
-    }
-}
-
 // PSK parameters a batch accepts: batch_check_params_psk's, and a loop order the reference writes an output for
 int batch_costas_check(const urhgpu_params *p) {
     URH_TRY(batch_check_params_psk(p));
@@ -155,14 +141,15 @@ int launch_batch_costas(const urhgpu_params *p, const BatchArgs &b, const urhgpu
     a.iq = b.iq; a.n = b.total; a.out = b.qad;
     URH_TRY(costas_args(p, a));
     const unsigned grid = (unsigned)std::max<int64_t>((b.k + kBcTile - 1) / kBcTile, 1);
-    switch (p->dtype) {
-        case URHGPU_DT_I8: return launch_batch_costas_2<URHGPU_DT_I8>(a, b, d_noise, grid, s);
-        case URHGPU_DT_U8: return launch_batch_costas_2<URHGPU_DT_U8>(a, b, d_noise, grid, s);
-        case URHGPU_DT_I16: return launch_batch_costas_2<URHGPU_DT_I16>(a, b, d_noise, grid, s);
-        case URHGPU_DT_U16: return launch_batch_costas_2<URHGPU_DT_U16>(a, b, d_noise, grid, s);
-        case URHGPU_DT_F32: return launch_batch_costas_2<URHGPU_DT_F32>(a, b, d_noise, grid, s);
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(p->dtype, [&](auto dt) {
+        // (any other loop order: the reference leaves the output unwritten)
+        return dispatch_one_of<2, 4>(a.loop_order, URHGPU_ERR_UNSUPPORTED, [&](auto order) {
+            return dispatch_bool(d_noise != nullptr, [&](auto dn) {
+                hipLaunchKernelGGL((k_batch_costas<dt.value, order.value, dn.value>), dim3(grid), dim3(64), 0, s, a, b, d_noise);
+                return URHGPU_OK;
+            });
+        });
+    });
 }
 
 }  // namespace urh

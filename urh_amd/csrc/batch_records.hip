@@ -74,13 +74,10 @@ int urhgpu_batch_msg_records_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t tota
     const unsigned grid = (unsigned)std::max<int64_t>(k, 1), blocks = (unsigned)std::max<int64_t>(std::min<int64_t>(cap_rec, kRecMaxBlocks), 1);
     hipLaunchKernelGGL(k_batch_rec_dir, dim3(1), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_batch_rec_pos<false>, dim3(grid), dim3(64), 0, s, a);
-    switch (p->dtype) {
-        case URHGPU_DT_I8: hipLaunchKernelGGL(k_batch_msg_records<URHGPU_DT_I8>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        case URHGPU_DT_U8: hipLaunchKernelGGL(k_batch_msg_records<URHGPU_DT_U8>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        case URHGPU_DT_I16: hipLaunchKernelGGL(k_batch_msg_records<URHGPU_DT_I16>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        case URHGPU_DT_U16: hipLaunchKernelGGL(k_batch_msg_records<URHGPU_DT_U16>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        default: hipLaunchKernelGGL(k_batch_msg_records<URHGPU_DT_F32>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-    }
+    URH_TRY(dispatch_dtype(p->dtype, [&](auto dt) {        // (batch_check_params has refused every other code)
+        hipLaunchKernelGGL(k_batch_msg_records<dt.value>, dim3(blocks), dim3(kRecThreads), 0, s, a);
+        return URHGPU_OK;
+    }));
     ctx->batch_launches += 3;
     URH_HIP(hipGetLastError());
     return URHGPU_OK;

@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "launchers.hpp"
 #include "pairwise.hpp"
 
@@ -290,19 +291,15 @@ int launch_chunk_stats(const void *d_src, int dtype, int64_t n_rows, void *d_dst
     if (n_rows <= 0 || n_rows > (int64_t(1) << 31) || store_rows < 0 || store_rows > n_rows) return URHGPU_ERR_ARG;
     const int64_t ne = 2 * n_rows, ns = d_dst ? 2 * store_rows : 0;
     const int nb = (int)chunk_stats_blocks(dtype, n_rows);
-    switch (dtype) {
-        case URHGPU_DT_F32: {
+    return dispatch_dtype(dtype, [&](auto dt) {
+        if constexpr (dt.value == URHGPU_DT_F32) {
             float *ps = (float *)scratch, *pm = ps + nb;
             hipLaunchKernelGGL(k_chunk_stats_f32, dim3((unsigned)nb), dim3(kCsBlock), 0, s, (const float *)d_src, ne, (float *)d_dst, ns, ps, pm);
             hipLaunchKernelGGL(k_chunk_finish_f32, dim3(1), dim3(kCsBlock), 0, s, ps, pm, nb, h_out);
-            return URHGPU_OK;
-        }
-        case URHGPU_DT_I8: chunk_stats_int_launch<int8_t>(d_src, ne, d_dst, ns, scratch, nb, h_out, s); return URHGPU_OK;
-        case URHGPU_DT_U8: chunk_stats_int_launch<uint8_t>(d_src, ne, d_dst, ns, scratch, nb, h_out, s); return URHGPU_OK;
-        case URHGPU_DT_I16: chunk_stats_int_launch<int16_t>(d_src, ne, d_dst, ns, scratch, nb, h_out, s); return URHGPU_OK;
-        case URHGPU_DT_U16: chunk_stats_int_launch<uint16_t>(d_src, ne, d_dst, ns, scratch, nb, h_out, s); return URHGPU_OK;
-        default: return URHGPU_ERR_DTYPE;
-    }
+        } else
+            chunk_stats_int_launch<typename decltype(dt)::type>(d_src, ne, d_dst, ns, scratch, nb, h_out, s);
+        return URHGPU_OK;
+    });
 }
 
 }  // namespace urh

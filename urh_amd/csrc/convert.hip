@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "launchers.hpp"
 
 namespace urh {
@@ -54,30 +55,6 @@ static int conv_launch(const void *src, void *dst, int64_t n, hipStream_t s) {
     return URHGPU_OK;
 }
 
-template <typename S>
-static int conv_from(const void *src, int dst_dtype, void *dst, int64_t n, hipStream_t s);
-#define URH_CONV_CASE(S, code, D) case code: return conv_launch<S, D>(src, dst, n, s);
-template <> int conv_from<uint8_t>(const void *src, int d, void *dst, int64_t n, hipStream_t s) {
-    switch (d) { URH_CONV_CASE(uint8_t, URHGPU_DT_I8, int8_t) URH_CONV_CASE(uint8_t, URHGPU_DT_I16, int16_t) URH_CONV_CASE(uint8_t, URHGPU_DT_U16, uint16_t)
-                 URH_CONV_CASE(uint8_t, URHGPU_DT_F32, float) default: return URHGPU_ERR_DTYPE; }
-}
-template <> int conv_from<int8_t>(const void *src, int d, void *dst, int64_t n, hipStream_t s) {
-    switch (d) { URH_CONV_CASE(int8_t, URHGPU_DT_U8, uint8_t) URH_CONV_CASE(int8_t, URHGPU_DT_I16, int16_t) URH_CONV_CASE(int8_t, URHGPU_DT_U16, uint16_t)
-                 URH_CONV_CASE(int8_t, URHGPU_DT_F32, float) default: return URHGPU_ERR_DTYPE; }
-}
-template <> int conv_from<uint16_t>(const void *src, int d, void *dst, int64_t n, hipStream_t s) {
-    switch (d) { URH_CONV_CASE(uint16_t, URHGPU_DT_I8, int8_t) URH_CONV_CASE(uint16_t, URHGPU_DT_U8, uint8_t) URH_CONV_CASE(uint16_t, URHGPU_DT_I16, int16_t)
-                 URH_CONV_CASE(uint16_t, URHGPU_DT_F32, float) default: return URHGPU_ERR_DTYPE; }
-}
-template <> int conv_from<int16_t>(const void *src, int d, void *dst, int64_t n, hipStream_t s) {
-    switch (d) { URH_CONV_CASE(int16_t, URHGPU_DT_I8, int8_t) URH_CONV_CASE(int16_t, URHGPU_DT_U8, uint8_t) URH_CONV_CASE(int16_t, URHGPU_DT_U16, uint16_t)
-                 URH_CONV_CASE(int16_t, URHGPU_DT_F32, float) default: return URHGPU_ERR_DTYPE; }
-}
-template <> int conv_from<float>(const void *src, int d, void *dst, int64_t n, hipStream_t s) {
-    switch (d) { URH_CONV_CASE(float, URHGPU_DT_I8, int8_t) URH_CONV_CASE(float, URHGPU_DT_U8, uint8_t) URH_CONV_CASE(float, URHGPU_DT_I16, int16_t)
-                 URH_CONV_CASE(float, URHGPU_DT_U16, uint16_t) default: return URHGPU_ERR_DTYPE; }
-}
-
 // ---- plain numpy casts (ndarray.astype / assignment into an array of another type, no IQArray scaling) -------------------
 // integer -> float32 is exact; float32 -> integer is the C cast as x86-64 evaluates it (truncation toward zero through
 // int32, low bits kept) -- what `IQArray.__setitem__` does with a filtered complex64 range (IQArray.py:31-33).
@@ -98,25 +75,13 @@ static int astype_launch(const void *src, void *dst, int64_t n, hipStream_t s) {
 // one side is float32 (the filters' working type), the other one of the four integer sample types
 int launch_astype(const void *src, int src_dtype, void *dst, int dst_dtype, int64_t n, hipStream_t s) {
     if (n <= 0) return URHGPU_OK;
-    if (dst_dtype == URHGPU_DT_F32) {
-        switch (src_dtype) {
-            case URHGPU_DT_I8: return astype_launch<int8_t, float>(src, dst, n, s);
-            case URHGPU_DT_U8: return astype_launch<uint8_t, float>(src, dst, n, s);
-            case URHGPU_DT_I16: return astype_launch<int16_t, float>(src, dst, n, s);
-            case URHGPU_DT_U16: return astype_launch<uint16_t, float>(src, dst, n, s);
-            default: return URHGPU_ERR_DTYPE;
-        }
-    }
-    if (src_dtype == URHGPU_DT_F32) {
-        switch (dst_dtype) {
-            case URHGPU_DT_I8: return astype_launch<float, int8_t>(src, dst, n, s);
-            case URHGPU_DT_U8: return astype_launch<float, uint8_t>(src, dst, n, s);
-            case URHGPU_DT_I16: return astype_launch<float, int16_t>(src, dst, n, s);
-            case URHGPU_DT_U16: return astype_launch<float, uint16_t>(src, dst, n, s);
-            default: return URHGPU_ERR_DTYPE;
-        }
-    }
-    return URHGPU_ERR_DTYPE;
+    if ((src_dtype == URHGPU_DT_F32) == (dst_dtype == URHGPU_DT_F32)) return URHGPU_ERR_DTYPE;
+    const bool from_float = src_dtype == URHGPU_DT_F32;
+    return dispatch_dtype(from_float ? dst_dtype : src_dtype, [&](auto dt) {
+        using T = typename decltype(dt)::type;
+        if constexpr (dt.value == URHGPU_DT_F32) return URHGPU_ERR_DTYPE;
+        else return from_float ? astype_launch<float, T>(src, dst, n, s) : astype_launch<T, float>(src, dst, n, s);
+    });
 }
 
 // ---- PCM frames of a WAV file -> float32 IQ (Signal.__load_wav_file, Signal.py:114-173) ----------------------------------
@@ -152,14 +117,12 @@ int launch_pcm_to_iq(const void *raw, int64_t n_frames, int channels, int width,
 // n = number of VALUES (2 per IQ sample); src_dtype != dst_dtype
 int launch_convert(const void *src, int src_dtype, void *dst, int dst_dtype, int64_t n, hipStream_t s) {
     if (n <= 0) return URHGPU_OK;
-    switch (src_dtype) {
-        case URHGPU_DT_U8: return conv_from<uint8_t>(src, dst_dtype, dst, n, s);
-        case URHGPU_DT_I8: return conv_from<int8_t>(src, dst_dtype, dst, n, s);
-        case URHGPU_DT_U16: return conv_from<uint16_t>(src, dst_dtype, dst, n, s);
-        case URHGPU_DT_I16: return conv_from<int16_t>(src, dst_dtype, dst, n, s);
-        case URHGPU_DT_F32: return conv_from<float>(src, dst_dtype, dst, n, s);
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(src_dtype, [&](auto from) {
+        return dispatch_dtype(dst_dtype, [&](auto to) {
+            if constexpr (from.value == to.value) return URHGPU_ERR_DTYPE;
+            else return conv_launch<typename decltype(from)::type, typename decltype(to)::type>(src, dst, n, s);
+        });
+    });
 }
 
 }  // namespace urh

@@ -40,6 +40,7 @@
 #include "cmul.hpp"
 #include "common.hpp"
 #include "costas_prims.hpp"
+#include "dispatch.hpp"
 #include "launchers.hpp"
 #include "glibc_sincosf.h"
 
@@ -641,9 +642,9 @@ static int launch_costas_dt(const CostasArgs &a, void *scratch, urhgpu_ctx *ctx)
     }
     if (ctx->tune_costas_dev_rounds >= 0 || ctx->pipelined) {
         const int rounds = ctx->tune_costas_dev_rounds >= 0 ? ctx->tune_costas_dev_rounds : costas_auto_rounds((a.n - 1 + kChunk - 1) / kChunk);
-        return a.loop_order == 4 ? launch_costas_dev<DT, 4>(a, scratch, ctx, rounds, h_stats) : launch_costas_dev<DT, 2>(a, scratch, ctx, rounds, h_stats);
+        return dispatch_bool(a.loop_order == 4, [&](auto o4) { return launch_costas_dev<DT, o4.value ? 4 : 2>(a, scratch, ctx, rounds, h_stats); });
     }
-    return a.loop_order == 4 ? launch_costas_spec<DT, 4>(a, scratch, ctx) : launch_costas_spec<DT, 2>(a, scratch, ctx);
+    return dispatch_bool(a.loop_order == 4, [&](auto o4) { return launch_costas_spec<DT, o4.value ? 4 : 2>(a, scratch, ctx); });
 }
 
 template <int DT, int ORDER>
@@ -713,13 +714,7 @@ int launch_costas(urhgpu_ctx *ctx, const void *d_iq, int64_t n, const urhgpu_par
     CostasArgs a;
     a.iq = d_iq; a.n = n; a.out = d_qad; a.d_noise = d_noise;
     URH_TRY(costas_args(p, a));
-    switch (p->dtype) {
-        case URHGPU_DT_I8: return launch_costas_dt<URHGPU_DT_I8>(a, scratch, ctx);
-        case URHGPU_DT_U8: return launch_costas_dt<URHGPU_DT_U8>(a, scratch, ctx);
-        case URHGPU_DT_I16: return launch_costas_dt<URHGPU_DT_I16>(a, scratch, ctx);
-        case URHGPU_DT_U16: return launch_costas_dt<URHGPU_DT_U16>(a, scratch, ctx);
-        default: return launch_costas_dt<URHGPU_DT_F32>(a, scratch, ctx);
-    }
+    return dispatch_dtype(p->dtype, [&](auto dt) { return launch_costas_dt<dt.value>(a, scratch, ctx); });      // (costas_args has refused every other code)
 }
 
 // ---- sharded captures: one rank's Costas pass (include/urhgpu.h, "PSK across shards") ----------------------------------------
@@ -865,30 +860,25 @@ static int costas_shard_resolve_t(urhgpu_ctx *ctx, const CostasArgsSh &a, int64_
     return URHGPU_OK;
 }
 
-#define URH_COSTAS_SHARD_DISPATCH(FN, ...)                                                                                       \
-    switch (cs.p.dtype) {                                                                                                        \
-        case URHGPU_DT_I8: return a.loop_order == 4 ? FN<URHGPU_DT_I8, 4>(__VA_ARGS__) : FN<URHGPU_DT_I8, 2>(__VA_ARGS__);        \
-        case URHGPU_DT_U8: return a.loop_order == 4 ? FN<URHGPU_DT_U8, 4>(__VA_ARGS__) : FN<URHGPU_DT_U8, 2>(__VA_ARGS__);        \
-        case URHGPU_DT_I16: return a.loop_order == 4 ? FN<URHGPU_DT_I16, 4>(__VA_ARGS__) : FN<URHGPU_DT_I16, 2>(__VA_ARGS__);     \
-        case URHGPU_DT_U16: return a.loop_order == 4 ? FN<URHGPU_DT_U16, 4>(__VA_ARGS__) : FN<URHGPU_DT_U16, 2>(__VA_ARGS__);     \
-        case URHGPU_DT_F32: return a.loop_order == 4 ? FN<URHGPU_DT_F32, 4>(__VA_ARGS__) : FN<URHGPU_DT_F32, 2>(__VA_ARGS__);     \
-        default: return URHGPU_ERR_DTYPE;                                                                                        \
-    }
-
 int launch_costas_shard_spec(urhgpu_ctx *ctx, const CostasShard &cs, void *d_summary) {
     CostasArgsSh a;
     int64_t nc = 0;
     URH_TRY(costas_shard_args(cs, a, nc));
-    URH_COSTAS_SHARD_DISPATCH(costas_shard_spec_t, ctx, a, nc, cs.scratch, d_summary)
+    return dispatch_dtype(cs.p.dtype, [&](auto dt) {
+        return dispatch_bool(a.loop_order == 4, [&](auto o4) { return costas_shard_spec_t<dt.value, o4.value ? 4 : 2>(ctx, a, nc, cs.scratch, d_summary); });
+    });
 }
 
 int launch_costas_shard_resolve(urhgpu_ctx *ctx, const CostasShard &cs, uint32_t freq_bits, uint32_t phase_bits, void *d_end) {
     CostasArgsSh a;
     int64_t nc = 0;
     URH_TRY(costas_shard_args(cs, a, nc));
-    URH_COSTAS_SHARD_DISPATCH(costas_shard_resolve_t, ctx, a, nc, cs.scratch, freq_bits, phase_bits, d_end)
+    return dispatch_dtype(cs.p.dtype, [&](auto dt) {
+        return dispatch_bool(a.loop_order == 4, [&](auto o4) {
+            return costas_shard_resolve_t<dt.value, o4.value ? 4 : 2>(ctx, a, nc, cs.scratch, freq_bits, phase_bits, d_end);
+        });
+    });
 }
-#undef URH_COSTAS_SHARD_DISPATCH
 
 // every float with |y| < 120 (bit patterns 0 .. 0x42f00000, both signs): urh_sincosf_fast against urh_sinf / urh_cosf
 __global__ __launch_bounds__(256) void k_test_sincosf_fast(unsigned long long *mismatches) {

@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "dc_sub.hpp"
+#include "dispatch.hpp"
 
 namespace urh {
 
@@ -565,13 +566,11 @@ int urhgpu_dc_correct_dev(urhgpu_ctx *ctx, const void *d_in, int64_t n, int dtyp
     URH_TRY(dc_work_area(ctx, dc_work_bytes(n, dtype)));
     ctx->dc_shard_n = -1;                                                   // (a shard's chunk records are overwritten)
     char *work = (char *)ctx->dc_work.base;
-    switch (dtype) {
-        case URHGPU_DT_I8: dc_launch_int<int8_t>(d_in, d_out, n, work, d_mean, ctx->stream); break;
-        case URHGPU_DT_U8: dc_launch_int<uint8_t>(d_in, d_out, n, work, d_mean, ctx->stream); break;
-        case URHGPU_DT_I16: dc_launch_int<int16_t>(d_in, d_out, n, work, d_mean, ctx->stream); break;
-        case URHGPU_DT_U16: dc_launch_int<uint16_t>(d_in, d_out, n, work, d_mean, ctx->stream); break;
-        default: dc_launch_f32(d_in, d_out, n, work, d_mean, ctx->stream); break;
-    }
+    URH_TRY(dispatch_dtype(dtype, [&](auto dt) {           // (the range check above has refused every other code)
+        if constexpr (dt.value == URHGPU_DT_F32) dc_launch_f32(d_in, d_out, n, work, d_mean, ctx->stream);
+        else dc_launch_int<typename decltype(dt)::type>(d_in, d_out, n, work, d_mean, ctx->stream);
+        return URHGPU_OK;
+    }));
     URH_HIP(hipGetLastError());
     URH_HIP(hipEventRecord(ctx->ev_dc, ctx->stream));
     return URHGPU_OK;
@@ -598,17 +597,16 @@ int urhgpu_shard_dc_sums_dev(urhgpu_ctx *ctx, const void *d_in, int64_t n, int d
     long long *words = (long long *)d_words;
     if (n == 0) {
         URH_HIP(hipMemsetAsync(d_words, 0, 24, ctx->stream));
-    } else if (dtype == URHGPU_DT_F32) {
-        const DcShardArea a = dc_shard_area(work, n);
-        k_dc_chunk_sums<<<(int)std::min<int64_t>(a.n_chunks, 8 * kDcMaxGrid), kDcBlock, 0, ctx->stream>>>((const float2 *)d_in, n, a.n_chunks, a.sums);
-        k_dc_prefix_base<<<2, 1024, 0, ctx->stream>>>(a.sums, a.n_chunks, 0.0, 0.0, nullptr, words, n);
     } else {
-        switch (dtype) {
-            case URHGPU_DT_I8: dc_launch_isum_shard<int8_t>(d_in, n, work, words, ctx->stream); break;
-            case URHGPU_DT_U8: dc_launch_isum_shard<uint8_t>(d_in, n, work, words, ctx->stream); break;
-            case URHGPU_DT_I16: dc_launch_isum_shard<int16_t>(d_in, n, work, words, ctx->stream); break;
-            default: dc_launch_isum_shard<uint16_t>(d_in, n, work, words, ctx->stream); break;
-        }
+        URH_TRY(dispatch_dtype(dtype, [&](auto dt) {       // (the range check above has refused every other code)
+            if constexpr (dt.value == URHGPU_DT_F32) {
+                const DcShardArea a = dc_shard_area(work, n);
+                k_dc_chunk_sums<<<(int)std::min<int64_t>(a.n_chunks, 8 * kDcMaxGrid), kDcBlock, 0, ctx->stream>>>((const float2 *)d_in, n, a.n_chunks, a.sums);
+                k_dc_prefix_base<<<2, 1024, 0, ctx->stream>>>(a.sums, a.n_chunks, 0.0, 0.0, nullptr, words, n);
+            } else
+                dc_launch_isum_shard<typename decltype(dt)::type>(d_in, n, work, words, ctx->stream);
+            return URHGPU_OK;
+        }));
     }
     URH_HIP(hipGetLastError());
     URH_HIP(hipEventRecord(ctx->ev_dc, ctx->stream));
@@ -668,13 +666,11 @@ int urhgpu_shard_dc_apply_dev(urhgpu_ctx *ctx, const void *d_in, int64_t n, int 
     if (d_in != d_out && (const char *)d_in < (const char *)d_out + bytes && (const char *)d_out < (const char *)d_in + bytes) return URHGPU_ERR_ARG;
     URH_TRY(dc_work_area(ctx, kDcHeader));
     char *work = (char *)ctx->dc_work.base;
-    switch (dtype) {
-        case URHGPU_DT_I8: dc_launch_apply<int8_t, double>(d_in, d_out, n, work, mean, ctx->stream); break;
-        case URHGPU_DT_U8: dc_launch_apply<uint8_t, double>(d_in, d_out, n, work, mean, ctx->stream); break;
-        case URHGPU_DT_I16: dc_launch_apply<int16_t, double>(d_in, d_out, n, work, mean, ctx->stream); break;
-        case URHGPU_DT_U16: dc_launch_apply<uint16_t, double>(d_in, d_out, n, work, mean, ctx->stream); break;
-        default: dc_launch_apply<float, float>(d_in, d_out, n, work, mean, ctx->stream); break;
-    }
+    URH_TRY(dispatch_dtype(dtype, [&](auto dt) {           // (the range check above has refused every other code)
+        using T = typename decltype(dt)::type;             // an integer capture's mean is a pair of doubles, a float32 capture's a pair of floats
+        dc_launch_apply<T, std::conditional_t<dt.value == URHGPU_DT_F32, float, double>>(d_in, d_out, n, work, mean, ctx->stream);
+        return URHGPU_OK;
+    }));
     URH_HIP(hipGetLastError());
     URH_HIP(hipEventRecord(ctx->ev_dc, ctx->stream));
     return URHGPU_OK;

@@ -34,6 +34,7 @@
 #include "cmul.hpp"
 #include "common.hpp"
 #include "demod_prims.hpp"
+#include "dispatch.hpp"
 #include "fdlibm_atan2f.h"
 #include "launchers.hpp"
 #include "runs.hpp"
@@ -1691,37 +1692,24 @@ static void launch_runs_4(RunArgs a, hipStream_t s, HotEvents *ev) {
     }
 }
 
+// The order == 2 / write_qad forks of launch_runs_4, shared by the two launchers below (the QAD source is instantiated with both WQ values, as ever).
 template <int SRC, int DT, int MOD>
-static void launch_runs_3(const RunArgs &a, bool write_qad, hipStream_t s, HotEvents *ev) {
-    if (a.order == 2) {
-        if (write_qad) launch_runs_4<SRC, DT, MOD, true, true>(a, s, ev);
-        else launch_runs_4<SRC, DT, MOD, true, false>(a, s, ev);
-    } else {
-        if (write_qad) launch_runs_4<SRC, DT, MOD, false, true>(a, s, ev);
-        else launch_runs_4<SRC, DT, MOD, false, false>(a, s, ev);
-    }
-}
-
-template <int DT>
-static int launch_runs_2(const RunArgs &a, int mod, bool write_qad, hipStream_t s, HotEvents *ev) {
-    switch (mod) {
-        case URHGPU_MOD_ASK: launch_runs_3<SRC_IQ, DT, URHGPU_MOD_ASK>(a, write_qad, s, ev); return URHGPU_OK;
-        case URHGPU_MOD_FSK: launch_runs_3<SRC_IQ, DT, URHGPU_MOD_FSK>(a, write_qad, s, ev); return URHGPU_OK;
-        case URHGPU_MOD_OTHER: launch_runs_3<SRC_IQ, DT, URHGPU_MOD_OTHER>(a, write_qad, s, ev); return URHGPU_OK;
-        default: return URHGPU_ERR_ARG;
-    }
+static int launch_runs_forks(const RunArgs &a, bool write_qad, hipStream_t s, HotEvents *ev) {
+    return dispatch_bool(a.order == 2, [&](auto o2) {
+        return dispatch_bool(write_qad, [&](auto wq) {
+            launch_runs_4<SRC, DT, MOD, o2.value, wq.value>(a, s, ev);
+            return URHGPU_OK;
+        });
+    });
 }
 
 // Fused demod + run segmentation over IQ (ASK / FSK / OTHER).
 int launch_demod_runs_iq(const RunArgs &a, int dtype, int mod, bool write_qad, hipStream_t s, HotEvents *ev) {
-    switch (dtype) {
-        case URHGPU_DT_F32: return launch_runs_2<URHGPU_DT_F32>(a, mod, write_qad, s, ev);
-        case URHGPU_DT_I8: return launch_runs_2<URHGPU_DT_I8>(a, mod, write_qad, s, ev);
-        case URHGPU_DT_U8: return launch_runs_2<URHGPU_DT_U8>(a, mod, write_qad, s, ev);
-        case URHGPU_DT_I16: return launch_runs_2<URHGPU_DT_I16>(a, mod, write_qad, s, ev);
-        case URHGPU_DT_U16: return launch_runs_2<URHGPU_DT_U16>(a, mod, write_qad, s, ev);
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(dtype, [&](auto dt) {
+        return dispatch_mod<URHGPU_MOD_ASK, URHGPU_MOD_FSK, URHGPU_MOD_OTHER>(mod, URHGPU_ERR_ARG, [&](auto m) {
+            return launch_runs_forks<SRC_IQ, dt.value, m.value>(a, write_qad, s, ev);
+        });
+    });
 }
 
 // How wide are an integer capture's phase steps?  ONE workgroup samples 4096 pairs of neighbouring samples spread over the capture and counts
@@ -1760,14 +1748,13 @@ __global__ __launch_bounds__(1024) void k_wide_probe(const void *iq, int64_t n, 
 }
 int launch_wide_probe(const void *d_iq, int dtype, int64_t n, float noise_sqrd, int32_t *h_out, hipStream_t s, const float *d_noise) {
     if (n < 2 || !d_iq || !h_out) return URHGPU_ERR_ARG;
-    switch (dtype) {
-        case URHGPU_DT_I8: hipLaunchKernelGGL(k_wide_probe<URHGPU_DT_I8>, dim3(1), dim3(1024), 0, s, d_iq, n, noise_sqrd, d_noise, h_out); break;
-        case URHGPU_DT_U8: hipLaunchKernelGGL(k_wide_probe<URHGPU_DT_U8>, dim3(1), dim3(1024), 0, s, d_iq, n, noise_sqrd, d_noise, h_out); break;
-        case URHGPU_DT_I16: hipLaunchKernelGGL(k_wide_probe<URHGPU_DT_I16>, dim3(1), dim3(1024), 0, s, d_iq, n, noise_sqrd, d_noise, h_out); break;
-        case URHGPU_DT_U16: hipLaunchKernelGGL(k_wide_probe<URHGPU_DT_U16>, dim3(1), dim3(1024), 0, s, d_iq, n, noise_sqrd, d_noise, h_out); break;
-        default: return URHGPU_ERR_DTYPE;
-    }
-    return URHGPU_OK;
+    return dispatch_dtype(dtype, [&](auto dt) {
+        if constexpr (dt.value == URHGPU_DT_F32) return URHGPU_ERR_DTYPE;      // (a question about integer captures only)
+        else {
+            hipLaunchKernelGGL(k_wide_probe<dt.value>, dim3(1), dim3(1024), 0, s, d_iq, n, noise_sqrd, d_noise, h_out);
+            return URHGPU_OK;
+        }
+    });
 }
 
 // Can a pass with these arguments be streamed (RunArgs::progress)?  Only the bit-plane kernel counts its chunks: orders 2 and 4,
@@ -1779,8 +1766,7 @@ bool runs_streamable(const RunArgs &a) {
 
 // Run segmentation over an already demodulated float32 signal (grab_pulse_lens proper).
 int launch_runs_qad(const RunArgs &a, hipStream_t s, HotEvents *ev) {
-    launch_runs_3<SRC_QAD, URHGPU_DT_F32, URHGPU_MOD_OTHER>(a, false, s, ev);
-    return URHGPU_OK;
+    return launch_runs_forks<SRC_QAD, URHGPU_DT_F32, URHGPU_MOD_OTHER>(a, false, s, ev);
 }
 
 template <int DT, int MOD>
@@ -1808,25 +1794,13 @@ static void launch_afp_3(const RunArgs &a0, int grid, hipStream_t s) {
     }
 }
 
-template <int DT>
-static int launch_afp_2(const RunArgs &a, int mod, int grid, hipStream_t s) {
-    switch (mod) {
-        case URHGPU_MOD_ASK: launch_afp_3<DT, URHGPU_MOD_ASK>(a, grid, s); return URHGPU_OK;
-        case URHGPU_MOD_FSK: launch_afp_3<DT, URHGPU_MOD_FSK>(a, grid, s); return URHGPU_OK;
-        case URHGPU_MOD_OTHER: launch_afp_3<DT, URHGPU_MOD_OTHER>(a, grid, s); return URHGPU_OK;
-        default: return URHGPU_ERR_ARG;
-    }
-}
-
 int launch_afp_demod(const RunArgs &a, int dtype, int mod, int grid, hipStream_t s) {
-    switch (dtype) {
-        case URHGPU_DT_F32: return launch_afp_2<URHGPU_DT_F32>(a, mod, grid, s);
-        case URHGPU_DT_I8: return launch_afp_2<URHGPU_DT_I8>(a, mod, grid, s);
-        case URHGPU_DT_U8: return launch_afp_2<URHGPU_DT_U8>(a, mod, grid, s);
-        case URHGPU_DT_I16: return launch_afp_2<URHGPU_DT_I16>(a, mod, grid, s);
-        case URHGPU_DT_U16: return launch_afp_2<URHGPU_DT_U16>(a, mod, grid, s);
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(dtype, [&](auto dt) {
+        return dispatch_mod<URHGPU_MOD_ASK, URHGPU_MOD_FSK, URHGPU_MOD_OTHER>(mod, URHGPU_ERR_ARG, [&](auto m) {
+            launch_afp_3<dt.value, m.value>(a, grid, s);
+            return URHGPU_OK;
+        });
+    });
 }
 
 // The seam value of a shard (urhgpu_shard_demod_dev): afp_demod's value of the sample BEFORE the shard, global sample pos_base - 1, from the
@@ -1845,25 +1819,14 @@ __global__ void k_afp_seam(const RunArgs p, float *out) {
     *out = q;
 }
 
-template <int DT>
-static int launch_seam_2(const RunArgs &a, int mod, float *d_out, hipStream_t s) {
-    switch (mod) {
-        case URHGPU_MOD_ASK: hipLaunchKernelGGL((k_afp_seam<DT, URHGPU_MOD_ASK>), dim3(1), dim3(64), 0, s, a, d_out); return URHGPU_OK;
-        case URHGPU_MOD_FSK: hipLaunchKernelGGL((k_afp_seam<DT, URHGPU_MOD_FSK>), dim3(1), dim3(64), 0, s, a, d_out); return URHGPU_OK;
-        default: return URHGPU_ERR_UNSUPPORTED;
-    }
-}
-
 int launch_afp_seam(const RunArgs &a, int dtype, int mod, float *d_out, hipStream_t s) {
     if (!a.left_halo || !d_out) return URHGPU_ERR_ARG;
-    switch (dtype) {
-        case URHGPU_DT_F32: return launch_seam_2<URHGPU_DT_F32>(a, mod, d_out, s);
-        case URHGPU_DT_I8: return launch_seam_2<URHGPU_DT_I8>(a, mod, d_out, s);
-        case URHGPU_DT_U8: return launch_seam_2<URHGPU_DT_U8>(a, mod, d_out, s);
-        case URHGPU_DT_I16: return launch_seam_2<URHGPU_DT_I16>(a, mod, d_out, s);
-        case URHGPU_DT_U16: return launch_seam_2<URHGPU_DT_U16>(a, mod, d_out, s);
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(dtype, [&](auto dt) {
+        return dispatch_mod<URHGPU_MOD_ASK, URHGPU_MOD_FSK>(mod, URHGPU_ERR_UNSUPPORTED, [&](auto m) {
+            hipLaunchKernelGGL((k_afp_seam<dt.value, m.value>), dim3(1), dim3(64), 0, s, a, d_out);
+            return URHGPU_OK;
+        });
+    });
 }
 
 void launch_test_div(uint64_t seed, int reps, unsigned long long *d_mismatches, hipStream_t s) {

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "launchers.hpp"
 #include "pairwise.hpp"
 #include "scan.hpp"
@@ -157,14 +158,7 @@ static int minmax_launch_t(const void *x, int64_t n, void *d_out2, void *scratch
 // d_out2: {min, max} in the element type
 int launch_minmax_any(const void *x, int dtype, int64_t n, void *d_out2, void *scratch, hipStream_t s) {
     if (n <= 0) return URHGPU_ERR_ARG;
-    switch (dtype) {
-        case URHGPU_DT_I8: return minmax_launch_t<int8_t>(x, n, d_out2, scratch, s);
-        case URHGPU_DT_U8: return minmax_launch_t<uint8_t>(x, n, d_out2, scratch, s);
-        case URHGPU_DT_I16: return minmax_launch_t<int16_t>(x, n, d_out2, scratch, s);
-        case URHGPU_DT_U16: return minmax_launch_t<uint16_t>(x, n, d_out2, scratch, s);
-        case URHGPU_DT_F32: return minmax_launch_t<float>(x, n, d_out2, scratch, s);
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(dtype, [&](auto dt) { return minmax_launch_t<typename decltype(dt)::type>(x, n, d_out2, scratch, s); });
 }
 
 // ---- segment_messages_from_magnitudes on caller-supplied magnitudes (auto_interpretation.pyx:55-111): the comparison

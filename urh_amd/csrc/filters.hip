@@ -17,6 +17,7 @@
 
 #include "cmul.hpp"
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "launchers.hpp"
 #include "magnitude.hpp"
 #include "noise_decide.hpp"
@@ -631,14 +632,10 @@ static void launch_mag_dt(const void *iq, int64_t n, double *out, int64_t chunk,
 
 static int launch_mag_any(int dtype, const void *iq, int64_t n, double *out, int64_t chunk, int64_t n_chunks, double *ps,
                           double *pm, double *d_sum, double *d_max, hipStream_t s) {
-    switch (dtype) {
-        case URHGPU_DT_F32: launch_mag_dt<URHGPU_DT_F32>(iq, n, out, chunk, n_chunks, ps, pm, d_sum, d_max, s); return URHGPU_OK;
-        case URHGPU_DT_I8: launch_mag_dt<URHGPU_DT_I8>(iq, n, out, chunk, n_chunks, ps, pm, d_sum, d_max, s); return URHGPU_OK;
-        case URHGPU_DT_U8: launch_mag_dt<URHGPU_DT_U8>(iq, n, out, chunk, n_chunks, ps, pm, d_sum, d_max, s); return URHGPU_OK;
-        case URHGPU_DT_I16: launch_mag_dt<URHGPU_DT_I16>(iq, n, out, chunk, n_chunks, ps, pm, d_sum, d_max, s); return URHGPU_OK;
-        case URHGPU_DT_U16: launch_mag_dt<URHGPU_DT_U16>(iq, n, out, chunk, n_chunks, ps, pm, d_sum, d_max, s); return URHGPU_OK;
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(dtype, [&](auto dt) {
+        launch_mag_dt<dt.value>(iq, n, out, chunk, n_chunks, ps, pm, d_sum, d_max, s);
+        return URHGPU_OK;
+    });
 }
 
 int launch_magnitudes(const void *iq, int dtype, int64_t n, double *out, hipStream_t s) {

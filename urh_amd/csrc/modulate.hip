@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "glibc_sincosf.h"
 #include "launchers.hpp"
 
@@ -172,13 +173,10 @@ static int launch_mod_t(const ModArgs &a, int64_t max_samples, hipStream_t s) {
     if (gx > 8192) gx = 8192;
     if (gx < 1) gx = 1;
     const dim3 grid((unsigned)gx, (unsigned)a.n_msgs), block(256);
-    switch (a.mod) {
-        case URHGPU_MOD_ASK: hipLaunchKernelGGL((k_modulate<T, URHGPU_MOD_ASK>), grid, block, 0, s, a); return URHGPU_OK;
-        case URHGPU_MOD_FSK: hipLaunchKernelGGL((k_modulate<T, URHGPU_MOD_FSK>), grid, block, 0, s, a); return URHGPU_OK;
-        case URHGPU_MOD_PSK: hipLaunchKernelGGL((k_modulate<T, URHGPU_MOD_PSK>), grid, block, 0, s, a); return URHGPU_OK;
-        case kModGfsk: hipLaunchKernelGGL((k_modulate<T, kModGfsk>), grid, block, 0, s, a); return URHGPU_OK;
-        default: return URHGPU_ERR_UNSUPPORTED;
-    }
+    return dispatch_mod<URHGPU_MOD_ASK, URHGPU_MOD_FSK, URHGPU_MOD_PSK, kModGfsk>(a.mod, URHGPU_ERR_UNSUPPORTED, [&](auto m) {
+        hipLaunchKernelGGL((k_modulate<T, m.value>), grid, block, 0, s, a);
+        return URHGPU_OK;
+    });
 }
 
 int launch_modulate(const ModArgs &a, int64_t max_samples, hipStream_t s) {
@@ -193,12 +191,11 @@ int launch_modulate(const ModArgs &a, int64_t max_samples, hipStream_t s) {
         }
         hipLaunchKernelGGL(k_gfsk_phase, dim3((unsigned)a.n_msgs), dim3(64), 0, s, a);
     }
-    switch (a.dtype) {
-        case URHGPU_DT_F32: return launch_mod_t<float>(a, max_samples, s);
-        case URHGPU_DT_I8: return launch_mod_t<int8_t>(a, max_samples, s);
-        case URHGPU_DT_I16: return launch_mod_t<int16_t>(a, max_samples, s);
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(a.dtype, [&](auto dt) {
+        using T = typename decltype(dt)::type;                 // get_numpy_dtype (:46-54) knows float32, int8 and int16
+        if constexpr (std::is_unsigned<T>::value) return URHGPU_ERR_DTYPE;
+        else return launch_mod_t<T>(a, max_samples, s);
+    });
 }
 
 }  // namespace urh

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "launchers.hpp"
 #include "scan.hpp"
 #include "seg_above.hpp"
@@ -186,14 +187,13 @@ int launch_message_ranges(const int64_t *d_rows, const int64_t *d_n_rows, int64_
     if (nb > kScanDirect) hipLaunchKernelGGL((k_scan_partials<1>), dim3(1), dim3(kScanPartialsBlock), 0, s, d_n_rows, part, nb, kScanDirect);
     hipLaunchKernelGGL((k_scan_apply<1, SegLoad, SegStore>), dim3(scan_grid(nb)), dim3(kScanBlock), 0, s, d_n_rows, ld, part, nb, SegStore{d_rows, d_seg, cap},
                        kScanDirect);
-    switch (dtype) {
-        case URHGPU_DT_F32: launch_seg_finish<URHGPU_DT_F32>(d_rows, d_n_rows, d_iq, n, thr, d_seg, cap, d_ctl, s); break;
-        case URHGPU_DT_I8: launch_seg_finish<URHGPU_DT_I8>(d_rows, d_n_rows, d_iq, n, thr, d_seg, cap, d_ctl, s); break;
-        case URHGPU_DT_U8: launch_seg_finish<URHGPU_DT_U8>(d_rows, d_n_rows, d_iq, n, thr, d_seg, cap, d_ctl, s); break;
-        case URHGPU_DT_I16: launch_seg_finish<URHGPU_DT_I16>(d_rows, d_n_rows, d_iq, n, thr, d_seg, cap, d_ctl, s); break;
-        case URHGPU_DT_U16: launch_seg_finish<URHGPU_DT_U16>(d_rows, d_n_rows, d_iq, n, thr, d_seg, cap, d_ctl, s); break;
-        case kDtAboveFlags: launch_seg_finish<kDtAboveFlags>(d_rows, d_n_rows, d_iq, n, thr, d_seg, cap, d_ctl, s); break;
-        default: return URHGPU_ERR_DTYPE;
+    if (dtype == kDtAboveFlags) {
+        launch_seg_finish<kDtAboveFlags>(d_rows, d_n_rows, d_iq, n, thr, d_seg, cap, d_ctl, s);
+    } else {
+        URH_TRY(dispatch_dtype(dtype, [&](auto dt) {
+            launch_seg_finish<dt.value>(d_rows, d_n_rows, d_iq, n, thr, d_seg, cap, d_ctl, s);
+            return URHGPU_OK;
+        }));
     }
     if (!ook_merge) return URHGPU_OK;
     const int gp = kSegParts;

@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "launchers.hpp"
 #include "magnitude.hpp"
 #include "pairwise.hpp"
@@ -226,13 +227,10 @@ int launch_msg_records(const void *d_iq, int64_t n, const urhgpu_params *p, cons
     RecArgs a{d_iq, n, out->msg_off, out->pauses, out->pos_off, out->pos, out->counts, out->cap_msg, out->cap_pos, cap_rec,
               (int64_t)p->samples_per_symbol, p->mod == URHGPU_MOD_ASK ? divisor : 1, records_norm(p->dtype), (urhgpu_msg_record *)d_rec};
     const int blocks = (int)std::min<int64_t>(cap, kRecMaxBlocks);
-    switch (p->dtype) {
-        case URHGPU_DT_I8: hipLaunchKernelGGL(k_msg_records<URHGPU_DT_I8>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        case URHGPU_DT_U8: hipLaunchKernelGGL(k_msg_records<URHGPU_DT_U8>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        case URHGPU_DT_I16: hipLaunchKernelGGL(k_msg_records<URHGPU_DT_I16>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        case URHGPU_DT_U16: hipLaunchKernelGGL(k_msg_records<URHGPU_DT_U16>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        default: hipLaunchKernelGGL(k_msg_records<URHGPU_DT_F32>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-    }
+    URH_TRY(dispatch_dtype(p->dtype, [&](auto dt) {        // (the dtype_bytes check above has refused every other code)
+        hipLaunchKernelGGL(k_msg_records<dt.value>, dim3(blocks), dim3(kRecThreads), 0, s, a);
+        return URHGPU_OK;
+    }));
     URH_HIP(hipGetLastError());
     if (h_rec) {
         hipLaunchKernelGGL(k_msg_records_mirror, dim3(1), dim3(64), 0, s, (const uint4 *)d_rec, (uint4 *)h_rec, out->counts, out->cap_msg, cap_rec);
@@ -318,13 +316,10 @@ int urhgpu_shard_msg_records_dev(urhgpu_ctx *ctx, const void *d_iq, int64_t n_lo
     a.window = window_len > 0 ? d_window : nullptr; a.window_len = window_len;
     for (int i = 0; i < URHGPU_SHARD_REC_FIRST_WORDS; ++i) a.first[i] = first[i];
     const int blocks = (int)std::min<int64_t>(cap, kRecMaxBlocks);
-    switch (p->dtype) {
-        case URHGPU_DT_I8: hipLaunchKernelGGL(k_shard_msg_records<URHGPU_DT_I8>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        case URHGPU_DT_U8: hipLaunchKernelGGL(k_shard_msg_records<URHGPU_DT_U8>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        case URHGPU_DT_I16: hipLaunchKernelGGL(k_shard_msg_records<URHGPU_DT_I16>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        case URHGPU_DT_U16: hipLaunchKernelGGL(k_shard_msg_records<URHGPU_DT_U16>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-        default: hipLaunchKernelGGL(k_shard_msg_records<URHGPU_DT_F32>, dim3(blocks), dim3(kRecThreads), 0, s, a); break;
-    }
+    URH_TRY(dispatch_dtype(p->dtype, [&](auto dt) {        // (the dtype_bytes check above has refused every other code)
+        hipLaunchKernelGGL(k_shard_msg_records<dt.value>, dim3(blocks), dim3(kRecThreads), 0, s, a);
+        return URHGPU_OK;
+    }));
     URH_HIP(hipGetLastError());
     if (h_rec) {
         hipLaunchKernelGGL(k_msg_records_mirror, dim3(1), dim3(64), 0, s, (const uint4 *)d_rec, (uint4 *)h_rec, out->counts, out->cap_msg, cap_msg);

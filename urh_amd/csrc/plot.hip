@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "launchers.hpp"
 
 namespace urh {
@@ -61,14 +62,10 @@ int launch_path_minmax(const void *samples, int dtype, int64_t start, int64_t en
     if (spp < 1 || end <= start) return URHGPU_ERR_ARG;
     const int64_t pixels = (end - start + spp - 1) / spp;
     if (pixels > 0x7fffffff) return URHGPU_ERR_ARG;
-    switch (dtype) {
-        case URHGPU_DT_I8: launch_path_t<int8_t>(samples, start, end, spp, values, pixels, s); return URHGPU_OK;
-        case URHGPU_DT_U8: launch_path_t<uint8_t>(samples, start, end, spp, values, pixels, s); return URHGPU_OK;
-        case URHGPU_DT_I16: launch_path_t<int16_t>(samples, start, end, spp, values, pixels, s); return URHGPU_OK;
-        case URHGPU_DT_U16: launch_path_t<uint16_t>(samples, start, end, spp, values, pixels, s); return URHGPU_OK;
-        case URHGPU_DT_F32: launch_path_t<float>(samples, start, end, spp, values, pixels, s); return URHGPU_OK;
-        default: return URHGPU_ERR_DTYPE;
-    }
+    return dispatch_dtype(dtype, [&](auto dt) {
+        launch_path_t<typename decltype(dt)::type>(samples, start, end, spp, values, pixels, s);
+        return URHGPU_OK;
+    });
 }
 
 }  // namespace urh

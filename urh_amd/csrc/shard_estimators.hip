@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "launchers.hpp"
 #include "magnitude.hpp"
 #include "pairwise.hpp"
@@ -119,15 +120,10 @@ int launch_mag_chunk_partials(const void *iq, int dtype, int64_t n_local, int64_
     if (nt > 65535) return URHGPU_ERR_ARG;                  // (detect_noise_level's geometry has at most 199 chunks)
     double *ps = (double *)scratch;
     double *pm = (double *)((char *)scratch + align256((size_t)n_chunks * kSpMagSlices * 8));
-    switch (dtype) {
-        case URHGPU_DT_F32: sp_mag_launch_dt<URHGPU_DT_F32>(iq, n_local, pos_base, n_total, chunk, kf, nt, ps, pm, d_sum, d_max, s); break;
-        case URHGPU_DT_I8: sp_mag_launch_dt<URHGPU_DT_I8>(iq, n_local, pos_base, n_total, chunk, kf, nt, ps, pm, d_sum, d_max, s); break;
-        case URHGPU_DT_U8: sp_mag_launch_dt<URHGPU_DT_U8>(iq, n_local, pos_base, n_total, chunk, kf, nt, ps, pm, d_sum, d_max, s); break;
-        case URHGPU_DT_I16: sp_mag_launch_dt<URHGPU_DT_I16>(iq, n_local, pos_base, n_total, chunk, kf, nt, ps, pm, d_sum, d_max, s); break;
-        case URHGPU_DT_U16: sp_mag_launch_dt<URHGPU_DT_U16>(iq, n_local, pos_base, n_total, chunk, kf, nt, ps, pm, d_sum, d_max, s); break;
-        default: return URHGPU_ERR_DTYPE;
-    }
-    return URHGPU_OK;
+    return dispatch_dtype(dtype, [&](auto dt) {
+        sp_mag_launch_dt<dt.value>(iq, n_local, pos_base, n_total, chunk, kf, nt, ps, pm, d_sum, d_max, s);
+        return URHGPU_OK;
+    });
 }
 
 // ---- numpy's float32 summation tree from an arbitrary global offset ----------------------------------------------------------------
